@@ -11,13 +11,18 @@ Workload = BASELINE config C4: 10 M sites x 5 000 haplotypes, 2 populations.
           summed by RCCL inside libferromic_hip.so (fmh_hudson_sweep_sharded_begin/_end: finalise on the device, ncclAllReduce
           on the communicator's stream, pipelined one step deep so the reduce of step k overlaps the sweep of step k + 1).
           --scaling strong (default): the 10 M sites are SPLIT over the ranks (the metric's "10M sites, 1 -> 8 GPUs");
-          --scaling weak: every rank owns --sites sites of an N x larger cohort.  The other mode is measured in the same run
-          and reported under "secondary".
+          --scaling weak: every rank owns --sites sites of an N x larger cohort.  With --full the other mode is measured in the
+          same run and reported under "secondary".
 
 Launch (N > 1):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                  --master-port P bench.py --gpus N --steps K --warmup W
 or simply `python bench.py --gpus N`: the script then starts that launcher itself, before touching the GPU.
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs: set up, warm up, time --steps steps, print the line.  --full adds what is measured or
+checked beside it: the sweep over the u8 rows (roofline.u8_layout_measured), the C restatement on the CPU (cpu_baseline), with N > 1
+the other scaling mode (secondary) and rank 0's one-GPU sweep of the whole cohort (parity_vs_n1.computed).
+--dump-outputs DIR writes what the last timed step handed its caller as float64 .npy files (see dump_outputs).
 """
 
 from __future__ import annotations
@@ -196,7 +201,7 @@ def parity_vs_n1(args, first, totals, rank, world, local_rank, lib, masks, poc, 
 
     rec = N1_RECORDED.get((first["total_sites"], H, first["seed"]))
     out["recorded"] = dict(compare(rec), source="bench.py N1_RECORDED (N = 1 runs of this cohort)") if rec else None
-    if rank != 0 or args.no_verify_n1:
+    if rank != 0 or args.no_verify_n1 or not args.full:
         return out
     total = first["total_sites"]
     if total * H > 120e9:
@@ -222,6 +227,35 @@ def parity_vs_n1(args, first, totals, rank, world, local_rank, lib, masks, poc, 
     return out
 
 
+DUMP_SITES = 1 << 19  # --dump-outputs: per-site tracks kept over all ranks (10 float64 arrays of 2^19 sites = 42 MB, under the 64 MB cap)
+DUMP_SEED = 20_251_016
+
+
+def dump_outputs(out_dir: str, bufs: dict, S: int, first_site: int, totals, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files - every field of the regional totals
+    (totals_<field>.npy, totals_pop_<field>.npy with one entry per population) and the per-site tracks (sites_alt / sites_called [2][k],
+    sites_dxy / _pi1 / _pi2 / _num / _den [k]) on a fixed, seeded sample of k sites whose global indices are site_index.npy.
+    With N > 1 every rank writes its own slab's files under a rank<r>_ prefix."""
+    from ferromic_amd import _abi
+
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    k = min(S, max(1, DUMP_SITES // world))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False)) if k < S else np.arange(S)
+    arrays = {"site_index": idx + first_site}
+    for name in ("alt", "called"):
+        arrays["sites_" + name] = bufs[name].to_numpy(np.uint32, 2 * S).reshape(2, S)[:, idx]
+    for name in ("dxy", "pi1", "pi2", "num", "den"):
+        arrays["sites_" + name] = bufs[name].to_numpy(np.float64, S)[idx]
+    for field, _ in _abi.HudsonTotals._fields_:
+        if field != "pop":
+            arrays["totals_" + field] = np.array([getattr(totals, field)])
+    for field, _ in _abi.PopTotals._fields_:
+        arrays["totals_pop_" + field] = np.array([getattr(totals.pop[p], field) for p in range(2)])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, pre + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -240,10 +274,10 @@ def parse_args():
                     help="sites of the cohort: the WHOLE cohort with --scaling strong (split over the ranks), per GPU with --scaling weak")
     ap.add_argument("--haplotypes", type=int, default=5000)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
-    ap.add_argument("--no-secondary", action="store_true", help="N > 1: skip the measurement of the other scaling mode")
+    ap.add_argument("--no-secondary", action="store_true", help="N > 1 with --full: skip the measurement of the other scaling mode")
     ap.add_argument("--cpu-sample-sites", type=int, default=1_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = the cores this process may use)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline of --full (0 = the cores this process may use)")
     ap.add_argument("--transport", choices=["rccl", "torch"], default="rccl",
                     help="who sums the accumulators over the ranks: libferromic_hip.so's own RCCL communicator (the product path) or "
                          "torch.distributed (with --backend gloo: the rehearsal of N > 1 on a one-GPU box)")
@@ -252,7 +286,7 @@ def parse_args():
     ap.add_argument("--layout", choices=["packed", "bytes"], default="packed",
                     help="resident layout of the cohort: bit-packed planes (what fmh_matrix_create keeps for alleles 0..3) or the u8 rows")
     ap.add_argument("--u8-reference-steps", type=int, default=5,
-                    help="N = 1 with --layout packed: before the u8 rows are released, time this many sweeps over them (the layout "
+                    help="N = 1 with --layout packed and --full: before the u8 rows are released, time this many sweeps over them (the layout "
                          "north_star names) and report their HBM fraction next to the headline; 0 skips it")
     ap.add_argument("--force-collective", action="store_true",
                     help="run the sharded path (communicator, device-side reduce, pipelining) even with one rank: measures its "
@@ -266,7 +300,7 @@ def parse_args():
                          "(sweep + finalize + D2H as one launch); measures the fixed cost per step against the eager path")
     ap.add_argument("--explicit-stream", action="store_true", help="N = 1: the eager pipelined steps on the same explicit stream (the A side of --graph)")
     ap.add_argument("--no-verify-n1", action="store_true",
-                    help="N > 1, strong scaling: skip rank 0's own sweep of the whole cohort after the timed region (parity_vs_n1.computed)")
+                    help="N > 1, strong scaling, --full: skip rank 0's own sweep of the whole cohort after the timed region (parity_vs_n1.computed)")
     ap.add_argument("--sync-steps", action="store_true",
                     help="N = 1: one blocking fmh_hudson_sweep per step instead of the pipelined begin / end pair on a local communicator")
     ap.add_argument("--single-process", action="store_true",
@@ -278,7 +312,15 @@ def parse_args():
                          "library's in-process host rendezvous (the rehearsal of N > 1 on a one-GPU box)")
     ap.add_argument("--rehearse-on-one-device", action="store_true",
                     help="all ranks share cuda:0 (needs --transport torch --backend gloo): exercises the sharded code path on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the u8-row sweep (--u8-reference-steps), the CPU "
+                         "baseline, with N > 1 the other scaling mode and rank 0's one-GPU sweep of the whole cohort (parity_vs_n1.computed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (regional totals, a seeded sample of the per-site tracks) "
+                         "as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not 1 <= args.pipeline_depth <= 3:  # FMH_SHARDED_IN_FLIGHT - 1: one more and _begin refuses mid-run
         ap.error("--pipeline-depth must be 1, 2 or 3 (the library keeps at most FMH_SHARDED_IN_FLIGHT = 4 sharded sweeps in flight per communicator)")
     return args
@@ -452,6 +494,9 @@ def main_single_process(args) -> int:
     for rep in reports[1:]:  # every rank must hold the same all-rank totals
         t = rep["totals"]
         assert int(t.pop[0].segregating_sites) == int(totals.pop[0].segregating_sites) and t.numerator_sum == totals.numerator_sum, "ranks disagree on the reduced totals"
+    if args.dump_outputs:
+        for rep in reports:
+            dump_outputs(args.dump_outputs, rep["keep"][2], rep["sites"], rep["slab"][0], rep["totals"], rep["rank"], world)
     for rep in reports:
         rep["keep"] = None  # release the slabs before rank 0 sweeps the whole cohort
     result["parity_vs_n1"] = parity_vs_n1(args, {"scaling": args.scaling, "total_sites": total, "seed": first["seed"]}, totals, 0, world, devices[0], lib, masks, poc, N, H)
@@ -622,7 +667,7 @@ def main() -> int:
         # matrix still holds them: its HBM fraction is reported next to the headline; then the rows are released
         u8_reference = None
         if args.layout == "packed":
-            if primary and world == 1 and args.u8_reference_steps > 0 and S > 0:
+            if args.full and primary and world == 1 and args.u8_reference_steps > 0 and S > 0:
                 with _abi.options(FMH_LAYOUT="bytes"):  # fmh_set_option: sweeps take the u8 kernels while the rows exist
                     local = sweep_local()
                     lib.fmh_timing_enable(1)
@@ -674,6 +719,8 @@ def main() -> int:
     first = run_mode(args.scaling, True)
     totals = first["totals"]
     S = first["S"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, first["bufs"], S, first["slab"][0], totals, rank, world)
     value = first["total_sites"] * args.steps / first["elapsed"]
     # ---- N > 1: the line carries its own evidence (who reduced, over what, what every rank did) --------------------------------
     comm_report = None
@@ -694,7 +741,7 @@ def main() -> int:
         else:
             per_rank = [mine]
     secondary = None
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # release the primary cohort, then the other mode on the same ranks
         keep = {k: first[k] for k in ("scaling", "total_sites", "elapsed", "avg_kernel_s", "timed_launches", "S", "seed", "gen_s", "pack_s", "slab")}
         first.clear()
@@ -791,7 +838,7 @@ def main() -> int:
                                           "(every timed step); null when the library's RCCL communicator is not the transport")
         result["parity_vs_n1"] = parity_vs_n1(args, first, totals, rank, world, local_rank, lib, masks, poc, N, H)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         bufs = first["bufs"]
 
         def gpu_check(sample, cpu):

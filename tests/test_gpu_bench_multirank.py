@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +34,7 @@ def test_two_ranks_equal_one_rank():
     weak = run(launch + ["--master-port", "29541", "bench.py", "--gpus", "2", "--sites", str(S), "--scaling", "weak", "--no-secondary"] + rehearse + common)
     assert weak["n_gpus"] == 2 and weak["scaling"] == "weak" and weak["steps"] == 2 and weak["config"]["sites_per_gpu"] == S
     assert weak["value"] == pytest.approx(2 * S * 2 / (weak["ms_per_step"] * 2 / 1e3), rel=1e-6)  # whole-job sites / max-over-ranks time
-    strong = run(launch + ["--master-port", "29542", "bench.py", "--gpus", "2", "--sites", str(2 * S)] + rehearse + common)
+    strong = run(launch + ["--master-port", "29542", "bench.py", "--gpus", "2", "--sites", str(2 * S), "--full"] + rehearse + common)
     assert strong["n_gpus"] == 2 and strong["scaling"] == "strong" and strong["config"]["sites_per_gpu"] == S and strong["config"]["total_sites"] == 2 * S
     assert strong["value"] == pytest.approx(2 * S * 2 / (strong["ms_per_step"] * 2 / 1e3), rel=1e-6)
     assert strong["secondary"]["scaling"] == "weak" and strong["secondary"]["sites_per_gpu"] == 2 * S and strong["secondary"]["total_sites"] == 4 * S
@@ -72,7 +73,7 @@ def test_plain_invocation_launches_its_own_ranks():
 def test_rccl_collective_path_with_one_rank():
     """The sharded path through the library's own RCCL communicator (a one-rank group): sweep, device-side finalise, ncclAllReduce on the
     communicator's stream, pipelined one step deep - same totals as the run without it, and both layouts' roofline blocks present."""
-    common = ["--steps", "4", "--warmup", "1", "--sites", "250000", "--haplotypes", "1000", "--no-cpu-baseline"]
+    common = ["--steps", "4", "--warmup", "1", "--sites", "250000", "--haplotypes", "1000", "--no-cpu-baseline", "--full"]
     plain = run([sys.executable, "bench.py"] + common)
     coll = run([sys.executable, "bench.py", "--force-collective"] + common)
     assert "RCCL" in coll["config"]["parallelism"] and "no collective" in plain["config"]["parallelism"] and "pipelined" in plain["config"]["parallelism"]
@@ -101,12 +102,12 @@ def test_rccl_collective_path_with_one_rank():
     assert u8["roofline"]["algorithmic_bytes_per_site"] == 1056 and u8["dtype"] == "u8"
 
 
-def test_single_process_route():
+def test_single_process_route(tmp_path):
     """`bench.py --single-process`: one process, one host thread per rank, fmh_comm_init_all - the route run_vcf --devices takes, without
     torch.distributed.run or gloo.  [0]: the library's RCCL communicator with one rank; [0, 0]: two ranks on the in-process host rendezvous
     (RCCL cannot place two ranks on one device).  Both carry the same evidence as the launcher route and agree with one plain rank."""
     S = 300_000
-    common = ["--steps", "3", "--warmup", "1", "--haplotypes", "1000", "--no-cpu-baseline", "--sites", str(2 * S)]
+    common = ["--steps", "3", "--warmup", "1", "--haplotypes", "1000", "--no-cpu-baseline", "--sites", str(2 * S), "--full"]
     one = run([sys.executable, "bench.py"] + common)
     rccl = run([sys.executable, "bench.py", "--single-process", "--devices", "0"] + common)
     c = rccl["comm"]
@@ -114,7 +115,7 @@ def test_single_process_route():
     assert c["ranks_reporting"] == 1 and c["per_rank"][0]["slab"] == [0, 2 * S] and c["per_rank"][0]["reduces_timed"] >= 1 and c["per_rank"][0]["reduce_ms_avg"] > 0
     assert rccl["results"] == one["results"] and "launcher" in rccl["config"] and "transport_fallback" not in rccl["config"]
     assert rccl["parity_vs_n1"]["computed"]["ok"] is True
-    host = run([sys.executable, "bench.py", "--single-process", "--gpus", "2", "--devices", "0,0"] + common)
+    host = run([sys.executable, "bench.py", "--single-process", "--gpus", "2", "--devices", "0,0", "--dump-outputs", str(tmp_path)] + common)
     c = host["comm"]
     assert host["n_gpus"] == 2 and c["transport"] == "host" and c["world"] == 2 and c["ranks_reporting"] == 2
     assert [r["rank"] for r in c["per_rank"]] == [0, 1] and [r["slab"] for r in c["per_rank"]] == [[0, S], [S, 2 * S]]
@@ -126,14 +127,21 @@ def test_single_process_route():
     assert host["results"]["hudson_fst"] == pytest.approx(one["results"]["hudson_fst"], rel=1e-9)
     pv = host["parity_vs_n1"]
     assert pv["mode"] == "strong" and pv["computed"]["ok"] is True and pv["computed"]["hudson_fst_rel_err"] <= 1e-9 and pv["computed"]["pi_sum_rel_err"] <= 1e-9
+    # --dump-outputs with two ranks: each rank's sample of its own slab, and the same all-rank totals on both
+    for r in (0, 1):
+        idx = np.load(tmp_path / f"rank{r}_site_index.npy")
+        assert 0 < len(idx) < S and r * S <= idx[0] and idx[-1] < (r + 1) * S and np.all(np.diff(idx) > 0)
+        assert np.load(tmp_path / f"rank{r}_sites_pi1.npy").shape == idx.shape
+        assert np.load(tmp_path / f"rank{r}_totals_pop_segregating_sites.npy").tolist() == host["results"]["segregating_sites"]
+    assert sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)) <= 64 << 20
     weak = run([sys.executable, "bench.py", "--single-process", "--devices", "0,0", "--scaling", "weak", "--steps", "2", "--warmup", "1", "--haplotypes", "400",
                 "--sites", "100000", "--no-cpu-baseline"])
     assert weak["scaling"] == "weak" and weak["config"]["total_sites"] == 200000 and weak["config"]["sites_per_gpu"] == 100000
 
 
 def test_bench_line_contract():
-    """The one JSON line the driver parses: every field of the contract, with the roofline and cpu_baseline objects."""
-    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--sites", "200000", "--haplotypes", "400", "--cpu-sample-sites", "50000"])
+    """The one JSON line the driver parses: every field of the contract, with the roofline and (--full) cpu_baseline objects."""
+    d = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--sites", "200000", "--haplotypes", "400", "--cpu-sample-sites", "50000", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline", "cpu_baseline"):
         assert key in d, key
@@ -146,3 +154,31 @@ def test_bench_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and 1 <= c["cores"] == c["cores_usable"] <= c["cores_visible"] and c["value"] > 0 and c["unit"] == "sites/s" and "sample" in c
     assert c["parity_vs_gpu"]["alt_counts_bit_exact"] is True and c["parity_vs_gpu"]["per_site_f64_max_rel_err"] <= 1e-9
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it (no cpu_baseline, no u8-row sweep); --steps sets the
+    timed steps.  --dump-outputs writes the last timed step's totals and a seeded sample of its per-site tracks: the same files for the
+    same arguments, and the totals the line reports."""
+    common = ["--steps", "3", "--warmup", "1", "--sites", "600000", "--haplotypes", "400"]
+    a = run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / "a")] + common)
+    b = run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / "b")] + common)
+    for d in (a, b):
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(600000 * 3 / (d["ms_per_step"] * 3 / 1e3), rel=1e-6)
+        assert "cpu_baseline" not in d and d["roofline"]["u8_layout_measured"] is None and d["unit"] == "sites/s" and d["dtype"] == "u1"
+    assert a["results"] == b["results"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "site_index.npy" in names and "sites_pi1.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n, x in got.items():
+        assert x.dtype == np.float64
+        assert np.array_equal(x, np.load(tmp_path / "b" / (n + ".npy")), equal_nan=True), n
+    idx = got["site_index"]
+    assert 0 < len(idx) < 600000 and np.all(np.diff(idx) > 0) and idx[-1] < 600000
+    assert got["sites_alt"].shape == (2, len(idx)) and got["sites_dxy"].shape == (len(idx),)
+    assert got["totals_pop_segregating_sites"].tolist() == a["results"]["segregating_sites"]
+    assert got["totals_pop_pi_sum"].tolist() == a["results"]["pi_sum"]
+    assert got["totals_numerator_sum"][0] / got["totals_denominator_sum"][0] == a["results"]["hudson_fst"]
+    # every haplotype of both populations is called (no missing data): 200 per population at every sampled site
+    assert np.all(got["sites_called"] == 200) and np.all(got["sites_alt"] <= 200)

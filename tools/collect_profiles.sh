@@ -43,9 +43,9 @@ for layout, suffix, mode, b_site in (("packed", "", 3, 681), ("bytes", "_u8_layo
 json.dump(out, open(o + "/pmc_traffic.json", "w"), indent=1)
 PY
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json   # on this box's copy of the repo: the bench lines below report the traffic just measured
-step "bench.py (C4, N = 1)"; python3 $R/bench.py --steps 20 --warmup 3 2> $O/c4_bench.err | grep '^{' > $O/c4_bench.json
+step "bench.py (C4, N = 1)"; python3 $R/bench.py --steps 20 --warmup 3 --full 2> $O/c4_bench.err | grep '^{' > $O/c4_bench.json
 step "kernel trace of the same command"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4_trace -o c4 -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline 2> $O/c4_trace.log | grep '^{' > $O/c4_bench_under_rocprof.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4_trace -o c4 -- python3 $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline 2> $O/c4_trace.log | grep '^{' > $O/c4_bench_under_rocprof.json
 python3 $R/tools/summarize_rocprof.py trace $O/c4_trace $O/c4_kernel_stats.csv
 python3 $R/bench.py --steps 10 --warmup 2 --layout bytes --no-cpu-baseline 2>/dev/null | grep '^{' > $O/c4_bench_u8_layout.json
 step "strong-scaling step sizes on one GPU (the per-rank slab of 1, 2, 4, 8 GPUs): blocking fmh_hudson_sweep, the pipelined begin / end path on a local communicator (bench's N = 1 default) and on a one-rank RCCL group"
