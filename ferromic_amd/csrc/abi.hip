@@ -409,10 +409,16 @@ static void free_planes(fmh_matrix* m) {
 // after the planes of a matrix have been written: which rows have a bit above plane 0 (row_hi_kernel) and which have an uncalled column
 // (row_gap_kernel) - the sweeps read the upper / called planes of those rows only.  FMH_ROW_HI=0: no tables, every plane of every row is read
 // as before round 4.  (A matrix of a few thousand rows is swept in one launch-bound round either way: no tables, no extra launches and
-// synchronisation per small region of run_vcf; FMH_ROW_HI=2 builds them for any size - tests.)
+// synchronisation per small region of run_vcf; FMH_ROW_HI=2 builds them for any size - tests.)  A pack that builds no tables drops the ones an
+// earlier pack left: the planes are re-used when max_allele is unchanged, and a table of other bytes would skip rows that need their planes.
 static int mark_upper_plane_rows(fmh_matrix* m) {
   const long long mode = options().row_hi.load();
-  if ((!m->p1 && !m->pc) || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) return FMH_OK;
+  if ((!m->p1 && !m->pc) || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) {
+    pool_free(m->device, m->row_hi);
+    pool_free(m->device, m->row_gap);
+    m->row_hi = m->row_gap = nullptr;
+    return FMH_OK;
+  }
   const int blocks = (int)std::min<size_t>((m->variants * 16 + 255) / 256, 1 << 16);
   hipError_t e = hipSuccess;
   if (m->p1) {
@@ -1387,14 +1393,13 @@ static int wc_slot_sums(DeviceScratch& scratch, hipStream_t st, size_t nslots, s
   return FMH_OK;
 }
 
-// W&C kernel slots follow the padded-P pair order; maps them to the caller's G-group order (a.wc_slot for the kernel's stores,
-// slot_of for the host's unpacking; -1 = a padded group takes part, never reported)
-void fmhi::wc_slot_map(const fmh_matrix* m, const fmh_groups* g, SweepArgs& a, int (&slot_of)[32]) {
-  for (int k = 0; k < 32; ++k) { a.wc_slot[k] = -1; slot_of[k] = -1; }
+// W&C kernel slots follow the padded-P pair order; a.wc_slot maps them to the caller's G-group order, -1 = a padded group takes part, never
+// reported.  The kernel writes per-site tracks AND its regional totals through this map: what reaches the host is in caller order.
+void fmhi::wc_slot_map(const fmh_matrix* m, const fmh_groups* g, SweepArgs& a) {
+  for (int k = 0; k < 32; ++k) a.wc_slot[k] = -1;
   if (!g) return;
   const int P = m ? wc_kernel_groups(m, g) : g->padded, G = g->n_groups;
   a.wc_slot[0] = 0;
-  slot_of[0] = 0;
   int k = 1;
   for (int i = 0; i < P; ++i)
     for (int j = i + 1; j < P; ++j, ++k) {
@@ -1402,8 +1407,7 @@ void fmhi::wc_slot_map(const fmh_matrix* m, const fmh_groups* g, SweepArgs& a, i
         int idx = 1;
         for (int x = 0; x < G; ++x)
           for (int y = x + 1; y < G; ++y, ++idx)
-            if (x == i && y == j) slot_of[k] = idx;
-        a.wc_slot[k] = (int8_t)slot_of[k];
+            if (x == i && y == j) a.wc_slot[k] = (int8_t)idx;
       }
     }
 }
@@ -1430,8 +1434,7 @@ extern "C" int fmh_wc_sweep(const fmh_matrix* m, const fmh_groups* g, size_t row
   a.wc_b = d_b;
   a.wc_state = d_state;
   a.called = d_group_called;
-  int slot_of[32];
-  wc_slot_map(m, g, a, slot_of);
+  wc_slot_map(m, g, a);
   // the fused kernel for 5..8 groups keeps the counts of alleles 0..3 per site; cohorts with alleles beyond 3 take the counts route
   const bool many_alleles8 = m && g && g->padded == 8 && m->max_allele > 3;
   if (m && g && (many_alleles8 || sweep_lds_bytes(g->padded, m->nvec) > wc_lds_limit(m->device, g->padded))) {
@@ -1453,13 +1456,11 @@ extern "C" int fmh_wc_sweep(const fmh_matrix* m, const fmh_groups* g, size_t row
   if (h_totals) {
     memset(h_totals, 0, sizeof *h_totals);
     h_totals->sites_attempted = row_count;
-    const int P = wc_kernel_groups(m, g);
-    const int nw = 1 + P * (P - 1) / 2;
+    const int nw = 1 + g->n_groups * (g->n_groups - 1) / 2;  // (the kernel's totals are in caller slot order)
     for (int k = 0; k < nw; ++k) {
-      if (slot_of[k] < 0) continue;
-      h_totals->sum_a[slot_of[k]] = r.f64[kOffWcA + k];
-      h_totals->sum_b[slot_of[k]] = r.f64[kOffWcB + k];
-      h_totals->informative_sites[slot_of[k]] = r.u64[kOffWcInf + k];
+      h_totals->sum_a[k] = r.f64[kOffWcA + k];
+      h_totals->sum_b[k] = r.f64[kOffWcB + k];
+      h_totals->informative_sites[k] = r.u64[kOffWcInf + k];
     }
   }
   return FMH_OK;

@@ -179,7 +179,7 @@ int pair_region_args(const fmh_groups* g, size_t row_begin, size_t row_count, in
                      const fmh_hudson_sites* sites, fmh::SweepArgs& a, int* mode);
 int harmonic_table(int device, size_t max_k, hipStream_t st, const double** out);
 // W&C slot order of the padded kernel -> the caller's pair order; which W&C / summaries calls are one fused sweep (abi.hip)
-void wc_slot_map(const fmh_matrix* m, const fmh_groups* g, fmh::SweepArgs& a, int (&slot_of)[32]);
+void wc_slot_map(const fmh_matrix* m, const fmh_groups* g, fmh::SweepArgs& a);
 int wc_kernel_groups(const fmh_matrix* m, const fmh_groups* g);
 bool wc_fused_lane_totals(const fmh_matrix* m, const fmh_groups* g);
 bool summaries_single_sweep(const fmh_matrix* m, const fmh_groups* g);

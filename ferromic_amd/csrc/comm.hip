@@ -163,7 +163,6 @@ struct ShardSlot {
   bool busy = false, launched = false, timed = false;
   int kind = 0;          // ShardKind
   int n_groups = 0, padded = 0;
-  int slot_of[32];       // W&C: kernel slot -> caller slot
   uint64_t sizes[FMH_MAX_GROUPS] = {0};
   size_t row_count = 0;
   unsigned long long* h_aux = nullptr;  // pinned: scalars added to the finalised vector before the reduce (W&C sites_attempted)
@@ -707,7 +706,7 @@ extern "C" int fmh_wc_sweep_sharded_begin(fmh_comm* c, const fmh_matrix* m, cons
   a.row_count = row_count;
   a.formula = FMH_FORMULA_SPARSE;
   a.wc_a = d_a; a.wc_b = d_b; a.wc_state = d_state; a.called = d_group_called;
-  wc_slot_map(m, g, a, s.slot_of);
+  wc_slot_map(m, g, a);  // the fused kernel writes its totals in caller slot order, like the counts route below: one layout on every rank
   if (wc_fused_lane_totals(m, g)) return sharded_enqueue(c, m, g, kModeWc, a, (hipStream_t)stream, s, false);
   // alleles beyond 3 with five to eight groups, or rows too wide for all masks at once: the blocking call (the counts route), then the same
   // device-side reduce of its totals, laid out like the fused kernel's vector in CALLER slot order
@@ -718,7 +717,6 @@ extern "C" int fmh_wc_sweep_sharded_begin(fmh_comm* c, const fmh_matrix* m, cons
   const int slots = 1 + g->n_groups * (g->n_groups - 1) / 2;
   for (int k = 0; k < slots; ++k) { s.h_f64[kOffWcA + k] = local.sum_a[k]; s.h_f64[kOffWcB + k] = local.sum_b[k]; s.h_u64[kOffWcInf + k] = local.informative_sites[k]; }
   s.h_u64[kOffWcAttempted] = local.sites_attempted;
-  for (int k = 0; k < 32; ++k) s.slot_of[k] = k < slots ? k : -1;
   return sharded_enqueue(c, m, g, kModeWc, a, (hipStream_t)stream, s, true);
 }
 
@@ -729,12 +727,11 @@ extern "C" int fmh_wc_sweep_sharded_end(fmh_comm* c, fmh_wc_totals* t) {
   if (t) {
     memset(t, 0, sizeof *t);
     t->sites_attempted = s.h_u64[kOffWcAttempted];
-    for (int k = 0; k < 29; ++k) {
-      const int slot = s.slot_of[k];
-      if (slot < 0) continue;
-      t->sum_a[slot] = s.h_f64[kOffWcA + k];
-      t->sum_b[slot] = s.h_f64[kOffWcB + k];
-      t->informative_sites[slot] = s.h_u64[kOffWcInf + k];
+    const int slots = 1 + s.n_groups * (s.n_groups - 1) / 2;
+    for (int k = 0; k < slots; ++k) {
+      t->sum_a[k] = s.h_f64[kOffWcA + k];
+      t->sum_b[k] = s.h_f64[kOffWcB + k];
+      t->informative_sites[k] = s.h_u64[kOffWcInf + k];
     }
   }
   return FMH_OK;

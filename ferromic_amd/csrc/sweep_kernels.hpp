@@ -1322,10 +1322,18 @@ __device__ __forceinline__ void reduce_block_totals(const SweepArgs& A, LaneTota
   if (lane < kMaxU64) s_u64[wave][lane] = 0;
   __syncthreads();
   if constexpr ((MODE & kModeWc) != 0) {
+    // the regional W&C totals land in the CALLER's slot order (A.wc_slot; the slots of a padding group are dropped): the vector then has
+    // one layout whichever kernel a matrix takes (exact or padded group count, or the counts route), and the sharded sweep adds the vectors
+    // of ranks whose slabs took different kernels position by position
     if constexpr (LaneTotals<P, MODE>::kWcLaneTotals) {
       constexpr int NW = 1 + (P * (P - 1)) / 2;
 #pragma unroll
-      for (int k = 0; k < NW; ++k) { put_f64(kOffWcA + k, T.wc_a[k]); put_f64(kOffWcB + k, T.wc_b[k]); put_u64(kOffWcInf + k, T.wc_inf[k]); }
+      for (int k = 0; k < NW; ++k) {
+        const int slot = A.wc_slot[k];
+        const double a = wave_sum(T.wc_a[k]), b = wave_sum(T.wc_b[k]);
+        const unsigned long long n = wave_sum(T.wc_inf[k]);
+        if (lane == 0 && slot >= 0) { s_f64[wave][kOffWcA + slot] = a; s_f64[wave][kOffWcB + slot] = b; s_u64[wave][kOffWcInf + slot] = n; }
+      }
     }
     if constexpr (LaneTotals<P, MODE>::kWcLdsTotals) {  // lane (r, 0) holds this wave's sum of transposition row 16 B + r
 #pragma unroll
@@ -1334,9 +1342,15 @@ __device__ __forceinline__ void reduce_block_totals(const SweepArgs& A, LaneTota
         if ((lane & 3) == 0 && row < LaneTotals<P, MODE>::kWcXposeRows) {
           const double v = wc_xpose_scratch()[wave * kWcXWave + kWcXRows * kWcXStride + row];
           const int k = row / 3, c = row - 3 * k;
-          if (c == 0) s_f64[wave][kOffWcA + k] = v;
-          else if (c == 1) s_f64[wave][kOffWcB + k] = v;
-          else s_u64[wave][kOffWcInf + k] = (unsigned long long)v;  // a count of sites as a sum of 1.0s: exact
+          // (A.wc_slot read at compile-time indices only: a run-time index into the kernel argument puts all of it in scratch)
+          int slot = -1;
+#pragma unroll
+          for (int q = 0; q < 1 + (P * (P - 1)) / 2; ++q)
+            if (q == k) slot = A.wc_slot[q];
+          if (slot < 0) continue;
+          if (c == 0) s_f64[wave][kOffWcA + slot] = v;
+          else if (c == 1) s_f64[wave][kOffWcB + slot] = v;
+          else s_u64[wave][kOffWcInf + slot] = (unsigned long long)v;  // a count of sites as a sum of 1.0s: exact
         }
       }
     }

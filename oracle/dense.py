@@ -28,6 +28,11 @@ class HudsonTotals(C.Structure):
                 ("site_num_sum", C.c_double), ("site_den_sum", C.c_double), ("sites_with_components", C.c_uint64)]
 
 
+class HudsonGeneralTotals(C.Structure):
+    _fields_ = [("site_num_sum", C.c_double), ("site_den_sum", C.c_double), ("site_dxy_sum", C.c_double),
+                ("sites_with_components", C.c_uint64), ("site_dxy_skipped", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -43,6 +48,9 @@ def load():
         lib.fo_hudson_sweep_threaded.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz] + [vp] * 10 + [
             C.POINTER(PopTotals), C.POINTER(HudsonTotals), i]
         lib.fo_hudson_sweep_threaded.restype = None
+        lib.fo_hudson_sweep_general_threaded.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz] + [vp] * 10 + [
+            C.POINTER(PopTotals), C.POINTER(HudsonGeneralTotals), i]
+        lib.fo_hudson_sweep_general_threaded.restype = None
         lib.fo_wc_sites_threaded.argtypes = [vp, vp, sz, sz, vp, i, vp, vp, vp, vp, vp, vp, i]
         lib.fo_wc_sites_threaded.restype = None
         _lib = lib
@@ -98,25 +106,55 @@ def hudson_sweep(data: np.ndarray, missing_words: Optional[np.ndarray], variants
                     totals={k: getattr(tot, k) for k, _ in HudsonTotals._fields_})
 
 
+def hudson_sweep_general(data: np.ndarray, missing_words: Optional[np.ndarray], variants: int, stride: int,
+                         offsets1: np.ndarray, offsets2: np.ndarray, nthreads: int = 1, want_sites: bool = True) -> SweepOut:
+    """fo_hudson_sweep_general_threaded: dense_hudson_sites_general (the reference's arm for every row of a matrix declared with
+    max_allele > 1) per site, the general arms' per-population totals (segregating = a second allele among the called entries,
+    uncallable = fewer than two calls, pi_sum) and the per-site sums (site_num_sum, site_den_sum, sites_with_components,
+    site_dxy_sum, site_dxy_skipped).  alt / called: build_dense_population_summary's gather (alt = sum of the allele values)."""
+    o1 = np.ascontiguousarray(offsets1, dtype=np.uint64)
+    o2 = np.ascontiguousarray(offsets2, dtype=np.uint64)
+    alt = np.empty((2, variants), dtype=np.uint32)
+    called = np.empty((2, variants), dtype=np.uint32)
+    tracks = [np.empty(variants, dtype=np.float64) if want_sites else None for _ in range(6)]
+    pop = (PopTotals * 2)()
+    tot = HudsonGeneralTotals()
+    load().fo_hudson_sweep_general_threaded(_p(data), _p(missing_words), variants, stride, _p(o1), o1.size, _p(o2), o2.size,
+                                            _p(alt[0]), _p(called[0]), _p(alt[1]), _p(called[1]),
+                                            *[_p(t) for t in tracks], pop, C.byref(tot), nthreads)
+    return SweepOut(alt, called, *tracks,
+                    pop=[{k: getattr(pop[i], k) for k, _ in PopTotals._fields_} for i in range(2)],
+                    totals={k: getattr(tot, k) for k, _ in HudsonGeneralTotals._fields_})
+
+
+def hudson_sweep_dense(data: np.ndarray, missing_words: Optional[np.ndarray], variants: int, stride: int, max_allele: int,
+                       offsets1: np.ndarray, offsets2: np.ndarray, nthreads: int = 1, want_sites: bool = True) -> SweepOut:
+    """dense_hudson_sites' choice (stats.rs:3060-3070): the biallelic sweep for a matrix declared max_allele <= 1, else the general twin."""
+    f = hudson_sweep if max_allele <= 1 else hudson_sweep_general
+    return f(data, missing_words, variants, stride, offsets1, offsets2, nthreads, want_sites)
+
+
 @dataclass
 class WcOut:
-    a: np.ndarray       # [slots][S]; slot 0 = overall, then pairs (0,1), (0,2), ...
-    b: np.ndarray
-    state: np.ndarray   # 0 calculable, 1 indeterminate, 2 no variance, 3 insufficient
+    a: Optional[np.ndarray]       # [slots][S]; slot 0 = overall, then pairs (0,1), (0,2), ...  (None: sites=False)
+    b: Optional[np.ndarray]
+    state: Optional[np.ndarray]   # 0 calculable, 1 indeterminate, 2 no variance, 3 insufficient
     sum_a: np.ndarray
     sum_b: np.ndarray
     informative: np.ndarray
 
 
 def wc_sites(data: np.ndarray, missing_words: Optional[np.ndarray], variants: int, stride: int, group_of_column: np.ndarray,
-             n_groups: int, nthreads: int = 1) -> WcOut:
-    """fo_wc_sites_threaded: Weir & Cockerham per site + regional sums (stats.rs:1814-2032, 2145-2374) on a dense matrix."""
+             n_groups: int, nthreads: int = 1, sites: bool = True) -> WcOut:
+    """fo_wc_sites_threaded: Weir & Cockerham per site + regional sums (stats.rs:1814-2032, 2145-2374) on a dense matrix.
+    sites=False: no per-site arrays, only the regional sums and informative counts (each thread's range summed in site order, the
+    ranges added in order: nthreads=1 gives the reference's serial sums)."""
     goc = np.ascontiguousarray(group_of_column, dtype=np.uint8)
-    assert goc.size == stride and 2 <= n_groups <= 16
+    assert goc.size == stride and 2 <= n_groups <= 32
     slots = 1 + n_groups * (n_groups - 1) // 2
-    a = np.empty((slots, variants), dtype=np.float64)
-    b = np.empty((slots, variants), dtype=np.float64)
-    st = np.empty((slots, variants), dtype=np.uint8)
+    a = np.empty((slots, variants), dtype=np.float64) if sites else None
+    b = np.empty((slots, variants), dtype=np.float64) if sites else None
+    st = np.empty((slots, variants), dtype=np.uint8) if sites else None
     sa, sb, inf = np.zeros(slots), np.zeros(slots), np.zeros(slots, dtype=np.uint64)
     load().fo_wc_sites_threaded(_p(data), _p(missing_words), variants, stride, _p(goc), n_groups, _p(a), _p(b), _p(st), _p(sa), _p(sb),
                                 _p(inf), nthreads)

@@ -327,6 +327,188 @@ void fo_hudson_sweep_threaded(const uint8_t* data, const uint64_t* missing, size
 }
 
 /* ================================================================================================
+ * The general twin: dense_hudson_sites_general (stats.rs:3072-3177) with dense_collect_counts (2823-2880) and the shared dot
+ * product (2557-2590 / 3106-3139), the arm the reference takes for EVERY row of a matrix whose declared max_allele > 1 (3060-3070).
+ * Per population: the counts of the alleles in the order they are first seen along its ascending column offsets, missing entries
+ * skipped; the dot product is driven by the population with fewer distinct alleles (ties: population 1), and its terms are added in
+ * that population's first-seen order.  Pinned to oracle/ferromic_ref.py bit for bit by tests/test_oracle_dense_c.py.
+ * ================================================================================================ */
+typedef struct {
+  size_t called;
+  double sum_counts_sq;
+  int k;                 /* distinct alleles */
+  uint8_t allele[256];   /* first-seen order */
+  size_t count[256];
+  int16_t slot_of[256];  /* allele -> index in allele[], -1 = not seen (reset after each row) */
+} dense_counts;
+
+static void dense_collect_counts_c(const uint8_t* data, const uint64_t* missing, size_t base, const size_t* offsets, size_t n_off, dense_counts* c) {
+  c->k = 0;
+  size_t called = 0;
+  for (size_t i = 0; i < n_off; ++i) {
+    const size_t idx = base + offsets[i];
+    if (missing && dense_missing(missing, idx)) continue;
+    const uint8_t a = data[idx];
+    if (c->slot_of[a] < 0) { c->slot_of[a] = (int16_t)c->k; c->allele[c->k] = a; c->count[c->k] = 0; ++c->k; }
+    c->count[c->slot_of[a]] += 1;
+    ++called;
+  }
+  c->called = called; /* without missing words: every offset is called (len(offsets)) */
+  double ss = 0.0;
+  for (int i = 0; i < c->k; ++i) ss += (double)c->count[i] * (double)c->count[i];
+  c->sum_counts_sq = ss;
+}
+
+static void dense_counts_reset(dense_counts* c) {
+  for (int i = 0; i < c->k; ++i) c->slot_of[c->allele[i]] = -1;
+  c->k = 0;
+}
+
+static double dense_dot_c(const dense_counts* c1, const dense_counts* c2) {
+  const double inv1 = 1.0 / (double)c1->called, inv2 = 1.0 / (double)c2->called;
+  double dot = 0.0;
+  if (c1->k <= c2->k) {
+    for (int i = 0; i < c1->k; ++i) {
+      const size_t a = c1->count[i];
+      if (a == 0) continue;
+      const int j = c2->slot_of[c1->allele[i]];
+      const size_t b = j < 0 ? 0 : c2->count[j];
+      if (b != 0) dot += ((double)a * inv1) * ((double)b * inv2);
+    }
+  } else {
+    for (int j = 0; j < c2->k; ++j) {
+      const size_t b = c2->count[j];
+      if (b == 0) continue;
+      const int i = c1->slot_of[c2->allele[j]];
+      const size_t a = i < 0 ? 0 : c1->count[i];
+      if (a != 0) dot += ((double)a * inv1) * ((double)b * inv2);
+    }
+  }
+  return dot;
+}
+
+typedef struct { /* hudson_component_sums (1625-1635) and calculate_dxy_dense's sum / skipped sites (2526-2611) */
+  double site_num_sum, site_den_sum, site_dxy_sum;
+  uint64_t sites_with_components, site_dxy_skipped;
+} fo_hudson_general_totals;
+
+typedef struct {
+  const uint8_t* data;
+  const uint64_t* missing;
+  size_t stride, s0, s1;
+  const size_t *off1, *off2;
+  size_t n1, n2;
+  uint32_t *alt1, *called1, *alt2, *called2;
+  double *fst, *dxy, *pi1, *pi2, *num, *den;
+  fo_pop_totals p1, p2;
+  fo_hudson_general_totals h;
+} general_job;
+
+static void* general_worker(void* p) {
+  general_job* j = (general_job*)p;
+  dense_counts* c = (dense_counts*)malloc(2 * sizeof(dense_counts));
+  if (!c) abort();
+  for (int q = 0; q < 2; ++q) { memset(c[q].slot_of, 0xFF, sizeof c[q].slot_of); c[q].k = 0; }
+  /* alt / called per site: build_dense_population_summary's gather (1367-1470), as the C sweep above */
+  fo_pop_totals unused;
+  fo_population_summary_range(j->data, j->missing, j->stride, j->s0, j->s1, j->off1, j->n1, j->alt1, j->called1, &unused);
+  fo_population_summary_range(j->data, j->missing, j->stride, j->s0, j->s1, j->off2, j->n2, j->alt2, j->called2, &unused);
+  memset(&j->h, 0, sizeof j->h);
+  memset(&j->p1, 0, sizeof j->p1);
+  memset(&j->p2, 0, sizeof j->p2);
+  for (size_t v = j->s0; v < j->s1; ++v) {
+    const size_t base = v * j->stride;
+    dense_collect_counts_c(j->data, j->missing, base, j->off1, j->n1, &c[0]);
+    dense_collect_counts_c(j->data, j->missing, base, j->off2, j->n2, &c[1]);
+    const size_t n1 = c[0].called, n2 = c[1].called;
+    double pi1 = NAN, pi2 = NAN, dxy = NAN;
+    const int ok1 = n1 >= 2, ok2 = n2 >= 2, okd = n1 != 0 && n2 != 0;
+    if (ok1) pi1 = (double)n1 / ((double)n1 - 1.0) * (1.0 - c[0].sum_counts_sq / ((double)n1 * (double)n1));
+    if (ok2) pi2 = (double)n2 / ((double)n2 - 1.0) * (1.0 - c[1].sum_counts_sq / ((double)n2 * (double)n2));
+    if (okd) {
+      dxy = 1.0 - dense_dot_c(&c[0], &c[1]);
+      if (dxy < 0.0) dxy = 0.0;
+      if (dxy > 1.0) dxy = 1.0;
+    }
+    /* fst_components (1736-1757 == 3143-3158) */
+    double f = NAN, nc = NAN, dc = NAN;
+    if (okd && ok1 && ok2) {
+      if (dxy > FST_EPSILON) {
+        const double numv = dxy - 0.5 * (pi1 + pi2);
+        f = numv / dxy; nc = numv; dc = dxy;
+      } else if (fabs(0.5 * (pi1 + pi2)) <= FST_EPSILON) {
+        nc = 0.0; dc = 0.0;
+      }
+    }
+    if (j->fst) j->fst[v] = f;
+    if (j->dxy) j->dxy[v] = dxy;
+    if (j->pi1) j->pi1[v] = pi1;
+    if (j->pi2) j->pi2[v] = pi2;
+    if (j->num) j->num[v] = nc;
+    if (j->den) j->den[v] = dc;
+    if (!isnan(nc)) { j->h.site_num_sum += nc; j->h.site_den_sum += dc; j->h.sites_with_components += 1; }
+    if (okd) j->h.site_dxy_sum += dxy; else j->h.site_dxy_skipped += 1;
+    /* the general arms of count_segregating_sites_dense (3891-4084: a second allele among the called entries) and
+     * calculate_pi_dense (4434-4597: pi of every site with two calls, the others skipped) */
+    if (c[0].k >= 2) j->p1.segregating_sites += 1;
+    if (c[1].k >= 2) j->p2.segregating_sites += 1;
+    if (ok1) j->p1.pi_sum += pi1; else j->p1.uncallable_sites += 1;
+    if (ok2) j->p2.pi_sum += pi2; else j->p2.uncallable_sites += 1;
+    dense_counts_reset(&c[0]);
+    dense_counts_reset(&c[1]);
+  }
+  free(c);
+  return NULL;
+}
+
+/*
+ * dense_hudson_sites_general over every row, site ranges over pthreads (partials combined in range order).  Per-site arrays have
+ * `variants` entries (f64 tracks may be NULL; NaN = None).  alt / called: build_dense_population_summary's per-site gather (alt = the
+ * SUM of the allele values; the reference builds that summary only for max_allele <= 1, so alt is the reference's only on biallelic
+ * rows).  pop_totals: the general arms' segregating sites, sites with fewer than two calls, and the sum of the per-site pi.
+ */
+void fo_hudson_sweep_general_threaded(const uint8_t* data, const uint64_t* missing, size_t variants, size_t stride, const size_t* off1, size_t n1,
+                                      const size_t* off2, size_t n2, uint32_t* alt1, uint32_t* called1, uint32_t* alt2, uint32_t* called2,
+                                      double* fst, double* dxy, double* pi1, double* pi2, double* num, double* den,
+                                      fo_pop_totals* pop_totals /*[2]*/, fo_hudson_general_totals* totals, int nthreads) {
+  if (nthreads < 1) nthreads = 1;
+  if ((size_t)nthreads > variants) nthreads = variants ? (int)variants : 1;
+  pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * nthreads);
+  general_job* jobs = (general_job*)calloc(nthreads, sizeof(general_job));
+  if (!th || !jobs) abort();
+  for (int t = 0; t < nthreads; ++t) {
+    general_job* j = &jobs[t];
+    j->data = data; j->missing = missing; j->stride = stride;
+    j->s0 = variants * t / nthreads; j->s1 = variants * (t + 1) / nthreads;
+    j->off1 = off1; j->off2 = off2; j->n1 = n1; j->n2 = n2;
+    j->alt1 = alt1; j->called1 = called1; j->alt2 = alt2; j->called2 = called2;
+    j->fst = fst; j->dxy = dxy; j->pi1 = pi1; j->pi2 = pi2; j->num = num; j->den = den;
+    pthread_create(&th[t], NULL, general_worker, j);
+  }
+  memset(totals, 0, sizeof *totals);
+  memset(pop_totals, 0, 2 * sizeof *pop_totals);
+  pop_totals[0].haplotype_capacity = n1;
+  pop_totals[1].haplotype_capacity = n2;
+  for (int t = 0; t < nthreads; ++t) {
+    pthread_join(th[t], NULL);
+    const general_job* j = &jobs[t];
+    pop_totals[0].segregating_sites += j->p1.segregating_sites;
+    pop_totals[0].uncallable_sites += j->p1.uncallable_sites;
+    pop_totals[0].pi_sum += j->p1.pi_sum;
+    pop_totals[1].segregating_sites += j->p2.segregating_sites;
+    pop_totals[1].uncallable_sites += j->p2.uncallable_sites;
+    pop_totals[1].pi_sum += j->p2.pi_sum;
+    totals->site_num_sum += j->h.site_num_sum;
+    totals->site_den_sum += j->h.site_den_sum;
+    totals->site_dxy_sum += j->h.site_dxy_sum;
+    totals->sites_with_components += j->h.sites_with_components;
+    totals->site_dxy_skipped += j->h.site_dxy_skipped;
+  }
+  free(th);
+  free(jobs);
+}
+
+/* ================================================================================================
  * Weir & Cockerham per site on a dense matrix (stats.rs:1814-2032, 2034-2127, 1781-1812) and the regional
  * sums of calculate_overall_fst_wc (2145-2374), for the full-size C3 parity gate: the Python
  * restatement (oracle/ferromic_ref.py) does ~100 sites per second, this does millions.
@@ -375,21 +557,29 @@ static uint8_t wc_state(double a, double b) {
   return 2;
 }
 
-#define FO_WC_MAX_GROUPS 16
+#define FO_WC_MAX_GROUPS 32
 typedef struct {
   const uint8_t* data;
   const uint64_t* missing;
   size_t stride, s0, s1, variants;
   const uint8_t* group_of_column;
   int G;
-  double *a, *b; /* [slots][variants] */
+  double *a, *b; /* [slots][variants], or NULL: then only part_a / part_b / part_inf (this range's sums, site order) */
   uint8_t* state;
+  double *part_a, *part_b;
+  uint64_t* part_inf;
 } wc_job;
 
 static void* wc_worker(void* pv) {
   wc_job* j = (wc_job*)pv;
   const int G = j->G;
   const int slots = 1 + G * (G - 1) / 2;
+  /* per-site pair slots on the heap: 32 groups make 497 slots, ~8 KB per array */
+  double* pa = (double*)malloc(sizeof(double) * (size_t)slots);
+  double* pb = (double*)malloc(sizeof(double) * (size_t)slots);
+  uint8_t* pseen = (uint8_t*)malloc((size_t)slots);
+  if (!pa || !pb || !pseen) abort();
+  for (int k = 0; k < slots; ++k) { j->part_a[k] = 0.0; j->part_b[k] = 0.0; j->part_inf[k] = 0; }
   for (size_t s = j->s0; s < j->s1; ++s) {
     const size_t base = s * j->stride;
     /* alleles present among ALL called entries (1826-1837), ascending (BTreeSet) */
@@ -397,9 +587,8 @@ static void* wc_worker(void* pv) {
     memset(present, 0, sizeof present);
     for (size_t h = 0; h < j->stride; ++h)
       if (!j->missing || !dense_missing(j->missing, base + h)) present[j->data[base + h]] = 1;
-    double sum_a = 0.0, sum_b = 0.0, pa[FO_WC_MAX_GROUPS * FO_WC_MAX_GROUPS], pb[FO_WC_MAX_GROUPS * FO_WC_MAX_GROUPS];
-    uint8_t pseen[FO_WC_MAX_GROUPS * FO_WC_MAX_GROUPS];
-    memset(pseen, 0, sizeof pseen);
+    double sum_a = 0.0, sum_b = 0.0;
+    memset(pseen, 0, (size_t)slots);
     for (int k = 0; k < slots; ++k) { pa[k] = 0.0; pb[k] = 0.0; }
     int populated = 0;
     for (int target = 0; target < 256; ++target) {
@@ -447,49 +636,71 @@ static void* wc_worker(void* pv) {
           pseen[k] = 1;
         }
     }
-    if (!populated) { /* InsufficientData everywhere (1987-2003) */
-      for (int k = 0; k < slots; ++k) { j->a[(size_t)k * j->variants + s] = 0.0; j->b[(size_t)k * j->variants + s] = 0.0; j->state[(size_t)k * j->variants + s] = 3; }
-      continue;
-    }
-    j->a[s] = sum_a;
-    j->b[s] = sum_b;
-    j->state[s] = wc_state(sum_a, sum_b);
-    for (int k = 1; k < slots; ++k) {
-      const size_t o = (size_t)k * j->variants + s;
-      if (pseen[k]) { j->a[o] = pa[k]; j->b[o] = pb[k]; j->state[o] = wc_state(pa[k], pb[k]); }
-      else { j->a[o] = 0.0; j->b[o] = 0.0; j->state[o] = 3; }
+    for (int k = 0; k < slots; ++k) {
+      /* slot 0: the overall estimate; a pair without both groups called, or a site without any allele, is insufficient (1987-2003) */
+      const int has = populated && (k == 0 || pseen[k]);
+      const double va = !has ? 0.0 : k == 0 ? sum_a : pa[k];
+      const double vb = !has ? 0.0 : k == 0 ? sum_b : pb[k];
+      const uint8_t st = has ? wc_state(va, vb) : 3;
+      if (j->a) {
+        const size_t o = (size_t)k * j->variants + s;
+        j->a[o] = va;
+        j->b[o] = vb;
+        j->state[o] = st;
+      } else if (st != 3) {
+        j->part_a[k] += va;
+        j->part_b[k] += vb;
+        j->part_inf[k] += 1;
+      }
     }
   }
+  free(pa);
+  free(pb);
+  free(pseen);
   return NULL;
 }
 
 /* Per-site a, b, state for every slot (0 = overall, then pairs (0,1),(0,2),...) and the regional sums over the sites whose
- * state is not insufficient, accumulated SERIALLY in site order as the reference does (2222-2229). */
+ * state is not insufficient, accumulated SERIALLY in site order as the reference does (2222-2229).  a, b and state may all be
+ * NULL (many groups over many sites: 26 groups make 326 slots per site): then only the sums and the informative counts, each thread's
+ * site range summed in site order and the ranges added in range order (one thread: the serial sums). */
 void fo_wc_sites_threaded(const uint8_t* data, const uint64_t* missing, size_t variants, size_t stride, const uint8_t* group_of_column,
                           int G, double* a, double* b, uint8_t* state, double* sum_a, double* sum_b, uint64_t* informative, int nthreads) {
   if (G < 2 || G > FO_WC_MAX_GROUPS) return;
+  const int sites = a && b && state;
   if (nthreads < 1) nthreads = 1;
   if ((size_t)nthreads > variants) nthreads = variants ? (int)variants : 1;
+  const int slots = 1 + G * (G - 1) / 2;
   pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)nthreads);
   wc_job* jobs = (wc_job*)malloc(sizeof(wc_job) * (size_t)nthreads);
+  double* parts = (double*)malloc(sizeof(double) * 2 * (size_t)slots * (size_t)nthreads);
+  uint64_t* parts_inf = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)slots * (size_t)nthreads);
+  if (!th || !jobs || !parts || !parts_inf) abort();
   for (int t = 0; t < nthreads; ++t) {
-    wc_job j = {data, missing, stride, variants * (size_t)t / (size_t)nthreads, variants * (size_t)(t + 1) / (size_t)nthreads, variants, group_of_column, G, a, b, state};
+    wc_job j = {data, missing, stride, variants * (size_t)t / (size_t)nthreads, variants * (size_t)(t + 1) / (size_t)nthreads, variants, group_of_column, G,
+                sites ? a : NULL, sites ? b : NULL, sites ? state : NULL, parts + (size_t)(2 * t) * slots, parts + (size_t)(2 * t + 1) * slots,
+                parts_inf + (size_t)t * slots};
     jobs[t] = j;
     pthread_create(&th[t], NULL, wc_worker, &jobs[t]);
   }
   for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
-  free(th);
-  free(jobs);
-  const int slots = 1 + G * (G - 1) / 2;
   for (int k = 0; k < slots; ++k) {
     double sa = 0.0, sb = 0.0;
     uint64_t n = 0;
-    for (size_t s = 0; s < variants; ++s) {
-      const size_t o = (size_t)k * variants + s;
-      if (state[o] != 3) { sa += a[o]; sb += b[o]; ++n; }
+    if (sites) {
+      for (size_t s = 0; s < variants; ++s) {
+        const size_t o = (size_t)k * variants + s;
+        if (state[o] != 3) { sa += a[o]; sb += b[o]; ++n; }
+      }
+    } else {
+      for (int t = 0; t < nthreads; ++t) { sa += jobs[t].part_a[k]; sb += jobs[t].part_b[k]; n += jobs[t].part_inf[k]; }
     }
     sum_a[k] = sa;
     sum_b[k] = sb;
     informative[k] = n;
   }
+  free(th);
+  free(jobs);
+  free(parts);
+  free(parts_inf);
 }

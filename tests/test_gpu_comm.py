@@ -315,6 +315,81 @@ def test_host_transport_device_side_wc_and_summaries(ranks):
         c.close()
 
 
+def test_sharded_wc_when_each_rank_runs_a_different_kernel():
+    """Three ranks whose slabs take three different W&C routes for the same 5, 6 or 7 groups: a biallelic slab with nothing missing
+    (the kernel instantiated for exactly that many groups), one with a single missing call (the kernel padded to eight groups) and one
+    with alleles up to 4 (the counts route).  The reduced vector is added position by position over the ranks, so every route must lay
+    it out in the caller's slot order: every rank's totals equal the whole matrix's fmh_wc_sweep and the C oracle (informative sites
+    exactly, sums to 1e-11)."""
+    from ferromic_amd import _abi, device, sharding
+    from oracle import dense as D
+
+    lib = _abi.load()
+    S, N, ranks = 9_001, 90, 3
+    data, _ = _cohort(S, N, 41)
+    cuts = [sharding.slab_for_rank(S, r, ranks) for r in range(ranks)]
+    b1, e1 = cuts[1]
+    b2, e2 = cuts[2]
+    rng = np.random.default_rng(42)
+    for r in range(b2, e2, 3):  # slab 2: multi-allelic rows up to allele 4
+        data[r] = np.where(rng.random(2 * N) < 0.5, data[r], rng.integers(0, 5, size=2 * N)).astype(np.uint8)
+    data[b2 + 1, 7] = 4
+    miss = np.zeros((S, 2 * N), dtype=bool)
+    miss[b1 + 17, 33] = True  # slab 1: one missing call
+    data[miss] = 0
+
+    def words_of(m):
+        w = np.packbits(m.reshape(-1), bitorder="little")
+        return np.frombuffer(np.pad(w, (0, (-w.size) % 8)).tobytes(), dtype="<u8").copy()
+
+    whole = device.DeviceMatrix.from_host(data, words_of(miss), S, N, 2, 4)
+    slabs = [(data[b:e], words_of(miss[b:e]) if miss[b:e].any() else None, int(data[b:e].max())) for b, e in cuts]
+    assert [s[1] is not None for s in slabs] == [False, True, False] and [s[2] for s in slabs] == [1, 1, 4]
+    comms = sharding.Comm.init_all([0] * ranks)
+    try:
+        for G in (5, 6, 7):
+            pop_of_column = np.repeat(np.minimum(np.arange(N) * G // N, G - 1), 2).astype(np.uint8)
+            masks = np.stack([pop_of_column == k for k in range(G)]).astype(np.uint8)
+            slots = 1 + G * (G - 1) // 2
+            ref = _abi.WcTotals()
+            gw = device.Groups(whole, masks)  # (held: the handle must outlive the call)
+            _abi.check(lib.fmh_wc_sweep(whole._h, gw._h, 0, S, None, None, None, None, C.byref(ref), None))
+            exp = D.wc_sites(data.reshape(-1), words_of(miss), S, 2 * N, pop_of_column, G, 4)
+            for k in range(slots):
+                assert ref.informative_sites[k] == exp.informative[k], (G, k)
+                assert ref.sum_a[k] == pytest.approx(exp.sum_a[k], rel=1e-11, abs=1e-13), (G, k)
+                assert ref.sum_b[k] == pytest.approx(exp.sum_b[k], rel=1e-11, abs=1e-13), (G, k)
+            out, errors = [None] * ranks, []
+
+            def work(r):
+                try:
+                    d, w, ma = slabs[r]
+                    dm = device.DeviceMatrix.from_host(d, w, d.shape[0], N, 2, ma)
+                    g = device.Groups(dm, masks)
+                    wc = _abi.WcTotals()
+                    _abi.check(lib.fmh_wc_sweep_sharded(comms[r]._h, dm._h, g._h, 0, d.shape[0], None, None, None, None, C.byref(wc), None))
+                    out[r] = wc
+                except Exception as exc:  # noqa: BLE001
+                    errors.append((r, exc))
+
+            threads = [threading.Thread(target=work, args=(r,)) for r in range(ranks)]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join(timeout=300)
+            assert not errors, errors
+            for r in range(ranks):
+                assert out[r].sites_attempted == S
+                for k in range(slots):
+                    assert out[r].informative_sites[k] == exp.informative[k], (G, r, k)
+                    assert out[r].sum_a[k] == pytest.approx(exp.sum_a[k], rel=1e-11, abs=1e-13), (G, r, k)
+                    assert out[r].sum_b[k] == pytest.approx(exp.sum_b[k], rel=1e-11, abs=1e-13), (G, r, k)
+                _wc_equal(out[r], ref, slots, 1e-11)
+    finally:
+        for c in comms:
+            c.close()
+
+
 def test_abort_wakes_the_peers_instead_of_hanging():
     """A rank that fails before its collective calls fmh_comm_abort: the peers blocked in the in-process rendezvous return an error
     (they used to wait for ever), and every later collective on the group is refused."""

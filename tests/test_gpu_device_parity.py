@@ -905,6 +905,95 @@ def test_pack_api_contract(dev):
     assert np.array_equal(s.alt[0], ((data == 1) & ~miss).sum(axis=1).astype(np.uint32))
 
 
+def test_repack_after_the_bytes_change_rebuilds_or_drops_the_row_tables(dev, fmh_opts):
+    """A matrix over memory the caller owns is packed with the row tables (FMH_ROW_HI=2), its bytes are rewritten so that OTHER rows
+    carry alleles 2-3 and OTHER rows carry gaps, and it is packed again under the default (no tables below 4 096 rows) and under
+    FMH_ROW_HI=0.  The planes keep their storage (same max_allele), so a table left over from the first pack would make the sweeps skip
+    the upper / called planes of rows that now need them: dense Hudson, W&C and the summaries must be the oracle's of the new bytes."""
+    import torch
+
+    from oracle import dense as D
+
+    S, N = 2000, 40
+    Hc = 2 * N
+    pitch, bits_pitch = Hc, 12
+    rows = np.arange(S)
+
+    def cohort(seed, multi, gaps):
+        rng = np.random.default_rng(seed)
+        data = (rng.random((S, Hc)) < rng.beta(0.8, 0.8, size=(S, 1))).astype(np.uint8)
+        for r in np.nonzero(multi)[0]:
+            data[r] = np.where(rng.random(Hc) < 0.5, data[r], rng.integers(0, 4, size=Hc)).astype(np.uint8)
+            data[r, int(rng.integers(0, Hc))] = 3
+        miss = np.zeros((S, Hc), dtype=bool)
+        for r in np.nonzero(gaps)[0]:
+            miss[r] = rng.random(Hc) < 0.1
+            miss[r, int(rng.integers(0, Hc))] = True
+        data[miss] = 0
+        called = np.zeros((S, bits_pitch * 8), dtype=np.uint8)
+        called[:, :Hc] = ~miss
+        return data, miss, np.packbits(called, axis=1, bitorder="little")
+
+    old = cohort(1, rows % 7 == 0, rows % 11 == 0)
+    new = cohort(2, (rows % 7 == 3) | (rows == 0) | (rows == S - 1), (rows % 11 == 5) | (rows == 0) | (rows == S - 1))
+    t_data = torch.from_numpy(old[0].copy()).cuda()
+    t_bits = torch.from_numpy(old[2].copy()).cuda()
+    torch.cuda.synchronize()
+    dm = dev.DeviceMatrix.wrap(t_data.data_ptr(), pitch, t_bits.data_ptr(), bits_pitch, S, N, 2, 3)
+
+    data, miss, _ = new
+    bits = np.packbits(miss.reshape(-1), bitorder="little")
+    words = np.frombuffer(np.concatenate([bits, np.zeros((-len(bits)) % 8, np.uint8)]).tobytes(), dtype="<u8").copy()
+    m = R.DenseGenotypeMatrix(bytes(data.reshape(-1)), [int(w) for w in words], S, N, 2, 3)
+    lists2 = [H.haps_for_samples(range(0, 17)), H.haps_for_samples(range(17, N - 1))]
+    off1, off2 = R.dense_membership_offsets(m, lists2[0]), R.dense_membership_offsets(m, lists2[1])
+    exp = R.dense_hudson_sites(m, [R.Variant(i, None) for i in range(S)], off1, off2)
+    goc = np.repeat(np.minimum(np.arange(N) * 3 // N, 2), 2).astype(np.uint8)
+    exp_wc = D.wc_sites(data.reshape(-1), words, S, Hc, goc, 3, 4)
+    L = 10 * S
+
+    for mode in (None, "0"):
+        t_data.copy_(torch.from_numpy(old[0]))
+        t_bits.copy_(torch.from_numpy(old[2]))
+        torch.cuda.synchronize()
+        fmh_opts.setenv("FMH_ROW_HI", "2")
+        dm.pack()
+        t_data.copy_(torch.from_numpy(new[0]))
+        t_bits.copy_(torch.from_numpy(new[2]))
+        torch.cuda.synchronize()
+        if mode is None:
+            fmh_opts.delenv("FMH_ROW_HI")
+        else:
+            fmh_opts.setenv("FMH_ROW_HI", mode)
+        dm.pack()
+        what = f"FMH_ROW_HI={mode or 'default'}"
+        g2 = dev.Groups.from_haplotype_lists(dm, lists2)
+        hs = dev.hudson_sweep(dm, g2, dev.FORMULA_DENSE)
+        H.assert_bits_equal(hs.sites["fst"], [H.opt(x.fst) for x in exp], f"fst {what}")
+        H.assert_bits_equal(hs.sites["dxy"], [H.opt(x.d_xy) for x in exp], f"dxy {what}")
+        H.assert_bits_equal(hs.sites["pi1"], [H.opt(x.pi_pop1) for x in exp], f"pi1 {what}")
+        H.assert_bits_equal(hs.sites["pi2"], [H.opt(x.pi_pop2) for x in exp], f"pi2 {what}")
+        H.assert_bits_equal(hs.sites["num"], [H.opt(x.num_component) for x in exp], f"num {what}")
+        H.assert_bits_equal(hs.sites["den"], [H.opt(x.den_component) for x in exp], f"den {what}")
+        assert np.array_equal(hs.sites["called"][0], np.array([x.n1_called for x in exp], dtype=np.uint32)), what
+        assert np.array_equal(hs.sites["called"][1], np.array([x.n2_called for x in exp], dtype=np.uint32)), what
+        g3 = dev.Groups(dm, np.stack([goc == k for k in range(3)]).astype(np.uint8))
+        w = dev.wc_sweep(dm, g3)
+        assert np.array_equal(w.state, exp_wc.state), what
+        assert np.array_equal(w.a.view(np.uint64), exp_wc.a.view(np.uint64)), what
+        assert np.array_equal(w.b.view(np.uint64), exp_wc.b.view(np.uint64)), what
+        assert np.array_equal(w.informative_sites, exp_wc.informative), what
+        s = dev.population_summaries(dm, g2, dev.FORMULA_DENSE)
+        for p, off in enumerate((off1, off2)):
+            cols = np.array(off, dtype=np.int64)
+            assert np.array_equal(s.called[p], (~miss[:, cols]).sum(axis=1).astype(np.uint32)), what
+            assert np.array_equal(s.alt[p], ((data[:, cols] == 1) & ~miss[:, cols]).sum(axis=1).astype(np.uint32)), what
+            assert s.totals[p]["segregating_sites"] == R.count_segregating_sites_dense(m, off), what
+            assert H.rel_close(s.totals[p]["pi_sum"] / (L - s.totals[p]["uncallable_sites"]), R.calculate_pi_dense(m, off, L)), what
+    fmh_opts.delenv("FMH_ROW_HI")
+    dm.close()
+
+
 @pytest.mark.parametrize("S,N,max_allele,p_missing", [(300, 333, 1, 0.0), (257, 100, 1, 0.07), (130, 700, 3, 0.02), (97, 45, 6, 0.1), (1, 3, 2, 0.0),
                                                        (40_000, 640, 1, 0.01)])
 def test_upload_routes_agree(dev, S, N, max_allele, p_missing):

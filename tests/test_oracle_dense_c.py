@@ -57,7 +57,9 @@ def test_generator_is_deterministic_and_thread_independent():
 
 
 @pytest.mark.parametrize("sites,samples,G,max_allele,p_missing,ungrouped,threads", [
-    (160, 24, 2, 1, 0.0, 0, 1), (140, 31, 4, 1, 0.08, 3, 3), (120, 26, 3, 3, 0.15, 5, 2), (90, 18, 5, 2, 0.5, 2, 4), (40, 9, 2, 1, 0.97, 0, 1)])
+    (160, 24, 2, 1, 0.0, 0, 1), (140, 31, 4, 1, 0.08, 3, 3), (120, 26, 3, 3, 0.15, 5, 2), (90, 18, 5, 2, 0.5, 2, 4), (40, 9, 2, 1, 0.97, 0, 1),
+    # more groups than the fused kernels take, up to a 26-population cohort
+    (60, 40, 9, 1, 0.05, 2, 3), (40, 50, 17, 2, 0.0, 0, 2), (30, 60, 26, 1, 0.03, 1, 4)])
 def test_c_wc_matches_python_oracle(sites, samples, G, max_allele, p_missing, ungrouped, threads):
     """fo_wc_sites_threaded against calculate_fst_wc_at_site_with_membership / calculate_overall_fst_wc, bit for bit:
     per-site a, b and state of the overall slot and of every pair, and the regional sums (serial, site order)."""
@@ -82,6 +84,14 @@ def test_c_wc_matches_python_oracle(sites, samples, G, max_allele, p_missing, un
         goc[2 * s + side] = membership.labels.index(label)
     n_groups = membership.group_count()
     out = D.wc_sites(data.reshape(-1), words, sites, 2 * samples, goc, n_groups, threads)
+    # without per-site arrays: the same informative counts; one thread sums in site order (the same bits), more threads range by range
+    for t in (1, threads):
+        lean = D.wc_sites(data.reshape(-1), words, sites, 2 * samples, goc, n_groups, t, sites=False)
+        assert lean.a is None and np.array_equal(lean.informative, out.informative)
+        if t == 1:
+            assert np.array_equal(lean.sum_a.view(np.uint64), out.sum_a.view(np.uint64)) and np.array_equal(lean.sum_b.view(np.uint64), out.sum_b.view(np.uint64))
+        else:
+            assert np.allclose(lean.sum_a, out.sum_a, rtol=1e-12, atol=1e-15) and np.allclose(lean.sum_b, out.sum_b, rtol=1e-12, atol=1e-15)
     pairs = [(i, j) for i in range(n_groups) for j in range(i + 1, n_groups)]
     states = {"calculable": 0, "components_yield_indeterminate_ratio": 1, "no_inter_population_variance": 2, "insufficient_data_for_estimation": 3}
     site_records = []
@@ -109,3 +119,107 @@ def test_c_wc_matches_python_oracle(sites, samples, G, max_allele, p_missing, un
         if key in agg and pw[key].state != "insufficient_data_for_estimation":
             assert (float(out.sum_a[k]), float(out.sum_b[k])) == agg[key], key
             assert int(out.informative[k]) == pw[key].sites
+
+
+def general_rows(rng, S, samples, half, with_missing):
+    """Multi-allelic rows built to reach every branch of dense_collect_counts / _dense_dot / dense_hudson_sites_general: 3 to 8 distinct
+    alleles met in a different first-seen order by the two populations, population 2 with fewer distinct alleles than population 1 and
+    the reverse (and ties), biallelic rows among them; with missing calls also a missing entry at a population's first member, a
+    population with one called haplotype (pi None) and one with none (dxy None).  Population 1 = columns [0, 2 half), population 2 =
+    columns [2 half, 2 samples - 2) (the last sample in neither)."""
+    Hc = 2 * samples
+    c1, c2 = np.arange(0, 2 * half), np.arange(2 * half, Hc - 2)
+    data = np.zeros((S, Hc), dtype=np.uint8)
+    miss = np.zeros((S, Hc), dtype=bool)
+    for r in range(S):
+        kind = r % 8
+        if kind == 0:    # biallelic row of a multi-allelic matrix: still the general formulas
+            data[r] = rng.random(Hc) < rng.random()
+            continue
+        if kind == 7:    # anything
+            data[r] = rng.integers(0, 8, size=Hc)
+            continue
+        k1 = int(rng.integers(3, 9)) if kind != 3 else int(rng.integers(1, 4))
+        k2 = int(rng.integers(3, 9)) if kind != 4 else int(rng.integers(1, 4))
+        if kind == 5:
+            k2 = k1      # a tie: population 1 drives
+        a1 = rng.permutation(8)[:k1]
+        a2 = rng.permutation(8)[:k2]
+        if kind == 6:
+            a2 = a1[::-1].copy()  # the same alleles, met in the opposite order
+        for cols, al in ((c1, a1), (c2, a2)):
+            v = al[rng.integers(0, len(al), size=len(cols))]
+            v[:len(al)] = al                      # every allele present, in the drawn first-seen order
+            v[len(al):] = rng.permutation(v[len(al):])
+            data[r, cols] = v
+        data[r, Hc - 2:] = rng.integers(0, 8, size=2)
+    if with_missing:
+        miss |= rng.random((S, Hc)) < 0.05
+        for r in range(1, S, 5):
+            miss[r, c1[0]] = True                  # population 1's first member is missing
+        for r in range(2, S, 7):
+            miss[r, c2[0]] = miss[r, c2[1]] = True  # population 2's first sample
+        for r in range(3, S, 11):
+            miss[r, c1[1:]] = True                 # one called haplotype in population 1: pi1 None
+        for r in range(4, S, 13):
+            miss[r, c2] = True                     # nothing called in population 2: dxy None
+        miss[S - 1, c1] = True
+        data[miss] = 0
+    return data, (miss if with_missing else None)
+
+
+@pytest.mark.parametrize("with_missing,threads", [(False, 1), (False, 4), (True, 1), (True, 4)])
+def test_c_general_twin_matches_python_oracle(with_missing, threads):
+    """fo_hudson_sweep_general_threaded (the reference's dense arm for a matrix declared multi-allelic) against dense_hudson_sites_general
+    bit for bit on every track, called counts and the per-site gather exactly, the general arms' per-population totals and the per-site
+    sums against the Python restatement."""
+    S, samples = 480, 33
+    half = 15
+    rng = np.random.default_rng(31 + threads + 10 * with_missing)
+    data, miss = general_rows(rng, S, samples, half, with_missing)
+    words = None
+    if miss is not None:
+        bits = np.packbits(miss.reshape(-1), bitorder="little")
+        words = np.frombuffer(np.concatenate([bits, np.zeros((-len(bits)) % 8, np.uint8)]).tobytes(), dtype="<u8").copy()
+    m = R.DenseGenotypeMatrix(bytes(data.reshape(-1)), None if words is None else [int(w) for w in words], S, samples, 2, int(data.max()))
+    assert m.max_allele == 7
+    h1, h2 = H.haps_for_samples(range(0, half)), H.haps_for_samples(range(half, samples - 1))
+    off1, off2 = R.dense_membership_offsets(m, h1), R.dense_membership_offsets(m, h2)
+    out = D.hudson_sweep_general(data.reshape(-1), words, S, m.stride, off1, off2, threads)
+    exp = R.dense_hudson_sites_general(m, [R.Variant(i, None) for i in range(S)], off1, off2)
+    H.assert_bits_equal(out.fst, [H.opt(x.fst) for x in exp], "fst")
+    H.assert_bits_equal(out.dxy, [H.opt(x.d_xy) for x in exp], "dxy")
+    H.assert_bits_equal(out.pi1, [H.opt(x.pi_pop1) for x in exp], "pi1")
+    H.assert_bits_equal(out.pi2, [H.opt(x.pi_pop2) for x in exp], "pi2")
+    H.assert_bits_equal(out.num, [H.opt(x.num_component) for x in exp], "num")
+    H.assert_bits_equal(out.den, [H.opt(x.den_component) for x in exp], "den")
+    assert np.array_equal(out.called[0], np.array([x.n1_called for x in exp], dtype=np.uint32))
+    assert np.array_equal(out.called[1], np.array([x.n2_called for x in exp], dtype=np.uint32))
+    # the edges the rows were built for are there
+    assert any(x.pi_pop1 is None and x.n1_called == 1 for x in exp) == with_missing
+    assert any(x.d_xy is None for x in exp) == with_missing
+    assert any(x.fst is not None for x in exp)
+    for p, (hl, off) in enumerate(((h1, off1), (h2, off2))):
+        s = R.build_dense_population_summary(m, hl)
+        assert np.array_equal(out.alt[p], np.array(s.alt_counts, dtype=np.uint32))
+        assert np.array_equal(out.called[p], np.array(s.called_counts, dtype=np.uint32))
+        pis = [x.pi_pop1 if p == 0 else x.pi_pop2 for x in exp]
+        assert out.pop[p]["segregating_sites"] == R.count_segregating_sites_dense(m, off)
+        assert out.pop[p]["uncallable_sites"] == sum(1 for v in pis if v is None)
+        assert out.pop[p]["haplotype_capacity"] == len(off)
+        assert H.rel_close(out.pop[p]["pi_sum"], sum(v for v in pis if v is not None), 1e-12)
+        L = 10 * S
+        assert H.rel_close(out.pop[p]["pi_sum"] / (L - out.pop[p]["uncallable_sites"]), R.calculate_pi_dense(m, off, L), 1e-12)
+    ns, ds = R.hudson_component_sums(exp)
+    assert H.rel_close(out.totals["site_num_sum"], ns, 1e-12) and H.rel_close(out.totals["site_den_sum"], ds, 1e-12)
+    assert out.totals["sites_with_components"] == sum(1 for x in exp if x.num_component is not None)
+    assert out.totals["site_dxy_skipped"] == sum(1 for x in exp if x.d_xy is None)
+    L = 10 * S
+    assert H.rel_close(out.totals["site_dxy_sum"] / (L - out.totals["site_dxy_skipped"]), R.calculate_dxy_dense(m, off1, off2, L), 1e-12)
+    # dense_hudson_sites picks this arm by the declared max_allele, also for a matrix whose rows happen to be biallelic
+    bi = (rng.random((50, 2 * samples)) < 0.4).astype(np.uint8)
+    mb = R.DenseGenotypeMatrix(bytes(bi.reshape(-1)), None, 50, samples, 2, 3)
+    eb = R.dense_hudson_sites(mb, [R.Variant(i, None) for i in range(50)], off1, off2)
+    ob = D.hudson_sweep_dense(bi.reshape(-1), None, 50, mb.stride, mb.max_allele, off1, off2, threads)
+    H.assert_bits_equal(ob.dxy, [H.opt(x.d_xy) for x in eb], "dxy, biallelic rows declared multi-allelic")
+    H.assert_bits_equal(ob.pi1, [H.opt(x.pi_pop1) for x in eb], "pi1, biallelic rows declared multi-allelic")
