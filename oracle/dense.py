@@ -33,6 +33,12 @@ class HudsonGeneralTotals(C.Structure):
                 ("sites_with_components", C.c_uint64), ("site_dxy_skipped", C.c_uint64)]
 
 
+class RegionTotals(C.Structure):  # the Hudson fields of fmh_hudson_totals
+    _fields_ = HudsonTotals._fields_ + [("site_dxy_sum", C.c_double), ("site_dxy_skipped", C.c_uint64)]
+
+
+FORMULA_SPARSE, FORMULA_DENSE, FORMULA_SUMMARY = 0, 1, 2  # FMH_FORMULA_*
+
 _lib = None
 
 
@@ -53,6 +59,9 @@ def load():
         lib.fo_hudson_sweep_general_threaded.restype = None
         lib.fo_wc_sites_threaded.argtypes = [vp, vp, sz, sz, vp, i, vp, vp, vp, vp, vp, vp, i]
         lib.fo_wc_sites_threaded.restype = None
+        lib.fo_region_sweep_threaded.argtypes = [vp, vp, sz, sz, i, vp, sz, vp, sz, i, i] + [vp] * 11 + [
+            C.POINTER(PopTotals), C.POINTER(RegionTotals), i]
+        lib.fo_region_sweep_threaded.restype = i
         _lib = lib
     return _lib
 
@@ -159,3 +168,46 @@ def wc_sites(data: np.ndarray, missing_words: Optional[np.ndarray], variants: in
     load().fo_wc_sites_threaded(_p(data), _p(missing_words), variants, stride, _p(goc), n_groups, _p(a), _p(b), _p(st), _p(sa), _p(sb),
                                 _p(inf), nthreads)
     return WcOut(a, b, st, sa, sb, inf)
+
+
+@dataclass
+class RegionOut:
+    alt: np.ndarray         # [2][S] u32: the sum of the allele values (hudson_sweep's gather)
+    called: np.ndarray      # [2][S] u32
+    distinct: np.ndarray    # [2][S] u32
+    site_pi: np.ndarray     # [2][S] f64: calculate_per_site_diversity of each group
+    site_theta: np.ndarray  # [2][S]
+    fst: Optional[np.ndarray]
+    dxy: Optional[np.ndarray]
+    pi1: Optional[np.ndarray]
+    pi2: Optional[np.ndarray]
+    num: Optional[np.ndarray]
+    den: Optional[np.ndarray]
+    pop: list
+    totals: dict
+
+
+def region_sweep(data: np.ndarray, missing_words: Optional[np.ndarray], variants: int, stride: int, max_allele: int,
+                 offsets1: np.ndarray, offsets2: np.ndarray, summary_formula: int, hudson_formula: int = FORMULA_SPARSE,
+                 nthreads: int = 1) -> RegionOut:
+    """fo_region_sweep_threaded: what fmh_pair_region_sweep computes - per site and group called / distinct / alt and the per-site
+    diversity (pi, theta), the six sparse Hudson tracks (hudson_formula = FORMULA_SPARSE; None below 0), the population totals by
+    summary_formula (SPARSE, DENSE: its no-missing biallelic arm when missing_words is None and max_allele <= 1, SUMMARY) and the Hudson
+    fields of fmh_hudson_totals.  Tracks are NaN where the reference has None."""
+    o1 = np.ascontiguousarray(offsets1, dtype=np.uint64)
+    o2 = np.ascontiguousarray(offsets2, dtype=np.uint64)
+    if missing_words is not None:
+        missing_words = np.ascontiguousarray(missing_words, dtype=np.uint64)
+    counts = [np.empty((2, variants), dtype=np.uint32) for _ in range(3)]
+    div = [np.empty((2, variants), dtype=np.float64) for _ in range(2)]
+    tracks = [np.empty(variants, dtype=np.float64) if hudson_formula >= 0 else None for _ in range(6)]
+    pop = (PopTotals * 2)()
+    tot = RegionTotals()
+    rc = load().fo_region_sweep_threaded(_p(np.ascontiguousarray(data, dtype=np.uint8)), _p(missing_words), variants, stride, int(max_allele),
+                                         _p(o1), o1.size, _p(o2), o2.size, int(summary_formula), int(hudson_formula),
+                                         *[_p(a) for a in counts + div + tracks], pop, C.byref(tot), nthreads)
+    if rc != 0:
+        raise ValueError(f"formulas outside the model: summary {summary_formula}, Hudson {hudson_formula}")
+    return RegionOut(*counts, *div, *tracks,
+                     pop=[{k: getattr(pop[i], k) for k, _ in PopTotals._fields_} for i in range(2)],
+                     totals={k: getattr(tot, k) for k, _ in RegionTotals._fields_})

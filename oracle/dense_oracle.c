@@ -704,3 +704,254 @@ void fo_wc_sites_threaded(const uint8_t* data, const uint64_t* missing, size_t v
   free(parts);
   free(parts_inf);
 }
+
+/* ================================================================================================
+ * The fused region sweep (fmh_pair_region_sweep, the one call run_vcf makes per region) on a dense matrix: per site and per group the
+ * called count, the distinct alleles, the alt gather (the SUM of the allele values, as fo_hudson_sweep / fo_hudson_sweep_general), the
+ * per-site diversity of calculate_per_site_diversity (stats.rs:4628-4806: pi = pi_from_components 2723-2733; theta = 1 / H(n - 1) with two
+ * or more distinct alleles, else 0; NaN / NaN below two calls), and - with hudson_formula = SPARSE - the six tracks of
+ * hudson_site_from_variant (2969-3014: dxy_from_counts 2907-2935 adds (c1 inv1)(c2 inv2) over the shared alleles in ascending allele order,
+ * then 1 - dot clamped to [0, 1]; fst_components).  hudson_formula < 0: no Hudson part.  The dense Hudson arm is fo_hudson_sweep[_general].
+ *
+ * Totals, in the layout of fmh_hudson_totals:
+ *   pop[p]     segregating = two or more distinct alleles among the called entries, uncallable = fewer than two calls, pi_sum = the sum of
+ *              the per-site pi of the sites with two calls by summary_formula: SPARSE pi_from_components; DENSE the no-missing biallelic arm
+ *              (stats.rs:4485-4507) when the MATRIX has no missing words and a declared max_allele <= 1, else dense_pi_from_counts over the
+ *              true sum of squared counts (1700-1709 / the general arm 4581-4584); SUMMARY dense_pi_from_counts as well (what the summary
+ *              computes on a biallelic matrix).
+ *   Hudson     site_num_sum / site_den_sum / sites_with_components (hudson_component_sums 1625-1635), site_dxy_sum / site_dxy_skipped
+ *              (calculate_d_xy_hudson's sparse fold 2476-2496), and the fields of aggregate_hudson_components_from_summaries (1554-1623) over
+ *              the alt gather (meaningful at max_allele <= 1 only).  All zero without the Hudson part.
+ *
+ * Model: column h of a row is one haplotype, called unless its missing bit is set, counted where it is.  A genotype whose first haplotype
+ * is missing and whose second is called has no sparse form (process.rs:479-496 makes it None); it counts its called column, as the kernels
+ * and the dense functions above do.  Site ranges over pthreads; each range's sums are added in range order.  Pinned to
+ * oracle/ferromic_ref.py bit for bit by tests/test_oracle_dense_c.py.
+ * ================================================================================================ */
+#define FO_FORMULA_SPARSE 0
+#define FO_FORMULA_DENSE 1
+#define FO_FORMULA_SUMMARY 2
+
+typedef struct { /* the Hudson fields of fmh_hudson_totals, in its order */
+  double numerator_sum, denominator_sum, pi1_sum, pi2_sum, dxy_sum_all;
+  uint64_t dxy_uncallable_sites;
+  double site_num_sum, site_den_sum;
+  uint64_t sites_with_components;
+  double site_dxy_sum;
+  uint64_t site_dxy_skipped;
+} fo_region_totals;
+
+typedef struct {
+  const uint8_t* data;
+  const uint64_t* missing;
+  size_t stride, s0, s1, variants;
+  const size_t* off[2];
+  size_t n_off[2];
+  const double* harmonic;
+  int summary_formula, hudson_formula, nomissing_arm;
+  uint32_t *alt, *called, *distinct; /* [2][variants] */
+  double *site_pi, *site_theta;      /* [2][variants], may be NULL */
+  double *fst, *dxy, *pi1, *pi2, *num, *den;
+  fo_pop_totals p[2];
+  fo_region_totals h;
+} region_job;
+
+/* pi_from_components, stats.rs:2723-2733 (n >= 2) */
+static inline double fo_pi_sparse(size_t total_called, double sum_counts_sq) {
+  const double n = (double)total_called;
+  const double inv_n = 1.0 / n;
+  const double sum_p2 = sum_counts_sq * inv_n * inv_n;
+  return n / (n - 1.0) * (1.0 - sum_p2);
+}
+
+static void* region_worker(void* pv) {
+  region_job* j = (region_job*)pv;
+  size_t* count = (size_t*)calloc(2 * 256, sizeof(size_t));
+  if (!count) abort();
+  memset(&j->h, 0, sizeof j->h);
+  memset(j->p, 0, sizeof j->p);
+  const size_t V = j->variants;
+  for (size_t v = j->s0; v < j->s1; ++v) {
+    const size_t base = v * j->stride;
+    size_t n[2], alt[2];
+    int top = 0;
+    for (int q = 0; q < 2; ++q) {
+      size_t called = 0, sum = 0;
+      size_t* c = count + 256 * q;
+      for (size_t i = 0; i < j->n_off[q]; ++i) {
+        const size_t idx = base + j->off[q][i];
+        if (j->missing && dense_missing(j->missing, idx)) continue;
+        const uint8_t a = j->data[idx];
+        c[a] += 1;
+        sum += a;
+        ++called;
+        if (a > top) top = a;
+      }
+      n[q] = called;
+      alt[q] = sum;
+    }
+    int k[2] = {0, 0};
+    double ssq[2];
+    for (int q = 0; q < 2; ++q) {
+      uint64_t s = 0; /* the integer sum of the squared counts: exact, so every order of the reference's additions gives these bits */
+      for (int a = 0; a <= top; ++a) {
+        const size_t c = count[256 * q + a];
+        if (c) { ++k[q]; s += (uint64_t)c * c; }
+      }
+      ssq[q] = (double)s;
+    }
+    double pi[2];
+    int ok[2];
+    for (int q = 0; q < 2; ++q) {
+      const size_t o = (size_t)q * V + v;
+      j->alt[o] = (uint32_t)alt[q];
+      j->called[o] = (uint32_t)n[q];
+      j->distinct[o] = (uint32_t)k[q];
+      ok[q] = n[q] >= 2;
+      pi[q] = NAN;
+      double tv = NAN;
+      if (ok[q]) {
+        pi[q] = fo_pi_sparse(n[q], ssq[q]);
+        if (k[q] > 1) {
+          const double denom = j->harmonic[n[q] - 1];
+          tv = denom > 0.0 ? 1.0 / denom : 0.0;
+        } else {
+          tv = 0.0;
+        }
+      }
+      if (j->site_pi) j->site_pi[o] = pi[q];
+      if (j->site_theta) j->site_theta[o] = tv;
+      /* the population summary by summary_formula */
+      if (ok[q]) {
+        double pv;
+        if (j->summary_formula == FO_FORMULA_SPARSE) pv = pi[q];
+        else if (j->summary_formula == FO_FORMULA_DENSE && j->nomissing_arm) {
+          if (alt[q] == 0 || alt[q] == n[q]) pv = 0.0;
+          else {
+            const double nf = (double)n[q], scale = nf / (nf - 1.0), inv_n_sq = 1.0 / (nf * nf);
+            const double alt_f = (double)alt[q], ref_f = (double)(n[q] - alt[q]);
+            pv = scale * (1.0 - (ref_f * ref_f + alt_f * alt_f) * inv_n_sq);
+          }
+        } else {
+          const double nf = (double)n[q];
+          pv = nf / (nf - 1.0) * (1.0 - ssq[q] / (nf * nf));
+        }
+        j->p[q].pi_sum += pv;
+      } else {
+        j->p[q].uncallable_sites += 1;
+      }
+      if (k[q] >= 2) j->p[q].segregating_sites += 1;
+    }
+    if (j->hudson_formula == FO_FORMULA_SPARSE) {
+      const int okd = n[0] != 0 && n[1] != 0;
+      double dxy = NAN;
+      if (okd) {
+        const double inv1 = 1.0 / (double)n[0], inv2 = 1.0 / (double)n[1];
+        double dot = 0.0;
+        for (int a = 0; a <= top; ++a) {
+          const size_t c1 = count[a], c2 = count[256 + a];
+          if (c1 != 0 && c2 != 0) dot += ((double)c1 * inv1) * ((double)c2 * inv2);
+        }
+        dxy = 1.0 - dot;
+        if (dxy < 0.0) dxy = 0.0;
+        if (dxy > 1.0) dxy = 1.0;
+      }
+      double f = NAN, nc = NAN, dc = NAN; /* fst_components */
+      if (okd && ok[0] && ok[1]) {
+        if (dxy > FST_EPSILON) {
+          const double numv = dxy - 0.5 * (pi[0] + pi[1]);
+          f = numv / dxy; nc = numv; dc = dxy;
+        } else if (fabs(0.5 * (pi[0] + pi[1])) <= FST_EPSILON) {
+          nc = 0.0; dc = 0.0;
+        }
+      }
+      if (j->fst) j->fst[v] = f;
+      if (j->dxy) j->dxy[v] = dxy;
+      if (j->pi1) j->pi1[v] = pi[0];
+      if (j->pi2) j->pi2[v] = pi[1];
+      if (j->num) j->num[v] = nc;
+      if (j->den) j->den[v] = dc;
+      if (!isnan(nc)) { j->h.site_num_sum += nc; j->h.site_den_sum += dc; j->h.sites_with_components += 1; }
+      if (okd) j->h.site_dxy_sum += dxy; else j->h.site_dxy_skipped += 1;
+    }
+    for (int q = 0; q < 2; ++q)
+      for (int a = 0; a <= top; ++a) count[256 * q + a] = 0;
+  }
+  if (j->hudson_formula == FO_FORMULA_SPARSE) {
+    fo_hudson_totals s;
+    memset(&s, 0, sizeof s);
+    fo_hudson_from_summaries_range(j->alt, j->called, j->alt + V, j->called + V, j->s0, j->s1, &s);
+    j->h.numerator_sum = s.numerator_sum;
+    j->h.denominator_sum = s.denominator_sum;
+    j->h.pi1_sum = s.pi1_sum;
+    j->h.pi2_sum = s.pi2_sum;
+    j->h.dxy_sum_all = s.dxy_sum_all;
+    j->h.dxy_uncallable_sites = s.dxy_uncallable_sites;
+  }
+  free(count);
+  return NULL;
+}
+
+/* Returns 0, or -1 for a formula outside the model (summary_formula not SPARSE / DENSE / SUMMARY, hudson_formula not SPARSE or < 0).
+ * alt, called, distinct: [2][variants] (required); site_pi, site_theta: [2][variants]; the six Hudson tracks: [variants] (all nullable). */
+int fo_region_sweep_threaded(const uint8_t* data, const uint64_t* missing, size_t variants, size_t stride, int max_allele, const size_t* off1,
+                             size_t n1, const size_t* off2, size_t n2, int summary_formula, int hudson_formula, uint32_t* alt, uint32_t* called,
+                             uint32_t* distinct, double* site_pi, double* site_theta, double* fst, double* dxy, double* pi1, double* pi2,
+                             double* num, double* den, fo_pop_totals* pop_totals /*[2]*/, fo_region_totals* totals, int nthreads) {
+  if (summary_formula < FO_FORMULA_SPARSE || summary_formula > FO_FORMULA_SUMMARY) return -1;
+  if (hudson_formula >= 0 && hudson_formula != FO_FORMULA_SPARSE) return -1;
+  if (nthreads < 1) nthreads = 1;
+  if ((size_t)nthreads > variants) nthreads = variants ? (int)variants : 1;
+  /* H_k = sum_{i=1..k} 1/i added in ascending order, harmonic() (stats.rs:4234-4240) */
+  const size_t max_n = n1 > n2 ? n1 : n2;
+  double* harmonic = (double*)malloc(sizeof(double) * (max_n + 1));
+  pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)nthreads);
+  region_job* jobs = (region_job*)calloc((size_t)nthreads, sizeof(region_job));
+  if (!harmonic || !th || !jobs) abort();
+  double hs = 0.0;
+  harmonic[0] = 0.0;
+  for (size_t k = 1; k <= max_n; ++k) {
+    hs += 1.0 / (double)k;
+    harmonic[k] = hs;
+  }
+  for (int t = 0; t < nthreads; ++t) {
+    region_job* j = &jobs[t];
+    j->data = data; j->missing = missing; j->stride = stride; j->variants = variants;
+    j->s0 = variants * (size_t)t / (size_t)nthreads; j->s1 = variants * (size_t)(t + 1) / (size_t)nthreads;
+    j->off[0] = off1; j->off[1] = off2; j->n_off[0] = n1; j->n_off[1] = n2;
+    j->harmonic = harmonic;
+    j->summary_formula = summary_formula; j->hudson_formula = hudson_formula;
+    j->nomissing_arm = missing == NULL && max_allele <= 1;
+    j->alt = alt; j->called = called; j->distinct = distinct; j->site_pi = site_pi; j->site_theta = site_theta;
+    j->fst = fst; j->dxy = dxy; j->pi1 = pi1; j->pi2 = pi2; j->num = num; j->den = den;
+    pthread_create(&th[t], NULL, region_worker, j);
+  }
+  memset(totals, 0, sizeof *totals);
+  memset(pop_totals, 0, 2 * sizeof *pop_totals);
+  pop_totals[0].haplotype_capacity = n1;
+  pop_totals[1].haplotype_capacity = n2;
+  for (int t = 0; t < nthreads; ++t) {
+    pthread_join(th[t], NULL);
+    const region_job* j = &jobs[t];
+    for (int q = 0; q < 2; ++q) {
+      pop_totals[q].segregating_sites += j->p[q].segregating_sites;
+      pop_totals[q].uncallable_sites += j->p[q].uncallable_sites;
+      pop_totals[q].pi_sum += j->p[q].pi_sum;
+    }
+    totals->numerator_sum += j->h.numerator_sum;
+    totals->denominator_sum += j->h.denominator_sum;
+    totals->pi1_sum += j->h.pi1_sum;
+    totals->pi2_sum += j->h.pi2_sum;
+    totals->dxy_sum_all += j->h.dxy_sum_all;
+    totals->dxy_uncallable_sites += j->h.dxy_uncallable_sites;
+    totals->site_num_sum += j->h.site_num_sum;
+    totals->site_den_sum += j->h.site_den_sum;
+    totals->sites_with_components += j->h.sites_with_components;
+    totals->site_dxy_sum += j->h.site_dxy_sum;
+    totals->site_dxy_skipped += j->h.site_dxy_skipped;
+  }
+  free(harmonic);
+  free(th);
+  free(jobs);
+  return 0;
+}

@@ -12,6 +12,7 @@ import pytest
 
 from oracle import dense as D
 from tests import helpers as H
+from tests.helpers import build_cohort, thresholds
 
 pytestmark = pytest.mark.gpu
 
@@ -21,74 +22,6 @@ def dev():
     from ferromic_amd import device
 
     return device
-
-
-def thresholds(S, seed, sigma=0.05):
-    rng = np.random.default_rng(seed)
-    base = rng.beta(0.8, 0.8, size=S)
-    div = rng.normal(0.0, sigma, size=S)
-    return (np.stack([np.clip(base + div, 0.001, 0.999), np.clip(base - div, 0.001, 0.999)]) * (1 << 24)).astype(np.uint32)
-
-
-def pick_rows(rng, S, frac):
-    """A seeded set of rows that always holds the first and the last row and rows on both sides of 64-row tile edges."""
-    edges = np.array([63, 64, 127, 128, 64 * (S // 128) - 1, 64 * (S // 128), 64 * (S // 64) - 1], dtype=np.int64)
-    rows = np.concatenate([[0, S - 1], edges[edges < S], rng.choice(S, size=max(1, int(frac * S)), replace=False)])
-    return np.unique(rows)
-
-
-def set_missing(words, Hc, rows, cols):
-    idx = rows.astype(np.uint64) * np.uint64(Hc) + cols.astype(np.uint64)
-    np.bitwise_or.at(words, (idx >> np.uint64(6)).astype(np.int64), np.uint64(1) << (idx & np.uint64(63)))
-
-
-def build_cohort(S, N, seed, frac_multi, max_allele, frac_gap, cut):
-    """Host bytes [S][2N] and missing words (or None).  Population 1 = samples [0, cut), population 2 = [cut, N - 1).  Among the multi-allelic
-    rows, some are built for the first-occurrence cases of the general D_xy: the two populations meet their alleles in different orders,
-    either one has fewer distinct alleles, a tie; among the gap rows, a missing call at a population's first member, a population with
-    one called haplotype and one with none."""
-    Hc = 2 * N
-    rng = np.random.default_rng(seed)
-    poc = np.repeat((np.arange(N) >= N // 2).astype(np.uint8), 2)
-    data, _ = D.generate(S, Hc, seed, 0, thresholds(S, seed), poc, 0, 16)
-    data = data.reshape(S, Hc)
-    c1, c2 = np.arange(0, 2 * cut), np.arange(2 * cut, Hc - 2)
-    multi = np.zeros(0, dtype=np.int64)
-    if frac_multi > 0:
-        multi = pick_rows(rng, S, frac_multi)
-        sub = data[multi]
-        vals = rng.integers(0, max_allele + 1, size=sub.shape, dtype=np.uint8)
-        sub = np.where(rng.random(sub.shape) < 0.5, sub, vals)
-        sub[np.arange(len(multi)), rng.integers(0, Hc, size=len(multi))] = rng.integers(2, max_allele + 1, size=len(multi))
-        data[multi] = sub
-        for i, r in enumerate(multi[rng.permutation(len(multi))[:300]]):
-            kind = i % 4
-            k1 = int(rng.integers(3, max_allele + 2)) if kind != 1 else int(rng.integers(1, 3))
-            k2 = int(rng.integers(3, max_allele + 2)) if kind != 2 else int(rng.integers(1, 3))
-            if kind == 3:
-                k2 = k1
-            a1 = rng.permutation(max_allele + 1)[:k1]
-            a2 = rng.permutation(max_allele + 1)[:k2] if kind != 3 else a1[::-1].copy()
-            for cols, al in ((c1, a1), (c2, a2)):
-                v = al[rng.integers(0, len(al), size=len(cols))]
-                v[:len(al)] = al
-                data[r, cols] = v
-        data[multi[0], 0] = max_allele  # the declared max_allele is met
-    words = None
-    if frac_gap > 0:
-        words = np.zeros((S * Hc + 63) // 64, dtype=np.uint64)
-        gaps = pick_rows(rng, S, frac_gap)
-        rr, cc = np.nonzero(rng.random((len(gaps), Hc)) < 0.05)
-        rows, cols = [gaps[rr], gaps], [cc, rng.integers(0, Hc, size=len(gaps))]
-        special = gaps[rng.permutation(len(gaps))[:200]]
-        for i, r in enumerate(special):
-            sel = (c1[:1], c2[:1], c1[1:], c2)[i % 4]  # first member of 1 / of 2; one called haplotype in 1; nothing called in 2
-            rows.append(np.full(len(sel), r))
-            cols.append(sel)
-        rows, cols = np.concatenate(rows), np.concatenate(cols)
-        data[rows, cols] = 0
-        set_missing(words, Hc, rows, cols)
-    return data, words, multi
 
 
 def check_hudson(got, exp, general, what):

@@ -1,6 +1,8 @@
 """Pins the C half of the oracle (oracle/dense_oracle.c) to the Python restatement, which is itself
 pinned by the reference's own KATs (tests/test_oracle_golden.py)."""
 
+import random
+
 import numpy as np
 import pytest
 
@@ -223,3 +225,106 @@ def test_c_general_twin_matches_python_oracle(with_missing, threads):
     ob = D.hudson_sweep_dense(bi.reshape(-1), None, 50, mb.stride, mb.max_allele, off1, off2, threads)
     H.assert_bits_equal(ob.dxy, [H.opt(x.d_xy) for x in eb], "dxy, biallelic rows declared multi-allelic")
     H.assert_bits_equal(ob.pi1, [H.opt(x.pi_pop1) for x in eb], "pi1, biallelic rows declared multi-allelic")
+
+
+REGION_CASES = [
+    # (sites, samples, max_allele, p_missing, p_haploid, all_missing_rows)
+    (150, 20, 1, 0.0, 0.0, 0),     # nothing missing: a matrix without missing words (the DENSE summary's no-missing arm)
+    (150, 21, 1, 0.15, 0.05, 2),
+    (120, 33, 2, 0.1, 0.1, 1),
+    (120, 26, 5, 0.08, 0.05, 1),
+    (90, 9, 1, 0.45, 0.1, 0),      # few calls per group: many sites with n < 2 and without any call
+]
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+@pytest.mark.parametrize("sites,samples,max_allele,p_missing,p_haploid,dead", REGION_CASES)
+def test_c_region_sweep_matches_python_oracle(sites, samples, max_allele, p_missing, p_haploid, dead, threads):
+    """fo_region_sweep_threaded (what fmh_pair_region_sweep computes) against the sparse restatement: the six tracks of
+    calculate_hudson_fst_per_site and both groups' calculate_per_site_diversity bit for bit, called / distinct / alt exactly, and the totals
+    against calculate_pi / calculate_pi_dense / build_dense_population_summary, count_segregating_sites_for_haplotypes,
+    hudson_component_sums, calculate_d_xy_hudson and aggregate_hudson_components_from_summaries - equal with one thread (the same additions
+    in the same order), to 1e-12 with more (ranges added in range order)."""
+    rng = random.Random(sites * 7 + samples + max_allele)
+    variants = H.random_sparse_variants(rng, sites, samples, max_allele, p_missing, p_haploid, dead)
+    for i, a in ((sites // 2, 0), (sites // 2 + 1, max_allele), (sites - 1, 1)):  # monomorphic for one allele in both groups: FST 0 / 0
+        variants[i] = R.make_variant(variants[i].position, [None if g is None else [a] * len(g) for g in variants[i].genotypes])
+    m = H.dense_from_variants(variants, samples)
+    words = H.missing_words_np(m)
+    if not words.any():
+        words = None
+    m = R.DenseGenotypeMatrix(m.data, None if words is None else m.missing, sites, samples, m.ploidy, m.max_allele)
+    assert (words is None) == (p_missing == 0 and p_haploid == 0 and dead == 0)
+    data = np.frombuffer(m.data, dtype=np.uint8)
+    third = samples // 3
+    h1 = H.haps_for_samples(range(0, third))
+    h2 = H.haps_for_samples(range(third, 2 * third)) + [(2 * third, 0)]  # one half-sample
+    off1, off2 = R.dense_membership_offsets(m, h1), R.dense_membership_offsets(m, h2)
+    names = [f"s{i}" for i in range(samples)]
+    L = variants[-1].position + 10
+    p1 = R.PopulationContext(0, h1, variants, names, L)
+    p2 = R.PopulationContext(1, h2, variants, names, L)
+    region = R.QueryRegion(0, L)
+    exp = R.calculate_hudson_fst_per_site(p1, p2, region)
+    div = [R.calculate_per_site_diversity(variants, hl, region) for hl in (h1, h2)]
+    mems = [R.HapMembership.build(samples, hl) for hl in (h1, h2)]
+    distinct = [[R.compute_pi_metrics_fast(v, mem)[2] for v in variants] for mem in mems]
+    rows = data.reshape(sites, m.stride)
+
+    def same(a, b):
+        return a == b if threads == 1 else H.rel_close(a, b, 1e-12)
+
+    formulas = [D.FORMULA_SPARSE, D.FORMULA_DENSE] + ([D.FORMULA_SUMMARY] if m.max_allele <= 1 else [])
+    base = None
+    for summary_formula in formulas:
+        out = D.region_sweep(data, words, sites, m.stride, m.max_allele, off1, off2, summary_formula, D.FORMULA_SPARSE, threads)
+        H.assert_bits_equal(out.fst, [H.opt(x.fst) for x in exp], "fst")
+        H.assert_bits_equal(out.dxy, [H.opt(x.d_xy) for x in exp], "dxy")
+        H.assert_bits_equal(out.pi1, [H.opt(x.pi_pop1) for x in exp], "pi1")
+        H.assert_bits_equal(out.pi2, [H.opt(x.pi_pop2) for x in exp], "pi2")
+        H.assert_bits_equal(out.num, [H.opt(x.num_component) for x in exp], "num")
+        H.assert_bits_equal(out.den, [H.opt(x.den_component) for x in exp], "den")
+        assert np.array_equal(out.called[0], np.array([x.n1_called for x in exp], dtype=np.uint32))
+        assert np.array_equal(out.called[1], np.array([x.n2_called for x in exp], dtype=np.uint32))
+        for p, (hl, off) in enumerate(((h1, off1), (h2, off2))):
+            H.assert_bits_equal(out.site_pi[p], [x.pi for x in div[p]], f"site pi group {p}")
+            H.assert_bits_equal(out.site_theta[p], [x.watterson_theta for x in div[p]], f"site theta group {p}")
+            assert np.array_equal(out.distinct[p], np.array(distinct[p], dtype=np.uint32)), p
+            assert np.array_equal(out.alt[p], rows[:, off].sum(axis=1, dtype=np.uint32)), p  # data is 0 under a missing call
+            unc = sum(1 for x in exp if (x.n1_called if p == 0 else x.n2_called) < 2)
+            pop = out.pop[p]
+            assert pop["haplotype_capacity"] == len(off)
+            assert pop["uncallable_sites"] == unc
+            assert pop["segregating_sites"] == R.count_segregating_sites_for_haplotypes(variants, hl)
+            if summary_formula == D.FORMULA_SPARSE:
+                assert same(pop["pi_sum"] / (L - unc), R.calculate_pi(variants, hl, L)), p
+            elif summary_formula == D.FORMULA_DENSE:
+                assert same(pop["pi_sum"] / (L - unc), R.calculate_pi_dense(m, off, L)), p
+            else:
+                assert same(pop["pi_sum"], R.build_dense_population_summary(m, hl).pi_sum), p
+        t = out.totals
+        ns, ds = R.hudson_component_sums(exp)
+        assert same(t["site_num_sum"], ns) and same(t["site_den_sum"], ds)
+        assert t["sites_with_components"] == sum(1 for x in exp if x.num_component is not None)
+        assert t["site_dxy_skipped"] == sum(1 for x in exp if x.d_xy is None)
+        assert same(t["site_dxy_sum"] / (L - t["site_dxy_skipped"]), R.calculate_d_xy_hudson(p1, p2))
+        if m.max_allele <= 1:
+            s = R.aggregate_hudson_components_from_summaries(R.build_dense_population_summary(m, h1), R.build_dense_population_summary(m, h2))
+            for k in ("numerator_sum", "denominator_sum", "pi1_sum", "pi2_sum", "dxy_sum_all"):
+                assert same(t[k], getattr(s, k)), k
+            assert t["dxy_uncallable_sites"] == s.dxy_uncallable_sites
+        base = out
+    # the edges are there
+    assert any(x.n1_called == 1 for x in exp) or p_missing < 0.3
+    assert any(x.d_xy is None for x in exp) or (dead == 0 and p_missing < 0.3)
+    assert any(x.num_component == 0.0 and x.den_component == 0.0 for x in exp)
+    assert any(x.watterson_theta == 0.0 for x in div[0]) and any(x.watterson_theta > 0.0 for x in div[1])
+    # without the Hudson part: no track, Hudson totals zero, the rest unchanged
+    none = D.region_sweep(data, words, sites, m.stride, m.max_allele, off1, off2, formulas[-1], -1, threads)
+    assert none.fst is None and all(v == 0 for v in none.totals.values())
+    assert none.pop == base.pop
+    for k in ("alt", "called", "distinct", "site_pi", "site_theta"):
+        assert np.array_equal(getattr(none, k).view(np.uint64 if k.startswith("site") else np.uint32),
+                              getattr(base, k).view(np.uint64 if k.startswith("site") else np.uint32)), k
+    with pytest.raises(ValueError):
+        D.region_sweep(data, words, sites, m.stride, m.max_allele, off1, off2, D.FORMULA_SPARSE, D.FORMULA_DENSE, threads)
