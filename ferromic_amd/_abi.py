@@ -139,6 +139,10 @@ SYMBOLS = {
     "fmh_wc_sweep": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _P(WcTotals), _vp]),
     "fmh_wc_sweep_many": (_i, [_vp, _vp, _i, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fmh_pairwise_differences": (_i, [_vp, _sz, _vp, _vp, _vp]),
+    "fmh_pca_scan_sites": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
+    "fmh_pca_gram": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmh_pca_eigen_scores": (_i, [_i, _vp, _sz, _sz, _vp, _vp]),
+    "fmh_pca_eigen_host": (_i, [_vp, _sz, _vp]),
     "fmh_hudson_totals_pack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_hudson_totals_unpack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_pop_totals_pack": (_i, [_P(PopTotals), _i, _P(_d), _P(_u64)]),
@@ -169,6 +173,7 @@ SYMBOLS = {
     "fmh_pair_region_sweep_sharded": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _i, _P(PairDiversitySites), _P(HudsonSites), _P(HudsonTotals), _vp]),
     "fmh_timing_read_reduce": (_i, [_P(_d), _P(_u64)]),
     "fmh_timing_reset_reduce": (_i, []),
+    "fmh_timing_read_pca": (_i, [_P(_d)]),
     "fmh_timing_enable": (_i, [_i]),
     "fmh_timing_reset": (_i, []),
     "fmh_timing_read": (_i, [_P(_d), _P(_u64)]),

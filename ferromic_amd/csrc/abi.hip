@@ -86,6 +86,9 @@ const OptionRow kOptionRows[] = {
     {"FMH_WC_BI_REPLICAS", &Options::wc_bi_replicas, 0, nullptr},
     {"FMH_WC_BI_CHUNKS", &Options::wc_bi_chunks, 0, nullptr},
     {"FMH_ROW_HI", &Options::row_hi, 1, nullptr},
+    {"FMH_PCA_EIGEN", &Options::pca_eigen, 0, "host=1,rocsolver=2,auto=0"},
+    {"FMH_PCA_SPLITS", &Options::pca_splits, 0, nullptr},
+    {"FMH_PCA_BUDGET_BYTES", &Options::pca_budget_bytes, (long long)16 << 30, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

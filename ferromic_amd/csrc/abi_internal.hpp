@@ -76,6 +76,9 @@ struct Options {
   std::atomic<long long> wc_bi_replicas{0};      // FMH_WC_BI_REPLICAS: 1 | 2 | 4 | 8 threads per pair in the biallelic pair kernel; 0 = by the lanes the last wave would waste
   std::atomic<long long> wc_bi_chunks{0};        // FMH_WC_BI_CHUNKS: row chunks of the biallelic pair kernel (measurement); 0 = about 8 192 workgroups
   std::atomic<long long> row_hi{1};              // FMH_ROW_HI: 0 = packed matrices get no tables of the rows with alleles above 1 / with uncalled columns (every plane of every row is read); 2 = tables at any size
+  std::atomic<long long> pca_eigen{0};           // FMH_PCA_EIGEN = host | rocsolver: the PCA's symmetric eigen solver; 0 = rocSOLVER, the host solver when it cannot be loaded
+  std::atomic<long long> pca_splits{0};          // FMH_PCA_SPLITS: K splits of the PCA Gram (1 = none); 0 = by the tile count
+  std::atomic<long long> pca_budget_bytes{(long long)16 << 30};  // FMH_PCA_BUDGET_BYTES: device memory one fmh_pca_gram call may use (Gram + bit words + slabs)
   std::atomic<long long> graph{0};               // FMH_GRAPH: 1 = replay a repeated pipelined sweep on a local communicator from a captured hipGraph
   std::atomic<unsigned long long> generation{0}; // bumped by every fmh_set_option: a captured launch is never replayed across an option change
 };

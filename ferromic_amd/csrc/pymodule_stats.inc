@@ -167,7 +167,7 @@ struct PairwiseDifference {
   }
 };
 
-struct ChromosomePcaResult {};  // lib.rs:195-257 — PCA is outside the hot path
+#include "pymodule_pca.inc"
 
 struct DiversitySite {
   int64_t position;
@@ -931,9 +931,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readonly("comparable_sites", &PairwiseDifference::comparable_sites)
       .def("__repr__", &PairwiseDifference::repr);
 
-  py::class_<ChromosomePcaResult>(m, "ChromosomePcaResult").def(py::init([](py::args, py::kwargs) -> ChromosomePcaResult {
-    raise(PyExc_NotImplementedError, "PCA is outside the per-site diversity/FST path implemented by ferromic_amd");
-  }));
+  bind_pca(m);
 
   py::class_<DiversitySite>(m, "DiversitySite")
       .def(py::init([](int64_t p, double pi, double th) { return DiversitySite{p, pi, th}; }), py::arg("position"), py::arg("pi"),
@@ -1075,6 +1073,6 @@ PYBIND11_MODULE(_core, m) {
     g_device.store(device);
   }, py::arg("device"));
   m.def("get_device", []() { return current_device(); });
-  for (const char* name : {"chromosome_pca", "chromosome_pca_to_file", "per_chromosome_pca", "global_pca"})
-    m.def(name, [](py::args, py::kwargs) -> py::object { pca_unavailable(); });
+  // the multi-chromosome driver is not wired up yet: per_chromosome_pca and _combine_pca_results are its two halves
+  m.def("global_pca", [](py::args, py::kwargs) -> py::object { pca_unavailable(); });
 }

@@ -367,3 +367,48 @@ def pairwise_differences(m: DeviceMatrix, n_samples: int):
         _abi.check(lib.fmh_device_zero(m.device, d_both.ptr, 8 * n * n, None))
     _abi.check(lib.fmh_pairwise_differences(m._h, n, d_diff.ptr, d_both.ptr, None))
     return d_diff.to_numpy(np.uint64, n * n).reshape(n, n), d_both.to_numpy(np.uint64, n * n).reshape(n, n)
+
+
+# ---- haplotype PCA (src/pca.rs) -----------------------------------------------------------------------------------------------
+PCA_SITE_UNCALLED = 1
+PCA_SITE_HIGH_ALLELE = 2
+
+
+def pca_scan_sites(m: DeviceMatrix, row_begin: int = 0, row_count: Optional[int] = None):
+    """fmh_pca_scan_sites: per row the count of called allele-1 entries (uint32) and the PCA_SITE_* flags (uint8)."""
+    rc = m.variants - row_begin if row_count is None else row_count
+    d_alt, d_flags = DeviceBuffer(m.device, max(4 * rc, 4)), DeviceBuffer(m.device, max(rc, 1))
+    _abi.check(_abi.load().fmh_pca_scan_sites(m._h, row_begin, rc, d_alt.ptr, d_flags.ptr, None))
+    return d_alt.to_numpy(np.uint32, rc), d_flags.to_numpy(np.uint8, rc)
+
+
+def pca_gram_device(m: DeviceMatrix, kept_rows, set_value, clear_value) -> DeviceBuffer:
+    """fmh_pca_gram into a fresh device buffer of (samples * 2) ** 2 doubles."""
+    kept = np.ascontiguousarray(kept_rows, dtype=np.uint64)
+    hi = np.ascontiguousarray(set_value, dtype=np.float64)
+    lo = np.ascontiguousarray(clear_value, dtype=np.float64)
+    if not (kept.size == hi.size == lo.size):
+        raise ValueError("kept_rows, set_value and clear_value must have one entry per kept site")
+    n = m.samples * 2
+    d_gram = DeviceBuffer(m.device, max(8 * n * n, 8))
+    _abi.check(_abi.load().fmh_pca_gram(m._h, _ptr(kept), kept.size, _ptr(hi), _ptr(lo), d_gram.ptr, None))
+    return d_gram
+
+
+def pca_gram(m: DeviceMatrix, kept_rows, set_value, clear_value) -> np.ndarray:
+    """The standardised haplotype Gram Z Z^T / (n - 1) as an (n, n) float64 array."""
+    n = m.samples * 2
+    return pca_gram_device(m, kept_rows, set_value, clear_value).to_numpy(np.float64, n * n).reshape(n, n)
+
+
+def pca_eigen_scores(device: int, gram, n_components: int):
+    """fmh_pca_eigen_scores of a symmetric (n, n) array or of a DeviceBuffer holding one (overwritten): (eigenvalues descending
+    [n_components], scores [n][n_components])."""
+    if isinstance(gram, DeviceBuffer):
+        buf, n = gram, int(round((gram.nbytes // 8) ** 0.5))
+    else:
+        a = np.ascontiguousarray(gram, dtype=np.float64)
+        buf, n = DeviceBuffer.from_numpy(device, a), a.shape[0]
+    values, scores = np.empty(n_components, dtype=np.float64), np.empty((n, n_components), dtype=np.float64)
+    _abi.check(_abi.load().fmh_pca_eigen_scores(device, buf.ptr, n, n_components, _ptr(values), _ptr(scores)))
+    return values, scores

@@ -338,6 +338,53 @@ int fmh_wc_sweep_many(const fmh_matrix* m, const uint8_t* h_column_mask, int n_g
 int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, unsigned long long* d_diff,
                              unsigned long long* d_both, void* stream);
 
+/* ---- haplotype PCA (src/pca.rs) --------------------------------------------------------------------- */
+/*
+ * The reference's chromosome PCA - rows are HAPLOTYPES (column sample * 2 + side of a diploid matrix), features the sites that pass
+ * its filter - as three calls, so that the Gram can be checked entry by entry, independent of eigenvector conditioning:
+ *
+ * fmh_pca_scan_sites: what the site filter of compute_chromosome_pca{,_from_dense} (pca.rs:46-203, 205-413) needs, per row of
+ *   [row_begin, row_begin + row_count): d_alt_count = called entries whose allele is 1, over all columns; d_flags = FMH_PCA_SITE_UNCALLED
+ *   when some entry is not called | FMH_PCA_SITE_HIGH_ALLELE when some called entry is above 1.  A row with flags 0 is complete and
+ *   biallelic and its count is the reference's allele_sum.  The decision itself (maf = min(f, 1.0 - f) >= 0.05, f = count / n in f64)
+ *   is the caller's, on the host.  Synchronises `stream`.
+ *
+ * fmh_pca_gram: d_gram[n][n] (n = samples * 2; ploidy must be 2) = Z Z^T / (n - 1), where Z[h][k] is h_set_value[k] when haplotype h
+ *   carries allele 1 at row h_kept_rows[k] and h_clear_value[k] otherwise - for the reference's standardisation (pca.rs:579-662) the
+ *   caller passes (1 - mean_k) / sd_k and -mean_k / sd_k.  The kept rows must be complete and biallelic (flags 0).  f64 throughout, on
+ *   the f64 matrix cores; Z is never materialised (the operands are expanded from one bit per entry).  The result is exactly symmetric
+ *   and two calls on the same input give the same bits (split-K partials are summed in a fixed order, no atomics).  Device memory:
+ *   n * n * 8 bytes of output (the caller's) plus scratch of 8 bytes per 64 kept sites and haplotype (haplotypes rounded up to 128)
+ *   and, when K is split, 128 KiB per (tile, split); the sum must stay within FMH_PCA_BUDGET_BYTES (16 GiB unless set), else
+ *   FMH_ERR_UNSUPPORTED.  n < 2 or n_kept == 0: FMH_ERR_INVALID; ploidy != 2: FMH_ERR_UNSUPPORTED.  Scratch comes from the library's
+ *   pool (fmh_device_release_scratch).  Synchronises `stream`.
+ *
+ * fmh_pca_eigen_scores: the n x n symmetric eigenproblem of d_gram (OVERWRITTEN) and pca.rs:751-797: h_eigenvalues[k] = the k-th
+ *   largest eigenvalue, h_scores[i * n_components + k] = U[i][k] * sqrt((n - 1) * lambda_k), a column left zero when lambda_k is
+ *   numerically zero.  The sign of a column is the solver's.  rocSOLVER's rocsolver_dsyevd on the device, bound at run time (dlopen;
+ *   FMH_ROCSOLVER_LIBRARY names a file); option FMH_PCA_EIGEN = host takes a plain Householder + implicit-QL solver on the host, which is
+ *   also the fallback when rocSOLVER cannot be loaded (one warning on stderr: it is O(n^3) on one thread); FMH_PCA_EIGEN = rocsolver
+ *   makes that an error instead.  The call takes no stream: rocSOLVER runs on the NULL stream and the call synchronises it; one
+ *   eigenproblem at a time per device (the cached rocBLAS handle is guarded by a lock).  n <= 46 340.
+ *
+ * fmh_pca_eigen_host: that host solver alone (no device): h_matrix[n][n] symmetric in, column k = unit eigenvector of h_eigenvalues[k]
+ *   out, eigenvalues ascending.
+ *
+ * Options: FMH_PCA_EIGEN (host | rocsolver | auto)   FMH_PCA_SPLITS (K splits of the Gram; 1 = none, 0 = by the tile count)
+ *          FMH_PCA_BUDGET_BYTES
+ */
+/* efficient_pca::pca::NEAR_ZERO_THRESHOLD (pca.rs:2): below it a standard deviation counts as zero (scale 1) and an eigenvalue yields a
+ * zero column.  UNVERIFIED - the crate's source was not available; no kept site and no tested component comes near it. */
+#define FMH_PCA_NEAR_ZERO_THRESHOLD 1e-9
+#define FMH_PCA_SITE_UNCALLED 1
+#define FMH_PCA_SITE_HIGH_ALLELE 2
+int fmh_pca_scan_sites(const fmh_matrix* m, size_t row_begin, size_t row_count, uint32_t* d_alt_count, uint8_t* d_flags, void* stream);
+int fmh_pca_gram(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value,
+                 const double* h_clear_value, double* d_gram /* n x n, n = samples * 2 */, void* stream);
+int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t n_components, double* h_eigenvalues,
+                         double* h_scores /* n x n_components, row-major */);
+int fmh_pca_eigen_host(double* h_matrix, size_t n, double* h_eigenvalues);
+
 /* ---- multi-GPU: region sharding + RCCL reduce of the regional accumulators -------------------------------- */
 /*
  * Sites are independent: rank r of G sweeps only its contiguous slab of the region and writes its own
@@ -466,6 +513,10 @@ int fmh_timing_read_minmax(double* h_min_ms, double* h_max_ms);
  * ncclGroupStart .. ncclGroupEnd - the device-side latency of one 2 x 512-byte reduce. */
 int fmh_timing_read_reduce(double* h_total_ms, uint64_t* h_reduces);
 int fmh_timing_reset_reduce(void);
+/* PCA stage times of the calling thread while timing was enabled, ms by HIP events: [0..2] gather + transpose, Gram, split-K reduce of
+ * the last fmh_pca_gram; [3] the kernel of the last fmh_pca_scan_sites; [4] the eigen solver of the last fmh_pca_eigen_scores
+ * (rocsolver_dsyevd by events, the host solver by the host clock); [5] which solver that was (1 = host, 2 = rocSOLVER; set always). */
+int fmh_timing_read_pca(double* h_stage_ms /*[6]*/);
 
 #ifdef __cplusplus
 }
