@@ -171,6 +171,7 @@ SYMBOLS = {
     "fmh_population_summaries_sharded": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _vp, _vp, _P(PopTotals), _vp]),
     "fmh_pair_region_sweep_sharded_begin": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _i, _P(PairDiversitySites), _P(HudsonSites), _vp]),
     "fmh_pair_region_sweep_sharded": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _i, _P(PairDiversitySites), _P(HudsonSites), _P(HudsonTotals), _vp]),
+    "fmh_pca_gram_sharded": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "fmh_timing_read_reduce": (_i, [_P(_d), _P(_u64)]),
     "fmh_timing_reset_reduce": (_i, []),
     "fmh_timing_read_pca": (_i, [_P(_d)]),

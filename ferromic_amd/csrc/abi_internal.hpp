@@ -187,6 +187,13 @@ int wc_kernel_groups(const fmh_matrix* m, const fmh_groups* g);
 bool wc_fused_lane_totals(const fmh_matrix* m, const fmh_groups* g);
 bool summaries_single_sweep(const fmh_matrix* m, const fmh_groups* g);
 
+// the pieces of fmh_pca_gram_sharded that live beside the Gram (pca.hip): every check of fmh_pca_gram plus `extra_bytes` against the budget,
+// nothing allocated or enqueued (n_kept == 0 is valid here); the upper triangle of an n x n matrix packed / unpacked with the mirror on `st`
+int pca_gram_check(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value, const double* h_clear_value,
+                   double* d_gram, size_t extra_bytes);
+int pca_pack_triangle(const double* d_full, size_t n, double* d_tri, hipStream_t st);
+int pca_unpack_triangle(const double* d_tri, size_t n, double* d_full, hipStream_t st);
+
 // One function per (mask route, lanes per row): dispatches on (P, mode, missing, general) to the instantiation, sizes the
 // persistent grid and launches.  FMH_ERR_UNSUPPORTED for a combination the route does not build.
 int launch_sweep_packed4(int P, int mode, bool missing, bool general, const fmh::SweepArgs& a, size_t smem, hipStream_t st, const LaunchCtx& ctx, int* grid);

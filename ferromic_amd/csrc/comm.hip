@@ -143,6 +143,45 @@ struct HostGroup {
     for (size_t i = 0; i < nu; ++i) u64[i] = ru[i];
     return FMH_OK;
   }
+  // The bulk form (fmh_pca_gram_sharded: the packed triangle of a Gram, tens of megabytes): every rank leaves its own buffer where it is,
+  // the last arriver adds them in rank order into `bulk_sum`, every rank copies the sum back.  Same rendezvous, same abort handling;
+  // the vectors of the small form are set empty so that a rank that entered the other collective is a length mismatch, not a wrong sum.
+  std::vector<double*> bulk;
+  std::vector<size_t> bulk_n;
+  std::vector<double> bulk_sum;
+  int allreduce_bulk(int rank, double* data, size_t count) {
+    std::unique_lock<std::mutex> lock(mu);
+    if (aborted) return fail(FMH_ERR_INVALID, "the communicator was aborted by rank %d: a peer failed before its collective", aborted_by);
+    bulk.resize(n, nullptr);
+    bulk_n.resize(n, 0);
+    bulk[rank] = data;
+    bulk_n[rank] = count;
+    f[rank].clear();
+    u[rank].clear();
+    const uint64_t gen = generation;
+    if (++arrived == n) {
+      mismatch = false;
+      for (int r = 0; r < n; ++r) mismatch |= !bulk[r] || bulk_n[r] != count;
+      if (!mismatch) {
+        bulk_sum.assign(bulk[0], bulk[0] + count);
+        for (int r = 1; r < n; ++r) {
+          const double* src = bulk[r];
+          for (size_t i = 0; i < count; ++i) bulk_sum[i] += src[i];
+        }
+      }
+      for (int r = 0; r < n; ++r) { if (r != rank) bulk[r] = nullptr; }
+      arrived = 0;
+      ++generation;
+      cv.notify_all();
+    } else {
+      cv.wait(lock, [&] { return generation != gen || aborted; });
+      if (aborted && generation == gen) { bulk[rank] = nullptr; return fail(FMH_ERR_INVALID, "the communicator was aborted by rank %d: a peer failed before its collective", aborted_by); }
+    }
+    bulk[rank] = nullptr;
+    if (mismatch) return fail(FMH_ERR_INVALID, "fmh_pca_gram_sharded: the ranks passed matrices of different sample counts (or entered different collectives)");
+    memcpy(data, bulk_sum.data(), count * sizeof(double));  // under the lock, as above
+    return FMH_OK;
+  }
   void abort(int rank) {
     std::lock_guard<std::mutex> lock(mu);
     if (!aborted) { aborted = true; aborted_by = rank; }
@@ -796,6 +835,59 @@ extern "C" int fmh_population_summaries_sharded(fmh_comm* c, const fmh_matrix* m
   if (c && c->head != c->tail) return fail(FMH_ERR_INVALID, "pipelined sharded sweeps are in flight: collect them with their _end first");
   FMH_TRY(fmh_population_summaries_sharded_begin(c, m, g, row_begin, row_count, formula, d_alt, d_called, stream));
   return fmh_population_summaries_sharded_end(c, t);
+}
+
+// ---- the PCA Gram of a cohort whose sites live on several ranks ------------------------------------------------------------------------
+// local Gram (fmh_pca_gram's path, split-K slabs included) -> pack the upper triangle -> sum over the ranks -> unpack with the mirror.
+extern "C" int fmh_pca_gram_sharded(fmh_comm* c, const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value,
+                                    const double* h_clear_value, double* d_gram, void* stream) {
+  if (!c || !m || !d_gram) return fail(FMH_ERR_INVALID, "NULL argument");
+  if (c->aborted) return fail(FMH_ERR_INVALID, "the communicator was aborted");
+  if (m->device != c->device) return fail(FMH_ERR_INVALID, "matrix lives on device %d, the communicator on device %d", m->device, c->device);
+  if (c->pending || c->head != c->tail) return fail(FMH_ERR_INVALID, "another collective is in flight on this communicator: collect it first");
+  const size_t n = m->samples * 2, tri = n * (n + 1) / 2;
+  const bool travels = c->transport != 2;  // a local communicator has nobody to add to
+  FMH_TRY(pca_gram_check(m, h_kept_rows, n_kept, h_set_value, h_clear_value, d_gram, travels ? tri * sizeof(double) : 0));
+  // ---- from here on the rank is part of the collective ----
+  FMH_TRY(use_device(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_kept) FMH_TRY(fmh_pca_gram(m, h_kept_rows, n_kept, h_set_value, h_clear_value, d_gram, stream));
+  else HIP_TRY(hipMemsetAsync(d_gram, 0, n * n * sizeof(double), st));
+  if (!travels) { HIP_TRY(hipStreamSynchronize(st)); return FMH_OK; }
+  DeviceScratch scratch;
+  scratch.device = c->device;
+  scratch.stream = st;
+  double* d_tri = nullptr;
+  FMH_TRY(scratch.get(&d_tri, tri));
+  FMH_TRY(pca_pack_triangle(d_gram, n, d_tri, st));
+  if (c->transport == 0) {
+    // pack (caller's stream) -> ncclAllReduce (communicator's stream) -> unpack (caller's stream), ordered by two events
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipStreamWaitEvent(c->stream, ev[0], 0));
+    const int rc = rccl_reduce_on_stream(c, d_tri, tri, nullptr, 0);
+    if (rc != FMH_OK) { settle_after_failure(c, st); scratch.settled = true; return rc; }
+    HIP_TRY(hipEventRecord(ev[1], c->stream));
+    HIP_TRY(hipStreamWaitEvent(st, ev[1], 0));
+    FMH_TRY(pca_unpack_triangle(d_tri, n, d_gram, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    // ncclCommAbort ends a reduce in flight and the events complete - over an unreduced triangle
+    if (c->world > 1 && c->aborted) return fail(FMH_ERR_INVALID, "the communicator was aborted while the Gram's reduce was in flight");
+    return FMH_OK;
+  }
+  // in-process rendezvous: the triangle goes to the host, is added in rank order, and comes back
+  std::vector<double> h_tri(tri);
+  HIP_TRY(hipMemcpyAsync(h_tri.data(), d_tri, tri * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  FMH_TRY(c->host->allreduce_bulk(c->rank, h_tri.data(), tri));
+  HIP_TRY(hipMemcpyAsync(d_tri, h_tri.data(), tri * sizeof(double), hipMemcpyHostToDevice, st));
+  FMH_TRY(pca_unpack_triangle(d_tri, n, d_gram, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return FMH_OK;
 }
 
 // ---- packing of the totals structs ----------------------------------------------------------------------------------------

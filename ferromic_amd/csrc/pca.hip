@@ -272,8 +272,11 @@ extern "C" int fmh_pca_scan_sites(const fmh_matrix* m, size_t row_begin, size_t 
   return FMH_OK;
 }
 
-extern "C" int fmh_pca_gram(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value, const double* h_clear_value,
-                            double* d_gram, void* stream) {
+namespace {
+// fmh_pca_gram; `extra_bytes` = device memory the caller needs beside it (counted against the budget), `check_only` = return once every
+// argument and the budget have been checked, before anything is allocated or enqueued
+int gram_impl(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value, const double* h_clear_value, double* d_gram,
+              void* stream, size_t extra_bytes, bool check_only) {
   if (!m || !d_gram) return fail(FMH_ERR_INVALID, "NULL argument");
   if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "haplotype PCA needs diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
   const size_t n = m->samples * 2;
@@ -301,13 +304,14 @@ extern "C" int fmh_pca_gram(const fmh_matrix* m, const uint64_t* h_kept_rows, si
   const size_t tile_bytes = (size_t)kPcaTile * kPcaTile * sizeof(double);
   const size_t bits_bytes = kwords * n_pad * sizeof(unsigned long long), vals_bytes = kwords * 64 * sizeof(double2);
   const size_t budget = (size_t)options().pca_budget_bytes.load();
-  auto total_bytes = [&](size_t s) { return n * n * sizeof(double) + bits_bytes + vals_bytes + n_kept * 8 + (s > 1 ? s * tiles * tile_bytes : 0); };
+  auto total_bytes = [&](size_t s) { return n * n * sizeof(double) + bits_bytes + vals_bytes + n_kept * 8 + (s > 1 ? s * tiles * tile_bytes : 0) + extra_bytes; };
   splits = std::min<size_t>(splits, 65535);
   // (the split count is settled against the budget here and re-derived from whole stages below, where it can only shrink)
   if (total_bytes(splits) > budget) splits = 1;
   if (total_bytes(splits) > budget)
     return fail(FMH_ERR_UNSUPPORTED, "PCA of %zu haplotypes x %zu sites needs %zu bytes of device memory, budget %zu (FMH_PCA_BUDGET_BYTES)", n, n_kept,
                 total_bytes(splits), budget);
+  if (check_only) return FMH_OK;
   size_t words_per_split = round_up((kwords + splits - 1) / splits, kPcaStageWords);
   splits = (kwords + words_per_split - 1) / words_per_split;
 
@@ -363,6 +367,45 @@ extern "C" int fmh_pca_gram(const fmh_matrix* m, const uint64_t* h_kept_rows, si
   }
   return FMH_OK;
 }
+}  // namespace
+
+extern "C" int fmh_pca_gram(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value, const double* h_clear_value,
+                            double* d_gram, void* stream) {
+  return gram_impl(m, h_kept_rows, n_kept, h_set_value, h_clear_value, d_gram, stream, 0, false);
+}
+
+// ---- the pieces fmh_pca_gram_sharded (comm.hip) is made of ---------------------------------------------------------------------------
+namespace fmhi {
+
+int pca_gram_check(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value, const double* h_clear_value,
+                   double* d_gram, size_t extra_bytes) {
+  if (n_kept != 0) return gram_impl(m, h_kept_rows, n_kept, h_set_value, h_clear_value, d_gram, nullptr, extra_bytes, true);
+  // a rank without kept sites contributes zeros: the matrix only says how large they are
+  if (!m || !d_gram) return fail(FMH_ERR_INVALID, "NULL argument");
+  if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "haplotype PCA needs diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
+  const size_t n = m->samples * 2;
+  if (n < 2) return fail(FMH_ERR_INVALID, "haplotype PCA needs at least two haplotypes");
+  if (n > ((size_t)1 << 24)) return fail(FMH_ERR_UNSUPPORTED, "PCA cohort too large: %zu haplotypes", n);
+  const size_t need = n * n * sizeof(double) + extra_bytes, budget = (size_t)options().pca_budget_bytes.load();
+  if (need > budget) return fail(FMH_ERR_UNSUPPORTED, "PCA of %zu haplotypes needs %zu bytes of device memory, budget %zu (FMH_PCA_BUDGET_BYTES)", n, need, budget);
+  return FMH_OK;
+}
+
+// n x n row-major <-> its upper triangle, n (n + 1) / 2 doubles; enqueued on `st`, no synchronisation
+int pca_pack_triangle(const double* d_full, size_t n, double* d_tri, hipStream_t st) {
+  const size_t tiles_x = (n + kPcaTriCols - 1) / kPcaTriCols, tiles_y = (n + kPcaTriRows - 1) / kPcaTriRows;
+  hipLaunchKernelGGL(pca_pack_triangle_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, st, d_full, (uint32_t)n, (uint32_t)tiles_x, d_tri);
+  HIP_TRY(hipGetLastError());
+  return FMH_OK;
+}
+int pca_unpack_triangle(const double* d_tri, size_t n, double* d_full, hipStream_t st) {
+  const size_t tiles_x = (n + kPcaTriCols - 1) / kPcaTriCols, tiles_y = (n + kPcaTriRows - 1) / kPcaTriRows;
+  hipLaunchKernelGGL(pca_unpack_triangle_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, st, d_tri, (uint32_t)n, (uint32_t)tiles_x, d_full);
+  HIP_TRY(hipGetLastError());
+  return FMH_OK;
+}
+
+}  // namespace fmhi
 
 extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t n_components, double* h_eigenvalues, double* h_scores) {
   if (!d_gram || !h_eigenvalues || !h_scores) return fail(FMH_ERR_INVALID, "NULL argument");

@@ -262,4 +262,49 @@ __global__ __launch_bounds__(256) void pca_slab_reduce_kernel(const double* __re
   pca_store_entry(gram, n, row, col, sum / denom);
 }
 
+// ---- upper triangle <-> full matrix (fmh_pca_gram_sharded: only the triangle travels between the ranks) ----------------------------
+// Packed layout: row i holds columns i..n-1 at offset i n - i (i - 1) / 2, n (n + 1) / 2 doubles in all.  Both kernels are streams
+// over kPcaTriRows x kPcaTriCols tiles of the FULL matrix, one workgroup per tile (the grid follows the bytes, whatever n is): a
+// thread owns two neighbouring columns of one row, so consecutive lanes run along a row and a pair moves as one 16-byte access when
+// its address is 16-byte aligned.  No LDS, no scratch.
+constexpr int kPcaTriRows = 16, kPcaTriCols = 32;
+
+__device__ inline size_t pca_tri_offset(size_t i, size_t n) { return i * n - i * (i - 1) / 2 - i; }  // + column = index of (i, column)
+
+// full[n][n] -> tri: tiles wholly below the diagonal have nothing to write
+__global__ __launch_bounds__(256) void pca_pack_triangle_kernel(const double* __restrict__ full, uint32_t n, uint32_t tiles_x, double* __restrict__ tri) {
+  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+  const uint32_t r = ty * kPcaTriRows + (threadIdx.x >> 4), c = tx * kPcaTriCols + 2 * (threadIdx.x & 15);
+  if (r >= n || c >= n || c + 1 < r) return;
+  const size_t src = (size_t)r * n + c, dst = pca_tri_offset(r, n) + c;
+  const bool both = c >= r && c + 1 < n;
+  if (both && !(((uintptr_t)(full + src) | (uintptr_t)(tri + dst)) & 15)) {
+    *reinterpret_cast<double2*>(tri + dst) = *reinterpret_cast<const double2*>(full + src);
+    return;
+  }
+  if (c >= r) tri[dst] = full[src];
+  if (c + 1 < n) tri[dst + 1] = full[src + 1];  // (c + 1 >= r holds for every thread that came this far)
+}
+
+// tri -> full[n][n]: entry (r, c) reads the packed (min, max) element, so (r, c) and (c, r) carry the same bits whatever order the
+// transport added in.  The writes are whole row segments; below the diagonal the reads of a tile walk down packed rows, 16
+// neighbouring rows of one column = one 128-byte line.
+__global__ __launch_bounds__(256) void pca_unpack_triangle_kernel(const double* __restrict__ tri, uint32_t n, uint32_t tiles_x, double* __restrict__ full) {
+  const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+  const uint32_t r = ty * kPcaTriRows + (threadIdx.x >> 4), c = tx * kPcaTriCols + 2 * (threadIdx.x & 15);
+  if (r >= n || c >= n) return;
+  const size_t dst = (size_t)r * n + c;
+  const bool two = c + 1 < n;
+  double2 v;
+  if (c >= r && two && !((uintptr_t)(tri + pca_tri_offset(r, n) + c) & 15)) {
+    v = *reinterpret_cast<const double2*>(tri + pca_tri_offset(r, n) + c);
+  } else {
+    v.x = c >= r ? tri[pca_tri_offset(r, n) + c] : tri[pca_tri_offset(c, n) + r];
+    v.y = !two ? 0.0 : (c + 1 >= r ? tri[pca_tri_offset(r, n) + c + 1] : tri[pca_tri_offset(c + 1, n) + r]);
+  }
+  if (two && !((uintptr_t)(full + dst) & 15)) { *reinterpret_cast<double2*>(full + dst) = v; return; }
+  full[dst] = v.x;
+  if (two) full[dst + 1] = v.y;
+}
+
 }  // namespace fmh

@@ -35,6 +35,7 @@
 
 #include "../../include/ferromic_hip.h"
 #include "host_cpus.hpp"
+#include "pca_host.hpp"
 
 namespace py = pybind11;
 using std::optional;

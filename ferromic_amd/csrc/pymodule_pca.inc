@@ -1,8 +1,9 @@
 // pymodule_pca.inc — ferromic.chromosome_pca / chromosome_pca_to_file / per_chromosome_pca and ChromosomePcaResult (included inside
 // pymodule_stats.inc's namespace).  Mirrors src/lib.rs:195-257, 1780-2156 (coercions, validation order, error texts) and
 // src/pca.rs:46-413 (the site filter, on the host from the device scan's integer counts), :846-1103 (the TSV writer and the combiner).
-// The standardised Gram and the eigenproblem run behind the C-ABI (fmh_pca_*); the GIL is released around them.
-// (needs <cerrno>, <filesystem>, <fstream>, <sstream>: pymodule.cpp includes them)
+// The pipeline after parsing is pca_host.hpp's (shared with run_vcf): the standardised Gram and the eigenproblem run behind the C-ABI
+// (fmh_pca_*); the GIL is released around them.
+// (needs <cerrno>, <filesystem>, <fstream>, <sstream> and pca_host.hpp: pymodule.cpp includes them)
 struct ChromosomePcaResult {  // lib.rs:195-257
   vector<string> haplotype_labels;
   py::array_t<double> coordinates;
@@ -12,9 +13,6 @@ struct ChromosomePcaResult {  // lib.rs:195-257
            ", variants=" + std::to_string(positions.shape(0)) + ")";
   }
 };
-
-// pca.rs:621: here the threshold only guards the division by a zero standard deviation, which a site that passed the MAF filter never has
-constexpr double kPcaNearZeroThreshold = FMH_PCA_NEAR_ZERO_THRESHOLD;
 
 // One call's cohort on the host, one byte per entry: 0, 1, 2 for ANY allele above 1 (the filter only asks "above 1"), kPcaMissing.
 constexpr uint8_t kPcaMissing = 0xFF;
@@ -29,24 +27,13 @@ struct PcaInput {
   void set(size_t idx, long long value) { data[idx] = value < 0 ? kPcaMissing : (uint8_t)(value > 1 ? 2 : value); }
 };
 
-struct PcaOutput {
-  size_t haplotypes = 0, components = 0;
-  vector<double> coordinates;  // [haplotypes][components]
-  vector<int64_t> positions;   // the kept sites
-};
+typedef fmpca::Output PcaOutput;
 
-struct PcaDeviceBlock {
-  void* p = nullptr;
-  int device = 0;
-  ~PcaDeviceBlock() { if (p) (void)fmh_device_free(device, p); }
-};
-
-// The pipeline after parsing.  false = the reference's VcfError::Parse with `*parse_error`; device failures raise RuntimeError.
+// The pipeline after parsing (pca_host.hpp, shared with run_vcf) on one matrix on the current device.  false = the reference's
+// VcfError::Parse with `*parse_error`; device failures raise RuntimeError.
 bool pca_compute(PcaInput& in, size_t n_components, PcaOutput* out, string* parse_error) {
-  const size_t S = in.variants, n = in.samples * 2;
-  out->haplotypes = n;
-  static const char* kNoMaf = "No variants with MAF >= 5% found for PCA";
-  if (S == 0) { *parse_error = in.variant_rule ? "No variants provided for PCA" : kNoMaf; return false; }
+  const size_t S = in.variants;
+  if (S == 0) { out->haplotypes = in.samples * 2; *parse_error = in.variant_rule ? "No variants provided for PCA" : "No variants with MAF >= 5% found for PCA"; return false; }
   const int device = current_device();
   // the missing bitset of fmh_matrix_create (one bit per entry) straight from the sentinel, which becomes 0
   bool any_missing = false;
@@ -62,52 +49,15 @@ bool pca_compute(PcaInput& in, size_t n_components, PcaOutput* out, string* pars
   {
     py::gil_scoped_release nogil;
     fmh_matrix* mh = nullptr;
-    auto run = [&]() -> int {
-      int r = fmh_matrix_create(in.data.data(), any_missing ? words.data() : nullptr, S, in.samples, 2, max_allele, device, &mh);
-      if (r != FMH_OK) return r;
-      PcaDeviceBlock d_alt, d_flags, d_gram;
-      d_alt.device = d_flags.device = d_gram.device = device;
-      if ((r = fmh_device_alloc(device, S * sizeof(uint32_t), &d_alt.p)) != FMH_OK) return r;
-      if ((r = fmh_device_alloc(device, S, &d_flags.p)) != FMH_OK) return r;
-      if ((r = fmh_pca_scan_sites(mh, 0, S, (uint32_t*)d_alt.p, (uint8_t*)d_flags.p, nullptr)) != FMH_OK) return r;
-      vector<uint32_t> alt(S);
-      vector<uint8_t> flags(S);
-      if ((r = fmh_copy_to_host(device, alt.data(), d_alt.p, S * sizeof(uint32_t), nullptr)) != FMH_OK) return r;
-      if ((r = fmh_copy_to_host(device, flags.data(), d_flags.p, S, nullptr)) != FMH_OK) return r;
-      // the filter, pca.rs:257-290 / :68-125: the reference's f64 expression on the integer count
-      size_t complete = 0;
-      vector<uint64_t> kept;
-      vector<double> set_value, clear_value;
-      for (size_t r0 = 0; r0 < S; ++r0) {
-        if (flags[r0] & FMH_PCA_SITE_UNCALLED) continue;
-        if (flags[r0] & FMH_PCA_SITE_HIGH_ALLELE) { if (in.variant_rule) ++complete; continue; }
-        ++complete;
-        const double freq = (double)alt[r0] / (double)n;
-        const double maf = std::fmin(freq, 1.0 - freq);
-        if (!(maf >= 0.05)) continue;
-        kept.push_back(r0);
-        out->positions.push_back(in.positions[r0]);
-        // pca.rs:579-662: mean, variance over n - 1, scale 1 when the deviation is numerically zero
-        const double mean = (double)alt[r0] / (double)n;
-        const double d1 = 1.0 - mean, d0 = 0.0 - mean;
-        const double var = ((double)alt[r0] * (d1 * d1) + (double)(n - alt[r0]) * (d0 * d0)) / (double)(n - 1);
-        const double sd = std::sqrt(std::isfinite(var) ? std::max(var, 0.0) : 0.0);
-        const double inv = 1.0 / ((!std::isfinite(sd) || sd <= kPcaNearZeroThreshold) ? 1.0 : sd);
-        set_value.push_back(d1 * inv);
-        clear_value.push_back(d0 * inv);
-      }
-      if (kept.empty()) { *parse_error = kNoMaf; ok = false; return FMH_OK; }
-      const size_t wanted = std::min(n_components, std::min(complete, n));
-      out->components = std::min(wanted, std::min(kept.size(), n));  // pca.rs:694 / :759: min(n_components, min(m, n))
-      out->coordinates.assign(n * out->components, 0.0);
-      if (out->components == 0) return FMH_OK;
-      if ((r = fmh_device_alloc(device, n * n * sizeof(double), &d_gram.p)) != FMH_OK) return r;
-      if ((r = fmh_pca_gram(mh, kept.data(), kept.size(), set_value.data(), clear_value.data(), (double*)d_gram.p, nullptr)) != FMH_OK) return r;
-      vector<double> eigenvalues(out->components);
-      return fmh_pca_eigen_scores(device, (double*)d_gram.p, n, out->components, eigenvalues.data(), out->coordinates.data());
-    };
-    rc = run();
-    if (rc != FMH_OK) device_error = fmh_last_error();
+    try {
+      fmpca::check(fmh_matrix_create(in.data.data(), any_missing ? words.data() : nullptr, S, in.samples, 2, max_allele, device, &mh));
+      fmpca::SlabInput slab;
+      slab.m = mh; slab.device = device; slab.rows = S;
+      ok = fmpca::compute({slab}, in.samples, in.positions.data(), n_components, in.variant_rule, [](auto&& fn) { fn((size_t)0); }, out, parse_error);
+    } catch (const fmpca::DeviceError& e) {
+      rc = e.status;
+      device_error = e.what();
+    }
     if (mh) (void)fmh_matrix_destroy(mh);
   }
   if (rc != FMH_OK) raise(PyExc_RuntimeError, "libferromic_hip status " + std::to_string(rc) + ": " + device_error);
@@ -270,36 +220,12 @@ void pca_validate(const vector<string>& sample_names, size_t n_components) {  //
   if (n_components == 0) value_error("n_components must be greater than or equal to 1");
 }
 
-vector<string> pca_labels(const vector<string>& sample_names) {  // pca.rs:459-463
-  vector<string> labels;
-  labels.reserve(sample_names.size() * 2);
-  for (const string& name : sample_names) { labels.push_back(name + "_L"); labels.push_back(name + "_R"); }
-  return labels;
-}
-
-// write_chromosome_pca_to_file, pca.rs:846-893: "Haplotype\tPC1...", one row per haplotype, "\t{:.6}" per value
+// labels, TSV text and the file writer: pca_host.hpp
+vector<string> pca_labels(const vector<string>& sample_names) { return fmpca::labels(sample_names); }
 string pca_tsv_text(const vector<string>& labels, const double* coordinates, size_t rows, size_t components) {
-  string text = "Haplotype";
-  for (size_t k = 0; k < components; ++k) text += "\tPC" + std::to_string(k + 1);
-  text += "\n";
-  char buf[400];
-  for (size_t i = 0; i < std::min(labels.size(), rows); ++i) {
-    text += labels[i];
-    for (size_t k = 0; k < components; ++k) {
-      snprintf(buf, sizeof buf, "\t%.6f", coordinates[i * components + k]);
-      text += buf;
-    }
-    text += "\n";
-  }
-  return text;
+  return fmpca::tsv_text(labels, coordinates, rows, components);
 }
-bool pca_write_file(const std::filesystem::path& path, const string& text, string* error) {
-  std::ofstream f(path, std::ios::binary | std::ios::trunc);
-  if (f) f.write(text.data(), (std::streamsize)text.size());
-  if (f) f.close();
-  if (!f) { *error = string(strerror(errno)) + ": " + path.string(); return false; }
-  return true;
-}
+bool pca_write_file(const std::filesystem::path& path, const string& text, string* error) { return fmpca::write_file(path, text, error); }
 
 py::object chromosome_pca(const py::object& variants, const vector<string>& sample_names, size_t n_components) {
   pca_validate(sample_names, n_components);

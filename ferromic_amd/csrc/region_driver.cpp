@@ -2,6 +2,7 @@
 // process.rs:821-1188 and stats.rs on top of the sweeps, CSV-defined populations, the per-config-entry driver (process.rs:2468-3653),
 // flags and main().  Every statistic over genotype data is computed on the GPU.
 #include "run_vcf.hpp"
+#include "pca_host.hpp"
 
 namespace {
 
@@ -201,13 +202,14 @@ bool build_matrix_planes(const vector<const Variant*>& vs, size_t n_samples, siz
   return true;
 }
 
-RegionMatrix build_matrix(const vector<const Variant*>& vs, size_t n_samples, int device, bool shard = false) {
+// force_ploidy (the PCA's matrix is always diploid): column s * P + k is allele k of sample s, called iff k < glen(s); alleles beyond P are left out
+RegionMatrix build_matrix(const vector<const Variant*>& vs, size_t n_samples, int device, bool shard = false, size_t force_ploidy = 0) {
   RegionMatrix out;
   if (vs.empty()) return out;
   size_t max_ploidy = 0;
   for (auto* v : vs) max_ploidy = std::max(max_ploidy, v->max_len);
   out.has_dense = max_ploidy > 0;
-  const size_t P = std::max<size_t>(max_ploidy, 1);
+  const size_t P = force_ploidy ? force_ploidy : std::max<size_t>(max_ploidy, 1);
   out.ploidy = P;
   out.variants = vs.size();
   if (build_matrix_planes(vs, n_samples, P, device, shard, out)) return out;  // the common shape: straight to bit planes
@@ -831,6 +833,8 @@ struct Args {
   vector<string> exclude;
   unsigned min_gq = 30;
   bool enable_fst = false, enable_pca = false;
+  size_t pca_components = 10;  // --pca_components
+  string pca_output;           // --pca_output: accepted and unused, as in the reference
   int device = 0;
   int workers_per_device = 0;  // region workers per GPU (0 = by the CPU share): host-side packing, downloads and track writers of one region overlap the sweeps of another
   bool print_formats = false;  // diagnostic: header lines + sample FALSTA records (needs no GPU, no inputs)
@@ -985,6 +989,82 @@ std::optional<RegionOutput> process_single_config_entry(const ConfigEntry& entry
   return out;
 }
 
+// ---- --pca: the haplotype PCA of one chromosome (process.rs:2033-2081, 2145-2164, 2288-2343; pca.rs:46-203, 415-479, 846-893) ----------
+// Input: every variant of the chromosome's ingest whose flag is FLAG_PASS, as a DIPLOID matrix: column 2 s + k is allele k of sample s,
+// called iff k < glen(s); a site is complete iff every entry is called (pca.rs:81-91).  A missing or unparsable cell or a low GQ already
+// cleared PASS at ingest, so among these the only incomplete sites are those with a haploid cell.
+vector<const Variant*> pca_pass_variants(const VcfData& vcf) {
+  vector<const Variant*> pass;
+  for (size_t i = 0; i < vcf.variants.size(); ++i) if (vcf.flags[i] == FLAG_PASS) pass.push_back(&vcf.variants[i]);
+  return pass;
+}
+
+// --ingest_only --pca: FNV-1a (the [INGEST] digest's constants) over, per PASS variant in order, the 8 little-endian bytes of the position
+// and the 2 S entry bytes of that matrix (the allele of a called entry, 0xFF otherwise): pins "which variants, which samples, which two
+// alleles" against the oracle's parse without a device
+void print_pca_input_digest(const string& chr, const VcfData& vcf) {
+  const vector<const Variant*> pass = pca_pass_variants(vcf);
+  const size_t N = vcf.sample_names.size();
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](uint8_t b) { h ^= b; h *= 1099511628211ull; };
+  for (const Variant* v : pass) {
+    for (int k = 0; k < 8; ++k) mix((uint8_t)((uint64_t)v->position >> (8 * k)));
+    for (size_t s = 0; s < N; ++s) {
+      const size_t len = v->glen(s);
+      for (size_t k = 0; k < 2; ++k) mix(k < len ? v->data[s * v->stride + k] : (uint8_t)0xFF);
+    }
+  }
+  printf("[PCA_INPUT] chr %s: %zu variants x %zu samples digest %016llx\n", chr.c_str(), pass.size(), N, (unsigned long long)h);
+}
+
+// Never fails the run: every outcome but a written file is a WARN line.
+void chromosome_pca(const string& chr, const VcfData& vcf, const Args& args) {
+  StageTimer tm("pca");
+  logmsg("INFO", "Performing single PCA after all regions for chromosome " + chr);
+  const vector<const Variant*> pass = pca_pass_variants(vcf);
+  if (pass.empty()) { logmsg("WARN", "No filtered variants remain for chromosome " + chr + ". Skipping PCA."); return; }
+  const size_t N = vcf.sample_names.size();
+  try {
+    std::optional<StageTimer> stage;
+    stage.emplace("  pca:matrix_build_and_upload");
+    const bool shard = want_shard(pass.size(), N);
+    std::unique_lock<std::mutex> shard_lock(g_shard.region_mutex, std::defer_lock);
+    if (shard) { shard_lock.lock(); restore_shard_group(); }
+    // the Variant route (variant_rule): a complete site with an allele above 1 counts as complete and is then skipped
+    const RegionMatrix rm = build_matrix(pass, N, args.device, shard && want_shard(pass.size(), N), /*force_ploidy=*/2);
+    vector<int64_t> positions(pass.size());
+    for (size_t i = 0; i < pass.size(); ++i) positions[i] = pass[i]->position;
+    vector<fmpca::SlabInput> slabs;
+    for (const Slab& sl : rm.slabs) {
+      fmpca::SlabInput in;
+      in.m = sl.dm->h; in.comm = sl.comm; in.device = sl.device; in.row0 = sl.row0; in.rows = sl.dm->variants;
+      slabs.push_back(in);
+    }
+    stage.emplace("  pca:scan_gram_eigen");
+    fmpca::Output out;
+    string parse_error;
+    // a slab that fails aborts the group (on_slabs), so its peers leave the Gram's collective with an error instead of waiting
+    const bool ok = fmpca::compute(slabs, N, positions.data(), args.pca_components, /*variant_rule=*/true,
+                                   [&](auto&& fn) { on_slabs(rm, [&](const Slab&, size_t k) { fn(k); }); }, &out, &parse_error);
+    stage.reset();
+    if (getenv("FERROMIC_TIMING") && string(getenv("FERROMIC_TIMING")) == "1")
+      fprintf(stderr, "[TIMING]   pca:scan %.3f\n[TIMING]   pca:gram %.3f\n[TIMING]   pca:eigen %.3f\n", out.scan_seconds, out.gram_seconds, out.eigen_seconds);
+    logmsg("INFO", "Found " + std::to_string(out.complete) + " variants with complete data out of " + std::to_string(out.total) + " total variants");
+    if (ok) logmsg("INFO", "Keeping " + std::to_string(out.kept) + "/" + std::to_string(out.complete) + " variants with MAF >= 5% for PCA");
+    if (!ok) { logmsg("WARN", "Chromosome " + chr + " PCA error: Parse error: " + parse_error); return; }
+    StageTimer tw("  pca:write");
+    const string dir = "pca_per_chr_outputs";  // process.rs:2317: relative to the working directory, not next to --output_file
+    mkdirs(dir);
+    string error;
+    const string text = fmpca::tsv_text(fmpca::labels(vcf.sample_names), out.coordinates.data(), out.haplotypes, out.components);
+    if (!fmpca::write_file(dir + "/pca_chr_" + chr + ".tsv", text, &error)) { logmsg("WARN", "Chromosome " + chr + " PCA error: " + error); return; }
+    logmsg("INFO", "PCA for chromosome " + chr + ": " + std::to_string(out.haplotypes) + " haplotypes x " + std::to_string(out.components) + " components from " +
+                       std::to_string(out.kept) + " variants");
+  } catch (const std::exception& e) {
+    logmsg("WARN", "Chromosome " + chr + " PCA error: " + e.what());
+  }
+}
+
 // resolve_sample_exclusions, run_vcf.rs:24-187
 std::set<string> resolve_exclusions(const Args& args, const string& chr, const vector<ConfigEntry>* entries) {
   std::set<string> requested(args.exclude.begin(), args.exclude.end());
@@ -1097,7 +1177,6 @@ int run(const Args& args) {
   } else {
     throw Error("Parse(\"Either --config_file or --chr must be specified\")");
   }
-  if (args.enable_pca) logmsg("WARN", "--pca is outside the accelerated path and is ignored (DESIGN.md section 8)");
   std::optional<PopulationCsv> csv_for_hudson;  // process.rs:1394-1426: parsed once, exclusions removed
   if (args.enable_fst && !args.fst_populations.empty()) {
     try {
@@ -1163,6 +1242,7 @@ int run(const Args& args) {
           }
         printf("[INGEST] chr %s: %zu variants x %zu samples digest %016llx\n", chr.c_str(), vcf.variants.size(), vcf.sample_names.size(),
                (unsigned long long)h);
+        if (args.enable_pca) print_pca_input_digest(chr, vcf);
         continue;
       }
       warmup.join();
@@ -1230,6 +1310,8 @@ int run(const Args& args) {
         for (int d : worker_devices) pool.emplace_back(worker, d);
         for (auto& t : pool) t.join();
       }
+      // process.rs:2288-2343: one PCA per chromosome, after all of its regions (also when regions were dropped)
+      if (args.enable_pca) { tm.reset(); chromosome_pca(chr, vcf, args); }
     } catch (const Error& e) {
       fprintf(stderr, "Error processing chromosome %s: %s\n", chr.c_str(), e.what());
       continue;
@@ -1280,7 +1362,13 @@ Args parse_args(int argc, char** argv) {  // clap Args, process.rs:67-144
     else if (k == "--reference") { a.reference = value(); have_ref = true; }
     else if (k == "--gtf") { a.gtf = value(); have_gtf = true; }
     else if (k == "--pca") a.enable_pca = true;
-    else if (k == "--pca_components" || k == "--pca_output") (void)value();
+    else if (k == "--pca_components") {  // usize
+      const string t = value();
+      int64_t c = 0;
+      if (t.empty() || t[0] == '-' || !parse_i64(t, &c)) throw Error("invalid value '" + t + "' for '--pca_components <PCA_COMPONENTS>'");
+      a.pca_components = (size_t)c;
+    }
+    else if (k == "--pca_output") a.pca_output = value();
     else if (k == "--fst") a.enable_fst = true;
     else if (k == "--fst_populations") a.fst_populations = value();
     else if (k == "--ingest_only") a.ingest_only = true;
@@ -1302,7 +1390,8 @@ Args parse_args(int argc, char** argv) {  // clap Args, process.rs:67-144
     }
     else if (k == "--help" || k == "-h") {
       printf("run_vcf --vcf_folder DIR --reference FA --gtf GTF [--config_file TSV | --chr C [--region S-E]] [--output_file CSV]\n"
-             "        [--min_gq 30] [--mask_file F] [--allow_file F] [--exclude a,b] [--fst] [--fst_populations CSV] [--device N | --devices N|a,b,c] [--workers_per_device N]\n");
+             "        [--min_gq 30] [--mask_file F] [--allow_file F] [--exclude a,b] [--fst] [--fst_populations CSV] [--device N | --devices N|a,b,c] [--workers_per_device N]\n"
+             "        [--pca [--pca_components 10] [--pca_output F]]   per chromosome: pca_per_chr_outputs/pca_chr_<chr>.tsv under the working directory\n");
       exit(0);
     } else throw Error("unexpected argument '" + k + "'");
   }

@@ -401,6 +401,26 @@ def pca_gram(m: DeviceMatrix, kept_rows, set_value, clear_value) -> np.ndarray:
     return pca_gram_device(m, kept_rows, set_value, clear_value).to_numpy(np.float64, n * n).reshape(n, n)
 
 
+def pca_gram_sharded_device(comm, m: DeviceMatrix, kept_rows, set_value, clear_value) -> DeviceBuffer:
+    """fmh_pca_gram_sharded: this rank's slab matrix `m` and the kept rows of that slab (possibly none) in, the Gram summed over the
+    ranks of `comm` (a sharding.Comm) out, in a fresh device buffer.  Collective: every rank calls it."""
+    kept = np.ascontiguousarray(kept_rows, dtype=np.uint64)
+    hi = np.ascontiguousarray(set_value, dtype=np.float64)
+    lo = np.ascontiguousarray(clear_value, dtype=np.float64)
+    if not (kept.size == hi.size == lo.size):
+        raise ValueError("kept_rows, set_value and clear_value must have one entry per kept site")
+    n = m.samples * 2
+    d_gram = DeviceBuffer(m.device, max(8 * n * n, 8))
+    _abi.check(_abi.load().fmh_pca_gram_sharded(comm._h, m._h, _ptr(kept), kept.size, _ptr(hi), _ptr(lo), d_gram.ptr, None))
+    return d_gram
+
+
+def pca_gram_sharded(comm, m: DeviceMatrix, kept_rows, set_value, clear_value) -> np.ndarray:
+    """The same as an (n, n) float64 array."""
+    n = m.samples * 2
+    return pca_gram_sharded_device(comm, m, kept_rows, set_value, clear_value).to_numpy(np.float64, n * n).reshape(n, n)
+
+
 def pca_eigen_scores(device: int, gram, n_components: int):
     """fmh_pca_eigen_scores of a symmetric (n, n) array or of a DeviceBuffer holding one (overwritten): (eigenvalues descending
     [n_components], scores [n][n_components])."""

@@ -477,6 +477,32 @@ int fmh_pair_region_sweep_sharded(fmh_comm* c, const fmh_matrix* m, const fmh_gr
                                   const fmh_hudson_sites* sites_or_null, fmh_hudson_totals* h_global_totals, void* stream);
 
 /*
+ * The PCA Gram (fmh_pca_gram) of a cohort whose SITES are spread over the ranks - the Gram is a plain sum over sites, and the only
+ * O(n^2 m) step of the PCA.  Every rank passes ITS slab matrix (same samples, ploidy 2) and the kept rows of that slab (row indices
+ * local to the slab) with their set / clear values; n_kept may be 0 on a rank (it contributes zeros).  On return every rank's
+ * d_gram[n][n] (n = samples * 2, on the communicator's device) holds the sum over the ranks of Z_r Z_r^T / (n - 1).
+ *
+ * How: the local Gram is fmh_pca_gram's own path; only the upper triangle travels (n (n + 1) / 2 doubles, row i at offset
+ * i n - i (i - 1) / 2), and the full matrix is rebuilt from the summed triangle with (i, j) and (j, i) written from the same value - so the
+ * result is exactly symmetric on every transport.  Local communicator: nothing is exchanged.  In-process transport: the triangles are
+ * added on the host in rank order, so every rank ends with the same bits and two calls give the same bits.  RCCL: one ncclAllReduce
+ * (f64, sum) on the communicator's stream, ordered behind the pack and before the unpack by events; the order of RCCL's additions is
+ * RCCL's, so run-to-run bits are NOT promised there with more than one rank.  A communicator of one rank gives fmh_pca_gram's bits
+ * (zeros for n_kept == 0) on every transport.
+ *
+ * Collective: every rank calls it.  Every argument and the memory budget are checked BEFORE anything is enqueued, so a rank whose call
+ * returned FMH_ERR_INVALID / FMH_ERR_UNSUPPORTED from those checks has not entered the collective and may call fmh_comm_abort to
+ * release its peers.  On the in-process transport ranks whose matrices differ in sample count get FMH_ERR_INVALID from the collective
+ * (it compares the lengths), not a wrong sum.  No other collective may be in flight on the communicator.
+ *
+ * Device memory: what fmh_pca_gram takes plus the packed triangle, 4 n (n + 1) bytes from the library's pool; the sum must stay
+ * within FMH_PCA_BUDGET_BYTES, else FMH_ERR_UNSUPPORTED.  The in-process transport also holds one triangle per rank plus the sum in
+ * host memory.  This reduce is not bound by FMH_COMM_MAX_VALUES (that is fmh_allreduce_totals' limit).  Synchronises `stream`.
+ */
+int fmh_pca_gram_sharded(fmh_comm* c, const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, const double* h_set_value,
+                         const double* h_clear_value, double* d_gram /* n x n, n = samples * 2 */, void* stream);
+
+/*
  * Packing of the totals structs into the f64 + u64 vectors a sum-reduce moves (fmh_allreduce_totals, or MPI / any other
  * transport).  Everything packed is a plain sum over slabs, except haplotype_capacity / sites_attempted-style constants,
  * which unpack restores from the rank count carried in the last u64 slot.
