@@ -79,9 +79,13 @@ extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, u
     const size_t s_pad = round_up(rows, ksites);  // sites
     const size_t k_bytes = s_pad / spb;           // K bytes per sample in this slab
     if (from_packed) {
-      // bit rows are tiny in LDS: 256 samples per workgroup (64-byte row pieces for diploid samples)
-      const uint32_t sbp = 256;
-      const size_t bitb = ((size_t)sbp * m->ploidy + 7) / 8 + 1;
+      // bit rows are tiny in LDS: 256 samples per workgroup (64-byte row pieces for diploid samples), fewer when the three staged
+      // planes of a K block would pass the CU's 160 KiB (int8 route from ploidy 14: 3 x 128 x 449 B).  Halving keeps sbp a power of
+      // two, so n_pad stays a multiple of it; the kernel stages dword pieces where sbp x ploidy is a multiple of 32 bits and bytes elsewhere
+      uint32_t sbp = 256;
+      auto packed_bitb = [&](uint32_t s) { return ((size_t)s * m->ploidy + 7) / 8 + 1; };
+      while (3 * ksites * packed_bitb(sbp) > kPdPlanesLdsMax && sbp > 4) sbp /= 2;
+      const size_t bitb = packed_bitb(sbp);
       const size_t smem_p = 3 * ksites * bitb;
       const dim3 grid_p((unsigned)(s_pad / ksites), (unsigned)(n_pad / sbp));
       const uint8_t* q0 = m->p0 + row0 * m->plane_pitch;
@@ -139,10 +143,11 @@ extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, u
       if (oe == hipSuccess) oe = fp4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, pd_gram256_kernel<4, 4, true>, 1024, 2 * kPdBigStageBytes)
                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, pd_gram256_kernel<4, 4, false>, 1024, 2 * kPdBigStageBytes);
       if (oe != hipSuccess || occ < 1) occ = 1;
-      const int env_occ = (int)options().pd_occ.load();
-      if (env_occ > 0 && occ > env_occ) occ = env_occ;
       gram_occ[m->device][fp4] = occ;
     }
+    // FMH_PD_OCC is read on every call (the hardware's answer above is what is kept), so fmh_set_option takes effect in a running process
+    const int env_occ = (int)options().pd_occ.load();
+    const int occ_now = env_occ > 0 && gram_occ[m->device][fp4] > env_occ ? env_occ : gram_occ[m->device][fp4];
     static thread_local bool phased_ready[64][2];
     if (phased && !phased_ready[m->device][fp4]) {
       e = hipFuncSetAttribute(fp4 ? (const void*)pd_gram256p_kernel<true> : (const void*)pd_gram256p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPdPhaseLdsBytes);
@@ -150,7 +155,7 @@ extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, u
       phased_ready[m->device][fp4] = true;
     }
     // persistent: every workgroup resident (the phased kernel's two K tiles of LDS leave one workgroup per CU)
-    const unsigned grid = phased ? (unsigned)std::max(8, w->cus / 8 * 8) : (unsigned)std::max(8, w->cus * gram_occ[m->device][fp4] / 8 * 8);
+    const unsigned grid = phased ? (unsigned)std::max(8, w->cus / 8 * 8) : (unsigned)std::max(8, w->cus * occ_now / 8 * 8);
     const size_t slots = grid / 8;
     size_t j = env_chunk ? std::max<size_t>(1, (k_bytes + 8 * env_chunk - 1) / (8 * env_chunk)) : std::max<size_t>(1, (slots * 8 + tiles - 1) / tiles);
     // an item's accumulators must stay exact: int32 for the int8 route, integers up to 2^24 in f32 for FP4 (counts <= ploidy)

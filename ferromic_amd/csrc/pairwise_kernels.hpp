@@ -18,6 +18,7 @@ namespace fmh {
 // which the same product delivers as G(i, ones) against an all-ones row appended after the last sample.
 // ------------------------------------------------------------------------------------------------
 constexpr int kPdBlock = 128;   // samples per planes-kernel workgroup
+constexpr size_t kPdPlanesLdsMax = 160 * 1024;  // LDS of a gfx950 CU: the most a planes workgroup may ask for
 constexpr int kPdStageK = 128;  // K BYTES per sample per Gram stage: 128 sites as int8, 256 sites as FP4 (two per byte)
 
 // FP4 route (ploidy <= 4): the planes hold e2m1 codes of the counts 0..4 (0, 1, 2, 3, 4 are exact in e2m1) and the

@@ -62,6 +62,8 @@ def load():
         lib.fo_region_sweep_threaded.argtypes = [vp, vp, sz, sz, i, vp, sz, vp, sz, i, i] + [vp] * 11 + [
             C.POINTER(PopTotals), C.POINTER(RegionTotals), i]
         lib.fo_region_sweep_threaded.restype = i
+        lib.fo_pairwise_differences_threaded.argtypes = [vp, vp, sz, sz, sz, sz, i, vp, vp, i]
+        lib.fo_pairwise_differences_threaded.restype = i
         _lib = lib
     return _lib
 
@@ -211,3 +213,23 @@ def region_sweep(data: np.ndarray, missing_words: Optional[np.ndarray], variants
     return RegionOut(*counts, *div, *tracks,
                      pop=[{k: getattr(pop[i], k) for k, _ in PopTotals._fields_} for i in range(2)],
                      totals={k: getattr(tot, k) for k, _ in RegionTotals._fields_})
+
+
+def pairwise_differences(data: np.ndarray, missing_words: Optional[np.ndarray], variants: int, stride: int, ploidy: int, n_samples: int,
+                         max_allele: int, nthreads: int = 1):
+    """fo_pairwise_differences_threaded: (diff, both) as [n_samples, n_samples] uint64 arrays, upper triangle filled, of the first
+    n_samples samples of a site-major u8 matrix [variants][stride] (stride >= n_samples * ploidy columns, missing bit = site * stride +
+    column): calculate_pairwise_differences (stats.rs:4106-4231) with every genotype the prefix of its called alleles, computed
+    bit-parallel on haplotypes (XOR + popcount), not from allele counts."""
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    assert data.size >= variants * stride and n_samples * ploidy <= stride
+    if missing_words is not None:
+        missing_words = np.ascontiguousarray(missing_words, dtype=np.uint64)
+        assert missing_words.size >= (variants * stride + 63) // 64
+    diff = np.empty((n_samples, n_samples), dtype=np.uint64)
+    both = np.empty((n_samples, n_samples), dtype=np.uint64)
+    rc = load().fo_pairwise_differences_threaded(_p(data), _p(missing_words), variants, stride, ploidy, n_samples, int(max_allele),
+                                                 _p(diff), _p(both), int(nthreads))
+    if rc != 0:
+        raise MemoryError("fo_pairwise_differences_threaded: the haplotype-major transpose does not fit in memory")
+    return diff, both

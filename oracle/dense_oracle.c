@@ -955,3 +955,137 @@ int fo_region_sweep_threaded(const uint8_t* data, const uint64_t* missing, size_
   free(jobs);
   return 0;
 }
+
+/* ---- all-pairs differences (calculate_pairwise_differences, stats.rs:4106-4231) on a dense matrix, bit-parallel on haplotypes ------
+ * For samples i < j < n_samples over every site:
+ *   diff(i, j) = number of (a, b), a an allele of genotype i and b one of genotype j, with a != b, at sites where both are Some
+ *   both(i, j) = number of sites where both genotypes are Some
+ * where a sample's genotype at a site is the prefix of its called alleles (CompressedGenotypes::get, process.rs:479-496): slot k is
+ * EFFECTIVE iff slots 0..k are all called, and the genotype is Some iff slot 0 is effective.
+ * The matrix is transposed once to haplotype-major words of 64 sites - one word row per bit of the allele value and one for the
+ * effective bit e - and then
+ *   diff(i, j) = sum_{a, b < ploidy} popcount( OR_bits(h_ia ^ h_jb) & e_ia & e_jb ),   both(i, j) = popcount(e_i0 & e_j0).
+ * No allele counts, no products: deliberately not the algebra of the device kernels it checks.
+ * Layout: T[block][haplotype][plane][PD_BW words], planes = allele bits then e; a block (PD_BW * 64 sites of every haplotype) is what the
+ * pair loop keeps in cache.  Threads own disjoint sets of (sample tile, sample tile) pairs and walk the blocks in the same order. */
+#define PD_BW 64
+#define PD_TILE 32
+
+typedef struct {
+  const uint8_t* data;
+  const uint64_t* missing;
+  size_t variants, stride, ploidy, n_samples, blocks;
+  int planes; /* allele bits + 1 */
+  uint64_t* T;
+  uint64_t* tmp; /* this thread's P * H words of the transpose */
+  uint64_t *diff, *both;
+  int t, nthreads;
+} pd_job;
+
+static void* pd_transpose_worker(void* pv) {
+  pd_job* j = (pd_job*)pv;
+  const size_t H = j->n_samples * j->ploidy, P = (size_t)j->planes, nbits = P - 1;
+  const size_t words = (j->variants + 63) / 64;
+  const size_t w0 = words * (size_t)j->t / (size_t)j->nthreads, w1 = words * ((size_t)j->t + 1) / (size_t)j->nthreads;
+  uint64_t* tmp = j->tmp;
+  for (size_t w = w0; w < w1; ++w) {
+    memset(tmp, 0, sizeof(uint64_t) * P * H);
+    for (size_t s = 0; s < 64 && w * 64 + s < j->variants; ++s) {
+      const size_t base = (w * 64 + s) * j->stride;
+      for (size_t smp = 0; smp < j->n_samples; ++smp) {
+        uint64_t eff = 1;
+        for (size_t k = 0; k < j->ploidy; ++k) {
+          const size_t h = smp * j->ploidy + k;
+          if (j->missing) eff &= (uint64_t)!dense_missing(j->missing, base + h);
+          const uint64_t v = j->data[base + h] & (0 - eff);
+          for (size_t b = 0; b < nbits; ++b) tmp[h * P + b] |= ((v >> b) & 1u) << s;
+          tmp[h * P + nbits] |= eff << s;
+        }
+      }
+    }
+    uint64_t* blk = j->T + (w / PD_BW) * H * P * PD_BW + (w % PD_BW);
+    for (size_t hp = 0; hp < H * P; ++hp) blk[hp * PD_BW] = tmp[hp];
+  }
+  return NULL;
+}
+
+static void* pd_pairs_worker(void* pv) {
+  pd_job* j = (pd_job*)pv;
+  const size_t n = j->n_samples, pl = j->ploidy, P = (size_t)j->planes, nbits = P - 1, H = n * pl;
+  const size_t tiles = (n + PD_TILE - 1) / PD_TILE;
+  for (size_t blk = 0; blk < j->blocks; ++blk) {
+    const uint64_t* B = j->T + blk * H * P * PD_BW;
+    size_t tp = 0;
+    for (size_t ti = 0; ti < tiles; ++ti)
+      for (size_t tj = ti; tj < tiles; ++tj, ++tp) {
+        if (tp % (size_t)j->nthreads != (size_t)j->t) continue;
+        const size_t i1 = (ti + 1) * PD_TILE < n ? (ti + 1) * PD_TILE : n, j1 = (tj + 1) * PD_TILE < n ? (tj + 1) * PD_TILE : n;
+        for (size_t i = ti * PD_TILE; i < i1; ++i)
+          for (size_t jj = (tj == ti ? i + 1 : tj * PD_TILE); jj < j1; ++jj) {
+            uint64_t d = 0, bo = 0;
+            const uint64_t *ei0 = B + ((i * pl) * P + nbits) * PD_BW, *ej0 = B + ((jj * pl) * P + nbits) * PD_BW;
+            for (size_t w = 0; w < PD_BW; ++w) bo += (uint64_t)__builtin_popcountll(ei0[w] & ej0[w]);
+            for (size_t a = 0; a < pl; ++a) {
+              const uint64_t* x = B + ((i * pl + a) * P) * PD_BW;
+              for (size_t b = 0; b < pl; ++b) {
+                const uint64_t* y = B + ((jj * pl + b) * P) * PD_BW;
+                if (nbits == 1) {
+                  for (size_t w = 0; w < PD_BW; ++w)
+                    d += (uint64_t)__builtin_popcountll((x[w] ^ y[w]) & x[PD_BW + w] & y[PD_BW + w]);
+                } else {
+                  for (size_t w = 0; w < PD_BW; ++w) {
+                    uint64_t ne = 0;
+                    for (size_t q = 0; q < nbits; ++q) ne |= x[q * PD_BW + w] ^ y[q * PD_BW + w];
+                    d += (uint64_t)__builtin_popcountll(ne & x[nbits * PD_BW + w] & y[nbits * PD_BW + w]);
+                  }
+                }
+              }
+            }
+            j->diff[i * n + jj] += d;
+            j->both[i * n + jj] += bo;
+          }
+      }
+  }
+  return NULL;
+}
+
+/* data: [variants][stride] u8 (site-major, sample s = columns s * ploidy .. + ploidy - 1), missing: bit (site * stride + column) or NULL.
+ * diff, both: [n_samples][n_samples] u64, zeroed here, upper triangle filled.  Returns 0, or -1 when out of memory. */
+int fo_pairwise_differences_threaded(const uint8_t* data, const uint64_t* missing, size_t variants, size_t stride, size_t ploidy,
+                                     size_t n_samples, int max_allele, uint64_t* diff, uint64_t* both, int nthreads) {
+  memset(diff, 0, sizeof(uint64_t) * n_samples * n_samples);
+  memset(both, 0, sizeof(uint64_t) * n_samples * n_samples);
+  if (n_samples < 2 || variants == 0 || ploidy == 0) return 0;
+  if (nthreads < 1) nthreads = 1;
+  int nbits = 1;
+  while (nbits < 8 && (max_allele >> nbits) != 0) ++nbits;
+  const size_t words = (variants + 63) / 64, blocks = (words + PD_BW - 1) / PD_BW;
+  const size_t H = n_samples * ploidy, P = (size_t)nbits + 1;
+  uint64_t* T = (uint64_t*)calloc(blocks * H * P * PD_BW, sizeof(uint64_t)); /* words past the last site stay 0: e = 0 there */
+  uint64_t* tmp = (uint64_t*)malloc(sizeof(uint64_t) * P * H * (size_t)nthreads);
+  pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)nthreads);
+  pd_job* jobs = (pd_job*)malloc(sizeof(pd_job) * (size_t)nthreads);
+  int* started = (int*)malloc(sizeof(int) * (size_t)nthreads);
+  if (!T || !tmp || !th || !jobs || !started) {
+    free(T); free(tmp); free(th); free(jobs); free(started);
+    return -1;
+  }
+  for (int t = 0; t < nthreads; ++t) {
+    pd_job j = {data, missing, variants, stride, ploidy, n_samples, blocks, (int)P, T, tmp + (size_t)t * P * H, diff, both, t, nthreads};
+    jobs[t] = j;
+  }
+  void* (*phases[2])(void*) = {pd_transpose_worker, pd_pairs_worker};
+  for (int ph = 0; ph < 2; ++ph) { /* a thread that cannot be started: its share runs here, the result is the same */
+    for (int t = 0; t < nthreads; ++t) started[t] = pthread_create(&th[t], NULL, phases[ph], &jobs[t]) == 0;
+    for (int t = 0; t < nthreads; ++t) {
+      if (started[t]) pthread_join(th[t], NULL);
+      else phases[ph](&jobs[t]);
+    }
+  }
+  free(started);
+  free(th);
+  free(jobs);
+  free(tmp);
+  free(T);
+  return 0;
+}

@@ -328,3 +328,144 @@ def test_c_region_sweep_matches_python_oracle(sites, samples, max_allele, p_miss
                               getattr(base, k).view(np.uint64 if k.startswith("site") else np.uint32)), k
     with pytest.raises(ValueError):
         D.region_sweep(data, words, sites, m.stride, m.max_allele, off1, off2, D.FORMULA_SPARSE, D.FORMULA_DENSE, threads)
+
+
+# ---- fo_pairwise_differences_threaded: the bit-parallel all-pairs oracle of tests/test_gpu_scale_pairwise.py ----
+
+PD_PLOIDIES = [1, 2, 3, 4, 5, 9]
+PD_SITES = [1, 63, 64, 65, 200]   # around the 64-site word of the transpose
+PD_MAX_ALLELES = [1, 2, 3, 7, 9]  # 1, 2, 2, 3 and 4 allele bits
+PD_MISSING = [0.0, 0.05, 0.5]
+PD_SAMPLES = [2, 40, 7, 23, 31, 12]
+
+
+def _pd_case_data(case):
+    """(max_allele, missing fraction) of case = ploidy index p + 6 x site-count index q: allele range (p + q) % 5, missing fraction
+    (p + 2 q) % 3.  Every pair of {ploidy, site count, allele range, missing fraction} then meets all of its combinations
+    (test_c_pairwise_parameter_coverage)."""
+    p, q = case % len(PD_PLOIDIES), case // len(PD_PLOIDIES)
+    return PD_MAX_ALLELES[(p + q) % len(PD_MAX_ALLELES)], PD_MISSING[(p + 2 * q) % len(PD_MISSING)]
+
+
+def _pd_cohort(rng, sites, samples, ploidy, max_allele, p_missing):
+    """Random u8 matrix [sites][samples * ploidy] + missing words, and the same cohort as the reference's variants: every genotype the
+    prefix of its called alleles (CompressedGenotypes::get), None when the prefix is empty."""
+    Hc = samples * ploidy
+    data = rng.integers(0, max_allele + 1, size=(sites, Hc), dtype=np.uint8)
+    data[rng.random((sites, Hc)) < 0.4] = 0
+    miss = rng.random((sites, Hc)) < p_missing if p_missing > 0 else np.zeros((sites, Hc), dtype=bool)
+    data[miss] = 0
+    words = None
+    if p_missing > 0:
+        bits = np.packbits(miss.reshape(-1), bitorder="little")
+        words = np.frombuffer(np.concatenate([bits, np.zeros((-len(bits)) % 8, np.uint8)]).tobytes(), dtype="<u8").copy()
+    variants = []
+    for s in range(sites):
+        row = []
+        for i in range(samples):
+            g = []
+            for k in range(ploidy):
+                if miss[s, i * ploidy + k]:
+                    break
+                g.append(int(data[s, i * ploidy + k]))
+            row.append(g or None)
+        variants.append(R.make_variant(s + 1, row))
+    return data, words, variants
+
+
+def _pd_check_against_reference(data, words, variants, sites, samples, ploidy, max_allele, n, threads):
+    diff, both = D.pairwise_differences(data, words, sites, samples * ploidy, ploidy, n, max_allele, threads)
+    L = sites + 3  # sequence_length >= sites: `comparable` never clamps at 0
+    ref = R.calculate_pairwise_differences(variants, n, L)
+    assert len(ref) == n * (n - 1) // 2
+    first_len = [next((len(v.genotypes.get(i)) for v in variants if v.genotypes.get(i) is not None), 0) for i in range(n)]
+    for (i, j), d, comparable in ref:
+        assert int(diff[i, j]) == d, (i, j)
+        hi, hj = first_len[i], first_len[j]
+        if hi == 0 or hj == 0:  # a sample that is never called: the reference reports (0, 0)
+            assert int(both[i, j]) == 0 and comparable == 0
+            continue
+        lost = L * hi * hj - comparable
+        assert lost % (hi * hj) == 0
+        assert int(both[i, j]) == sites - lost // (hi * hj), (i, j)
+    assert not np.tril(diff).any() and not np.tril(both).any()
+    return diff, both
+
+
+@pytest.mark.parametrize("case", range(len(PD_PLOIDIES) * len(PD_SITES)))
+def test_c_pairwise_matches_python_oracle(case):
+    """diff equal to calculate_pairwise_differences (stats.rs:4106-4231) pair by pair, both recovered from its comparable-site count;
+    one thread and several threads give the same arrays."""
+    ploidy, sites = PD_PLOIDIES[case % len(PD_PLOIDIES)], PD_SITES[case // len(PD_PLOIDIES)]
+    max_allele, p_missing = _pd_case_data(case)
+    samples = PD_SAMPLES[(case + case // 6) % len(PD_SAMPLES)]
+    if ploidy >= 5 and sites == 200:
+        samples = min(samples, 12)  # the Python reference walks ploidy^2 allele pairs per site and sample pair
+    rng = np.random.default_rng(4106 + case)
+    data, words, variants = _pd_cohort(rng, sites, samples, ploidy, max_allele, p_missing)
+    diff, both = _pd_check_against_reference(data, words, variants, sites, samples, ploidy, max_allele, samples, 1)
+    for threads in (3, 16):
+        d2, b2 = D.pairwise_differences(data, words, sites, samples * ploidy, ploidy, samples, max_allele, threads)
+        assert np.array_equal(d2, diff) and np.array_equal(b2, both)
+
+
+def test_c_pairwise_parameter_coverage():
+    """The case table above meets every value the pin asks for, every (ploidy, missing fraction), every (max_allele, missing fraction) and
+    every (ploidy, max_allele) combination."""
+    cases = range(len(PD_PLOIDIES) * len(PD_SITES))
+    rows = [(PD_PLOIDIES[c % len(PD_PLOIDIES)],) + _pd_case_data(c) for c in cases]
+    assert {(p, m) for p, _, m in rows} == {(p, m) for p in PD_PLOIDIES for m in PD_MISSING}
+    assert {(a, m) for _, a, m in rows} == {(a, m) for a in PD_MAX_ALLELES for m in PD_MISSING}
+    assert {(p, a) for p, a, _ in rows} == {(p, a) for p in PD_PLOIDIES for a in PD_MAX_ALLELES}
+    sites = [PD_SITES[c // len(PD_PLOIDIES)] for c in cases]
+    assert {(s, r[1]) for s, r in zip(sites, rows)} == {(s, a) for s in PD_SITES for a in PD_MAX_ALLELES}
+    assert {(s, r[2]) for s, r in zip(sites, rows)} == {(s, m) for s in PD_SITES for m in PD_MISSING}
+    assert {PD_SAMPLES[(c + c // 6) % len(PD_SAMPLES)] for c in cases} >= {2, 40}
+
+
+@pytest.mark.parametrize("max_allele", [1, 3, 5])
+@pytest.mark.parametrize("p_missing", [0.05, 0.5])
+def test_c_pairwise_diploid_with_missing_slots(max_allele, p_missing):
+    """Ploidy 2 with calls missing slot by slot - (called, missing) is a haploid genotype, (missing, called) is None: the prefix rule the
+    full-size general cohorts of tests/test_gpu_scale_pairwise.py rest on."""
+    sites, samples = 150, 24
+    data, words, variants = _pd_cohort(np.random.default_rng(int(p_missing * 100) + max_allele), sites, samples, 2, max_allele, p_missing)
+    lengths = {len(g) for v in variants for g in (v.genotypes.get(i) for i in range(samples)) if g is not None}
+    assert lengths == {1, 2} and any(v.genotypes.get(i) is None for v in variants for i in range(samples))
+    _pd_check_against_reference(data, words, variants, sites, samples, 2, max_allele, samples, 3)
+
+
+@pytest.mark.parametrize("ploidy,max_allele,p_missing", [(2, 1, 0.0), (3, 5, 0.1), (1, 9, 0.3)])
+def test_c_pairwise_sample_subset(ploidy, max_allele, p_missing):
+    """n_samples < samples: the first n samples of wider rows (the stride stays the matrix's)."""
+    sites, samples = 130, 19
+    data, words, variants = _pd_cohort(np.random.default_rng(ploidy * 100 + max_allele), sites, samples, ploidy, max_allele, p_missing)
+    full, full_both = D.pairwise_differences(data, words, sites, samples * ploidy, ploidy, samples, max_allele, 2)
+    for n in (2, 7, samples - 1):
+        diff, both = _pd_check_against_reference(data, words, variants, sites, samples, ploidy, max_allele, n, 4)
+        assert np.array_equal(diff, full[:n, :n]) and np.array_equal(both, full_both[:n, :n])
+
+
+def test_c_pairwise_reference_literal_cases(kats):
+    """src/tests/stats_tests.rs:368-470 (the four tests behind kats['pairwise_differences']) through the C oracle: diff per pair, and
+    the comparable-site count rebuilt from `both` the way the reference counts it."""
+    n_expected = 0
+    for case in kats["pairwise_differences"]["cases"]:
+        n, L, sites = case["sample_count"], case["sequence_length"], len(case["variants"])
+        ploidy = max(len(g) for _, genos in case["variants"] for g in genos if g is not None)
+        data = np.zeros((sites, n * ploidy), dtype=np.uint8)
+        miss = np.zeros((sites, n * ploidy), dtype=bool)
+        for s, (_, genos) in enumerate(case["variants"]):
+            for i, g in enumerate(genos):
+                g = g or []
+                data[s, i * ploidy:i * ploidy + len(g)] = g
+                miss[s, i * ploidy + len(g):(i + 1) * ploidy] = True
+        bits = np.packbits(miss.reshape(-1), bitorder="little")
+        words = np.frombuffer(np.concatenate([bits, np.zeros((-len(bits)) % 8, np.uint8)]).tobytes(), dtype="<u8").copy()
+        diff, both = D.pairwise_differences(data, words if miss.any() else None, sites, n * ploidy, ploidy, n, int(data.max()), 2)
+        for key, (exp_diff, exp_comparable) in case["expected"].items():
+            i, j = (int(x) for x in key.split(","))
+            assert int(diff[i, j]) == exp_diff, (case["name"], key)
+            assert (L - (sites - int(both[i, j]))) * ploidy * ploidy == exp_comparable, (case["name"], key)
+            n_expected += 1
+    assert n_expected == 5
