@@ -86,6 +86,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_WC_BI_REPLICAS", &Options::wc_bi_replicas, 0, nullptr},
     {"FMH_WC_BI_CHUNKS", &Options::wc_bi_chunks, 0, nullptr},
     {"FMH_ROW_HI", &Options::row_hi, 1, nullptr},
+    {"FMH_COLUMN_WINDOW", &Options::column_window, 1, nullptr},
     {"FMH_PCA_EIGEN", &Options::pca_eigen, 0, "host=1,rocsolver=2,auto=0"},
     {"FMH_PCA_SPLITS", &Options::pca_splits, 0, nullptr},
     {"FMH_PCA_BUDGET_BYTES", &Options::pca_budget_bytes, (long long)16 << 30, nullptr},
@@ -406,8 +407,35 @@ static void free_planes(fmh_matrix* m) {
   pool_free(m->device, m->p0); pool_free(m->device, m->p1); pool_free(m->device, m->p2); pool_free(m->device, m->pc);
   pool_free(m->device, m->row_hi);
   pool_free(m->device, m->row_gap);
+  pool_free(m->device, m->row_alt);
   m->p0 = m->p1 = m->p2 = m->pc = nullptr;
   m->row_hi = m->row_gap = nullptr;
+  m->row_alt = nullptr;
+}
+// after the planes of a matrix have been written: the row totals of a biallelic matrix with nothing missing (row_alt_kernel), from which a sweep
+// whose groups partition the columns derives one group's counts without reading that group's vectors (sweep_window).  FMH_COLUMN_WINDOW=0: no
+// table; 1: matrices of at least 4 096 rows (the row_hi policy: smaller ones are swept in one launch-bound round, and run_vcf's small regions pay
+// no launch and synchronisation for a table); 2: any size (tests).  The table is rebuilt by EVERY call that wrote the planes and dropped by every
+// call that builds none - a table of other bytes would give silently wrong counts.  On the calling thread's own stream, synchronised before
+// return: every writer of the planes has synchronised by then (pack: hipDeviceSynchronize; uploads: their copy stream).
+static int build_row_totals(fmh_matrix* m) {
+  const long long mode = options().column_window.load();
+  if (!m->p0 || m->p1 || m->pc || m->max_allele > 1 || m->has_missing || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) {
+    pool_free(m->device, m->row_alt);
+    m->row_alt = nullptr;
+    return FMH_OK;
+  }
+  if (!m->row_alt && pool_malloc(m->device, (void**)&m->row_alt, m->variants * 4) != hipSuccess) { m->row_alt = nullptr; (void)hipGetLastError(); return FMH_OK; }  // no table: every group is counted
+  const int blocks = (int)std::min<size_t>((m->variants * 16 + 255) / 256, 1 << 16);
+  hipLaunchKernelGGL(row_alt_kernel, dim3(blocks), dim3(256), 0, hipStreamPerThread, (const uint8_t*)m->p0, m->plane_pitch, m->variants, m->columns, m->row_alt);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(hipStreamPerThread);
+  if (e != hipSuccess) {
+    pool_free(m->device, m->row_alt);
+    m->row_alt = nullptr;
+    return fail(FMH_ERR_HIP, "building the row totals failed: %s", hipGetErrorString(e));
+  }
+  return FMH_OK;
 }
 // after the planes of a matrix have been written: which rows have a bit above plane 0 (row_hi_kernel) and which have an uncalled column
 // (row_gap_kernel) - the sweeps read the upper / called planes of those rows only.  FMH_ROW_HI=0: no tables, every plane of every row is read
@@ -415,6 +443,7 @@ static void free_planes(fmh_matrix* m) {
 // synchronisation per small region of run_vcf; FMH_ROW_HI=2 builds them for any size - tests.)  A pack that builds no tables drops the ones an
 // earlier pack left: the planes are re-used when max_allele is unchanged, and a table of other bytes would skip rows that need their planes.
 static int mark_upper_plane_rows(fmh_matrix* m) {
+  FMH_TRY(build_row_totals(m));
   const long long mode = options().row_hi.load();
   if ((!m->p1 && !m->pc) || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) {
     pool_free(m->device, m->row_hi);
@@ -790,6 +819,27 @@ extern "C" int fmh_groups_create(const fmh_matrix* m, const uint8_t* h_mask, int
     }
     g->sizes[p] = cnt;
   }
+  // column geometry: each group's first and last vector with a member; disjoint = no column in two groups, covers = every column in some group
+  {
+    std::vector<uint8_t> seen(m->columns, 0);
+    bool disjoint = true;
+    for (int p = 0; p < n_groups; ++p) {
+      g->vec_first[p] = 1;
+      g->vec_last[p] = 0;
+      bool any = false;
+      for (uint32_t h = 0; h < m->columns; ++h) {
+        if (!h_mask[(size_t)p * m->columns + h]) continue;
+        if (!any) { g->vec_first[p] = h >> 7; any = true; }
+        g->vec_last[p] = h >> 7;
+        if (seen[h]) disjoint = false;
+        seen[h] = 1;
+      }
+    }
+    bool covers = true;
+    for (uint32_t h = 0; h < m->columns && covers; ++h) covers = seen[h] != 0;
+    g->disjoint = disjoint;
+    g->covers = covers;
+  }
   if (flat_len) {  // bits_len is a multiple of 256: the image is 16-byte aligned
     uint8_t* flat = staged.data() + bytes_len + bits_len;
     for (int p = 0; p < n_groups; ++p)
@@ -933,6 +983,58 @@ struct SweepResult {
   unsigned long long u64[kMaxU64];
 };
 
+// Column window.  A vector in which no group has a member adds zero to every count, so a sweep reads only the hull of
+// its groups' supports.  On a biallelic matrix with nothing missing the row's total alt count is a property of the resident image (row_alt), so
+// when one or two groups PARTITION the columns one of them need not be counted: alt[g] = row_alt - alt[other], integers, the same bits.  The
+// derived group is the one that leaves the shorter range to read (ties: the second group); nothing is derived when that saves no vector, e.g.
+// interleaved membership.  At least one vector is always read (the kernels' loops have no zero-trip form).
+// Short packed rows, biallelic, nothing missing: the LDS-staged flat-tile route (sweep_flat_kernels.hpp: one row per lane, scalar masks).
+// FMH_FLAT: 1 = wherever it is built, 0 = never, -1 = where it measured ahead of the four-lane route.
+static bool flat_route_taken(const fmh_matrix* m, const fmh_groups* g, int mode) {
+  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
+  const int P = mode == kModeWc ? wc_kernel_groups(m, g) : g->padded;
+  const long long want_flat = options().flat.load();
+  return packed && !m->has_missing && m->max_allele <= 1 && m->pvec <= (uint32_t)kFlatMaskMaxVec && g->mask_flat && flat_route_builds(P, mode) && want_flat != 0 &&
+         (want_flat > 0 || flat_route_default(P, mode, m->pvec));
+}
+ColumnWindow fmhi::sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode) {
+  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
+  ColumnWindow w{0, packed ? m->pvec : m->nvec, -1};
+  if (!packed || m->max_allele > 1 || m->has_missing || m->p1 || m->pc || options().column_window.load() == 0) return w;
+  if (flat_route_taken(m, g, mode)) return w;  // that route stages whole rows
+  auto hull = [&](int skip, uint32_t* first, uint32_t* count) {
+    uint32_t lo = UINT32_MAX, hi = 0;
+    for (int p = 0; p < g->n_groups; ++p) {
+      if (p == skip || g->vec_first[p] > g->vec_last[p]) continue;
+      lo = std::min(lo, g->vec_first[p]);
+      hi = std::max(hi, g->vec_last[p]);
+    }
+    if (lo == UINT32_MAX) { *first = 0; *count = 1; return; }  // no member anywhere: one vector, whose masks are zero
+    *first = lo;
+    *count = hi - lo + 1;
+  };
+  hull(-1, &w.first, &w.count);
+  if ((mode & kModeWc) == 0 && g->n_groups <= 2 && m->row_alt && g->disjoint && g->covers) {
+    for (int d = g->n_groups - 1; d >= 0; --d) {
+      uint32_t first, count;
+      hull(d, &first, &count);
+      if (count < w.count) { w.first = first; w.count = count; w.derived = d; }
+    }
+  }
+  return w;
+}
+
+extern "C" int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_t* first_vec, uint32_t* n_vec, int* derived_group) {
+  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
+  if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
+    return fail(FMH_ERR_INVALID, "groups were built for a different matrix geometry");
+  const ColumnWindow w = sweep_window(m, g, mode);
+  if (first_vec) *first_vec = w.first;
+  if (n_vec) *n_vec = w.count;
+  if (derived_group) *derived_group = w.derived;
+  return FMH_OK;
+}
+
 // Validates, fills the kernel arguments, picks the mask route and enqueues sweep + finalize on `st`: the 128 regional
 // accumulators land in b.out_f64 / b.out_u64 (device).  No synchronisation and no use of the shared workspace buffers, so
 // callers with private buffers (the pipelined sharded sweeps of comm.hip) need no device lock.  `*launched` = false when
@@ -975,6 +1077,20 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
   a.mask_pitch = g->mask_pitch;
   a.mask_bits = g->mask_bits;
   a.mask_flat = g->mask_flat;
+  // the column window: plane 0 and the bit masks advance to its first vector, the row is as long as the window; pitch and columns stay the row's.
+  // (The whole row and nothing derived: the launch is the one without a window, byte for byte.)
+  const ColumnWindow win = sweep_window(m, g, mode);
+  const uint32_t row_vecs = win.count;  // vectors a row of this sweep has: what sizes lanes per row, batch depth, LDS and deferral below
+  const bool windowed = packed && (win.first != 0 || win.count != m->pvec || win.derived >= 0);
+  a.derived_group = -1;
+  a.row_alt = nullptr;
+  if (windowed) {
+    a.mv.data = m->p0 + (size_t)win.first * 16;
+    a.mv.nvec = win.count;
+    a.mask_bits = g->mask_bits + (size_t)win.first * 8;  // one 16-bit word per 16 columns: eight per vector
+    a.derived_group = win.derived;
+    a.row_alt = win.derived >= 0 ? m->row_alt : nullptr;
+  }
   a.flat_slots = 0;
   a.flat_defer = 1;
   for (int p = 0; p < 8; ++p) a.group_size[p] = p < g->n_groups ? (uint32_t)g->sizes[p] : 0;
@@ -1027,7 +1143,7 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
     // W&C +3...+18 %, summaries -1...+8 % (profiles/r03/ab_eight_lanes_per_row.jsonl).  The 64-byte segments of the four-lane rows are not what holds them back.)
     const int env_punroll = (int)opt.packed_unroll.load();
     const int env_lpr = (int)opt.packed_lpr.load();
-    lpr = env_lpr == 4 || env_lpr == 16 ? env_lpr : (m->pvec <= 32 ? 4 : 16);
+    lpr = env_lpr == 4 || env_lpr == 16 ? env_lpr : (row_vecs <= 32 ? 4 : 16);
     // eight groups: the row loop of many batches is built with the shallow batches only (deeper ones kept P x U mask vectors and subset sums live and
     // spilled).  A biallelic row with nothing missing that ONE batch of loads per lane covers takes any depth: that loop (tile_rows_packed_prefetch,
     // MREG = false) re-reads its masks from LDS per row, and a 2 500-haplotype row is then one batch of five loads per lane instead of five trips
@@ -1039,12 +1155,12 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
       int best_u = us[0];
       size_t best = SIZE_MAX;
       for (int k = 0; k < nus; ++k) {
-        const size_t slots = round_up(m->pvec, (size_t)lpr * us[k]);
+        const size_t slots = round_up(row_vecs, (size_t)lpr * us[k]);
         if (slots <= best) { best = slots; best_u = us[k]; }
       }
       a.unroll = best_u;
       for (int k = 0; k < nus; ++k) if (env_punroll == us[k]) a.unroll = env_punroll;
-      a.nvec_pad = (uint32_t)round_up(m->pvec, (size_t)lpr * a.unroll);
+      a.nvec_pad = (uint32_t)round_up(row_vecs, (size_t)lpr * a.unroll);
     };
     const bool no_prefetch = opt.packed_no_prefetch.load() != 0;
     pick(P >= 5 && (general || missing || no_prefetch));
@@ -1108,11 +1224,7 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
     return fail(FMH_ERR_UNSUPPORTED, "unsupported sweep mode %d", mode);
   if (mask_mode == kMaskGlobalBytes && (P > 2 || mode == kModeWc))
     return fail(FMH_ERR_UNSUPPORTED, "%d group masks of %u columns exceed the LDS budget: sweep at most two groups at a time on rows this wide", P, m->columns);
-  // Short packed rows, biallelic, nothing missing: the LDS-staged flat-tile route (sweep_flat_kernels.hpp: one row per lane, scalar masks).
-  // FMH_FLAT: 1 = wherever it is built, 0 = never, -1 = where it measured ahead of the four-lane route.
-  const long long want_flat = opt.flat.load();
-  const bool flat = mask_mode == kMaskPacked && !mfma && !missing && !general && m->pvec <= (uint32_t)kFlatMaskMaxVec && g->mask_flat &&
-                    flat_route_builds(P, mode) && want_flat != 0 && (want_flat > 0 || flat_route_default(P, mode, m->pvec));
+  const bool flat = mask_mode == kMaskPacked && !windowed && !mfma && flat_route_taken(m, g, mode);
   int rc;
   if (flat) rc = launch_sweep_flat(P, mode, a, st, ctx, &grid);
   else if (mfma) rc = launch_sweep_mfma(P, mode, a, smem, st, ctx, &grid);

@@ -76,6 +76,7 @@ struct Options {
   std::atomic<long long> wc_bi_replicas{0};      // FMH_WC_BI_REPLICAS: 1 | 2 | 4 | 8 threads per pair in the biallelic pair kernel; 0 = by the lanes the last wave would waste
   std::atomic<long long> wc_bi_chunks{0};        // FMH_WC_BI_CHUNKS: row chunks of the biallelic pair kernel (measurement); 0 = about 8 192 workgroups
   std::atomic<long long> row_hi{1};              // FMH_ROW_HI: 0 = packed matrices get no tables of the rows with alleles above 1 / with uncalled columns (every plane of every row is read); 2 = tables at any size
+  std::atomic<long long> column_window{1};       // FMH_COLUMN_WINDOW: 0 = every sweep reads every vector of a row and no row totals are kept; 1 = sweeps read the vectors their groups have members in, row totals for packed biallelic matrices of >= 4 096 rows with nothing missing; 2 = row totals at any size
   std::atomic<long long> pca_eigen{0};           // FMH_PCA_EIGEN = host | rocsolver: the PCA's symmetric eigen solver; 0 = rocSOLVER, the host solver when it cannot be loaded
   std::atomic<long long> pca_splits{0};          // FMH_PCA_SPLITS: K splits of the PCA Gram (1 = none); 0 = by the tile count
   std::atomic<long long> pca_budget_bytes{(long long)16 << 30};  // FMH_PCA_BUDGET_BYTES: device memory one fmh_pca_gram call may use (Gram + bit words + slabs)
@@ -177,6 +178,15 @@ hipError_t unpack_rows(const fmh_matrix* m, size_t row0, size_t rows, uint8_t* d
 int enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, fmh::SweepArgs& a, hipStream_t st, const LaunchCtx& ctx,
                   const SweepBuffers& b, const double* harmonic, bool* launched);
 
+// What a sweep of `mode` over these groups reads of every row (abi.hip): vectors [first, first + count) of plane 0, and the
+// group whose alt count comes from the matrix's row totals instead of being counted (-1: none).  The whole row and -1 unless the image is
+// packed, biallelic and has nothing missing.
+struct ColumnWindow {
+  uint32_t first, count;
+  int derived;
+};
+ColumnWindow sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode);
+
 // the fused region sweep's kernel arguments and mode (abi.hip); the device's harmonic table
 int pair_region_args(const fmh_groups* g, size_t row_begin, size_t row_count, int summary_formula, int hudson_formula, const fmh_pair_diversity_sites* div,
                      const fmh_hudson_sites* sites, fmh::SweepArgs& a, int* mode);
@@ -230,6 +240,7 @@ struct fmh_matrix {
   // released (nullptr).
   uint8_t *p0 = nullptr, *p1 = nullptr, *p2 = nullptr, *pc = nullptr;
   uint8_t* row_gap = nullptr; // with pc: one byte per row, non-zero when some column of the row is not called (written wherever the planes are)
+  uint32_t* row_alt = nullptr;  // biallelic with nothing missing: popcount of plane 0 over the row's columns (rebuilt or dropped wherever the planes are written)
   uint8_t* row_hi = nullptr;  // with p1: one byte per row, non-zero when the row has a bit in plane 1 or 2 (written wherever the planes are)
   size_t plane_pitch = 0;
   uint32_t pvec = 0;
@@ -246,5 +257,9 @@ struct fmh_groups {
   uint32_t* mask_flat = nullptr;  // [round_up(ceil(columns / 128), 4)][padded][4]: the bit masks interleaved by vector (rows of at most 4 096 columns; same block)
   uint32_t columns = 0;
   uint64_t sizes[FMH_MAX_GROUPS] = {0};
+  // column geometry (fmh_groups_create): the first and last 128-column vector each group has a member in (first > last: no member), and whether
+  // the groups are pairwise disjoint / cover every column - together: a partition, the case in which one group's counts follow from the row totals
+  uint32_t vec_first[FMH_MAX_GROUPS] = {0}, vec_last[FMH_MAX_GROUPS] = {0};
+  bool disjoint = false, covers = false;
   std::vector<uint8_t> host_mask;  // [n_groups][columns] as handed in (the wide-matrix W&C route re-batches the groups)
 };

@@ -90,6 +90,11 @@ struct SweepArgs {
   int formula;
   int hudson_formula_p1;  // fused region sweep: formula of the HUDSON part + 1 when it differs from `formula` (which the population totals use); 0 = the same
   int max_allele;         // matrix max allele (general kernel loop bound upper limit)
+  // Column window (enqueue_sweep): mv.data, mv.nvec and mask_bits may describe only the vectors [first, first + n) of every row - the ones
+  // the groups of the sweep have members in; pitch and columns stay the row's.  When the groups partition the columns of a biallelic matrix with
+  // nothing missing, one group is not counted at all: its alt count is the row's total (row_alt, a table of the resident matrix) minus the other's.
+  int derived_group;      // -1 = every group is counted; else the group whose alt count is row_alt - (sum of the others'), one and two groups only
+  const uint32_t* row_alt;  // [variants] popcount of plane 0 over the row's columns; read only when derived_group >= 0
   // per-site outputs (nullable)
   uint32_t* alt;          // [P][row_count]
   uint32_t* called;       // [P][row_count]
@@ -765,6 +770,26 @@ __device__ __forceinline__ uint32_t allele_count_from_planes(uint32_t a, uint32_
     if ((T & a) == a) c += (__builtin_popcount(T ^ a) & 1) ? 0u - s[T - 1] : s[T - 1];
   }
   return c;
+}
+
+// Which kernels can take a derived group (SweepArgs::derived_group): packed, biallelic, nothing missing, one or two groups, not W&C
+template <int P, int MODE, bool MISSING, bool GENERAL, int MM>
+constexpr bool derive_kernel() { return MM == kMaskPacked && !GENERAL && !MISSING && P <= 2 && (MODE & kModeWc) == 0; }
+// the row total of the site this lane owns in the tile at `tile_row0` (rows past the end re-read the last one: their results are discarded)
+__device__ __forceinline__ uint32_t load_row_alt(const SweepArgs& A, size_t tile_row0, int lane) {
+  if (A.derived_group < 0) return 0u;
+  const size_t rel = tile_row0 + (size_t)lane;
+  return A.row_alt[A.row_begin + (rel < A.row_count ? rel : A.row_count - 1)];
+}
+// the derived group's alt count from the row total and the counted group's: integers, hence the bits a count of its own columns would give
+template <int P>
+__device__ __forceinline__ void derive_group(int derived, uint32_t row_alt, uint32_t (&alt)[P]) {
+  if (derived < 0) return;  // wave-uniform
+  if constexpr (P == 1) alt[0] = row_alt;
+  else if constexpr (P == 2) {
+    if (derived == 0) alt[0] = row_alt - alt[1];
+    else alt[1] = row_alt - alt[0];
+  }
 }
 
 // The LPR rows a group owns in one tile, for the commonest packed shape: biallelic, nothing missing, and a row that one
@@ -1509,6 +1534,7 @@ __global__ __launch_bounds__(kBlock, (sweep_min_blocks<P, MODE, GENERAL, MM, NPL
   // The prefetching row loop is kept on four-lane rows only: its variants for sixteen-lane rows cost this loop structure 40 VGPRs (two waves
   // per SIMD instead of three) for a path that long launches had stopped taking anyway.
   constexpr bool kDefer = defer_kernel<P, MODE, MISSING, GENERAL, MM, LPR>();
+  constexpr bool kDerive = derive_kernel<P, MODE, MISSING, GENERAL, MM>();
   if constexpr (kDefer) {
     {
       // (the only tile loop of these kernels: defer_tiles = 1 is the undeferred order, through the same code)
@@ -1527,6 +1553,8 @@ __global__ __launch_bounds__(kBlock, (sweep_min_blocks<P, MODE, GENERAL, MM, NPL
           uint32_t alt_mine[P], n_mine[P], n_all_mine = 0;
 #pragma unroll
           for (int p = 0; p < P; ++p) { alt_mine[p] = 0; n_mine[p] = 0; }
+          uint32_t row_alt = 0;  // issued before the tile's rows, consumed after them
+          if constexpr (kDerive) row_alt = load_row_alt(A, tile_row0, lane);
           bool counted = false;
           if constexpr (!MISSING && LPR != 16 && MM == kMaskPacked) {
             if (A.single_trip) {  // four-lane rows keep the prefetching row loop (level or 1-6 % ahead at every launch size)
@@ -1605,6 +1633,7 @@ __global__ __launch_bounds__(kBlock, (sweep_min_blocks<P, MODE, GENERAL, MM, NPL
               }
             }
           }
+          if constexpr (kDerive) derive_group<P>(A.derived_group, row_alt, alt_mine);
           uint32_t* slot = park + ((size_t)b * 64 + lane) * K;
 #pragma unroll
           for (int p = 0; p < P; ++p) { slot[p] = alt_mine[p]; if (MISSING) slot[P + p] = n_mine[p]; }
@@ -1661,6 +1690,8 @@ __global__ __launch_bounds__(kBlock, (sweep_min_blocks<P, MODE, GENERAL, MM, NPL
       for (int k = 0; k < NW; ++k) { wc.a[k] = 0.0; wc.b[k] = 0.0; }
     }
 
+    uint32_t row_alt = 0;  // issued before the tile's rows, consumed after them
+    if constexpr (kDerive) row_alt = load_row_alt(A, tile_row0, lane);
     bool rows_done = false;
     if constexpr (MM == kMaskPacked && !GENERAL && !MISSING) {
       if (A.single_trip) {
@@ -1982,6 +2013,7 @@ __global__ __launch_bounds__(kBlock, (sweep_min_blocks<P, MODE, GENERAL, MM, NPL
       }
     }
 
+    if constexpr (kDerive) derive_group<P>(A.derived_group, row_alt, mine.alt);
     if constexpr (!GENERAL) finish_biallelic_site<P, MODE>(mine, hud_dot);
 
     const size_t my_rel = tile_row0 + lane;
@@ -2006,6 +2038,7 @@ template <int P, int MODE, int U, int LPR>
 __device__ __forceinline__ void tiles_pipelined(const SweepArgs& A, const MatrixView& mv, const uint4* __restrict__ lm, uint32_t nvec_pad,
                                                 LaneTotals<P, MODE>& T) {
   constexpr bool MREG = P * U <= 12;
+  constexpr bool kDerive = derive_kernel<P, MODE, false, false, kMaskPacked>();
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int grp = lane / LPR, gl = lane % LPR;
@@ -2060,6 +2093,8 @@ __device__ __forceinline__ void tiles_pipelined(const SweepArgs& A, const Matrix
     uint32_t alt_mine[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) alt_mine[p] = 0;
+    uint32_t row_alt = 0;  // issued before the tile's rows, consumed after them
+    if constexpr (kDerive) row_alt = load_row_alt(A, tile * kTileRows, lane);
 #pragma unroll
     for (int s = 0; s < LPR; s += 2) {
       count_row(a, s, alt_mine);
@@ -2067,6 +2102,7 @@ __device__ __forceinline__ void tiles_pipelined(const SweepArgs& A, const Matrix
       count_row(b, s + 1, alt_mine);
       if (s + 3 < LPR) load_row(b, tile, s + 3); else load_row(b, nxt, s + 3 - LPR);
     }
+    if constexpr (kDerive) derive_group<P>(A.derived_group, row_alt, alt_mine);
     SiteTally<P> mine;
     WcSite<P> wc;
     double hud_dot = 0.0;

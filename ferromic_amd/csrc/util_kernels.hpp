@@ -194,6 +194,32 @@ __global__ __launch_bounds__(256) void row_gap_kernel(const uint8_t* __restrict_
   }
 }
 
+// row_alt[r] = set bits of plane 0 among the first `columns` bits of row r (the tail of the last vector is masked: fmh_matrix_create_packed takes
+// the caller's planes as they are).  On a biallelic matrix with nothing missing that is the row's alt count over ALL columns - a property of the
+// resident image, whatever the groups of a sweep: a sweep whose groups partition the columns counts all but one of them and takes that one's
+// count from here (SweepArgs::derived_group).  Sixteen lanes per row.
+__global__ __launch_bounds__(256) void row_alt_kernel(const uint8_t* __restrict__ p0, size_t plane_pitch, size_t rows, uint32_t columns,
+                                                      uint32_t* __restrict__ row_alt) {
+  const size_t group = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 16, groups = (size_t)gridDim.x * blockDim.x / 16;
+  const uint32_t gl = threadIdx.x % 16, nvec = (uint32_t)(plane_pitch / 16);
+  for (size_t r = group; r < rows; r += groups) {
+    uint32_t alt = 0;
+    for (uint32_t v = gl; v < nvec; v += 16) {
+      const uint4 a = *reinterpret_cast<const uint4*>(p0 + r * plane_pitch + (size_t)v * 16);
+      const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t lo = v * 128 + 32 * k;  // column of the word's bit 0
+        const uint32_t keep = lo + 32 <= columns ? ~0u : (lo >= columns ? 0u : (1u << (columns - lo)) - 1u);
+        alt += __popc(w[k] & keep);
+      }
+    }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) alt += __shfl_xor(alt, off, 64);
+    if (gl == 0) row_alt[r] = alt;
+  }
+}
+
 // row_hi[r] = 1 when row r of a packed multi-allelic matrix has a bit in plane 1 or plane 2 (a called allele above 1), else 0: the sweeps
 // read the upper planes of those rows only (MatrixView::row_hi).  Sixteen lanes per row, as many 16-byte vectors each as the row needs.
 __global__ __launch_bounds__(256) void row_hi_kernel(const uint8_t* __restrict__ p1, const uint8_t* __restrict__ p2, size_t plane_pitch, size_t rows,

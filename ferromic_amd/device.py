@@ -200,6 +200,16 @@ class Groups:
             pass
 
 
+SWEEP_SUMMARY, SWEEP_HUDSON, SWEEP_DIVERSITY, SWEEP_REGION, SWEEP_WC = 1, 3, 5, 7, 8  # FMH_SWEEP_* of include/ferromic_hip.h
+
+
+def sweep_window(m: DeviceMatrix, g: Groups, mode: int):
+    """fmh_sweep_window: (first vector, vectors, derived group or -1) - what the next sweep of `mode` reads of every row."""
+    first, count, derived = C.c_uint32(), C.c_uint32(), C.c_int()
+    _abi.check(_abi.load().fmh_sweep_window(m._h, g._h, mode, C.byref(first), C.byref(count), C.byref(derived)))
+    return first.value, count.value, derived.value
+
+
 def _pop_totals(t: _abi.PopTotals) -> Dict[str, float]:
     return dict(haplotype_capacity=int(t.haplotype_capacity), segregating_sites=int(t.segregating_sites),
                 uncallable_sites=int(t.uncallable_sites), pi_sum=float(t.pi_sum))

@@ -74,7 +74,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_LAYOUT (bytes | packed)   FMH_MASK_MODE (1 | 2)   FMH_DEFER_TILES (1..16)   FMH_PACKED_LPR (4 | 16)   FMH_PACKED_UNROLL
  *   FMH_PACKED_NO_PREFETCH   FMH_COUNTS_MFMA (1 | 2)   FMH_GRID_PER_CU   FMH_GRID_BLOCKS   FMH_MAX_OCC   FMH_UNROLL   FMH_PITCH_ALIGN
  *   FMH_COMM_TRANSPORT (host | rccl)   FMH_UPLOAD_THREADS   FMH_PD_TWO_PLANES   FMH_PD_INT8   FMH_PD_PLANES_BYTES   FMH_PD_KCHUNK
- *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH
+ *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -180,6 +180,18 @@ int fmh_matrix_generate(fmh_matrix* m, uint64_t seed, uint64_t first_global_site
 int fmh_groups_create(const fmh_matrix* m, const uint8_t* h_column_mask, int n_groups, fmh_groups** out);
 int fmh_groups_destroy(fmh_groups* g);
 int fmh_groups_sizes(const fmh_groups* g, int* n_groups, uint64_t* h_sizes /* [n_groups] mask popcounts */);
+
+/* Host only: what the next sweep of `mode` over these groups reads of every row of a packed matrix - the 16-byte vectors (128 columns each)
+ * [*first_vec, *first_vec + *n_vec) of bit plane 0 - and the group whose counts it derives from the matrix's row totals instead of counting
+ * (-1: none).  A sweep skips the vectors none of its groups has a member in; on a biallelic matrix with nothing missing whose one or two groups
+ * partition the columns it also skips one group's vectors (FMH_COLUMN_WINDOW: 0 = never, 1 = default, row totals kept for matrices of at
+ * least 4 096 rows, 2 = at any size).  Every other matrix: the whole row and -1.  Results never depend on the window. */
+#define FMH_SWEEP_SUMMARY 1   /* fmh_population_summaries */
+#define FMH_SWEEP_HUDSON 3    /* fmh_hudson_sweep */
+#define FMH_SWEEP_DIVERSITY 5 /* fmh_diversity_sites */
+#define FMH_SWEEP_REGION 7    /* fmh_pair_region_sweep */
+#define FMH_SWEEP_WC 8        /* fmh_wc_sweep */
+int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_t* first_vec, uint32_t* n_vec, int* derived_group);
 
 /* ---- per-population summary sweep ------------------------------------------------------------ */
 typedef struct {

@@ -34,6 +34,9 @@ def main():
         poc = np.zeros(H, dtype=np.uint8)
         poc[H // 2:] = 1
         masks = np.stack([(poc == 0), (poc == 1)]).astype(np.uint8)
+        if os.environ.get("AB_MASKS") == "interleaved":  # even samples | odd samples: no vector without members of both groups (the data keeps its two halves)
+            even = (np.arange(H) // 2 % 2 == 0)
+            masks = np.stack([even, ~even]).astype(np.uint8)
         thr = bench.synthetic_thresholds(S, 0, S + N)
         missing = layout.endswith(":m")  # SITESxSAMPLES:packed:m = 1 % missing calls
         layout = layout.split(":")[0]
@@ -82,7 +85,7 @@ def main():
                     res.setdefault(name, []).append(ms.value / max(n.value, 1))
             _abi.set_option(var, None)
             a, b = min(res["unset"]), min(res["set"])
-            print(json.dumps({"switch": sys.argv[1], "kind": kind, "sites": rows, "haplotypes": H, "layout": layout + (" +1% missing" if missing else ""), "unset_ms": round(a, 4), "set_ms": round(b, 4),
+            print(json.dumps({"switch": sys.argv[1], "kind": kind, "masks": os.environ.get("AB_MASKS", "halves"), "sites": rows, "haplotypes": H, "layout": layout + (" +1% missing" if missing else ""), "unset_ms": round(a, 4), "set_ms": round(b, 4),
                               "set_over_unset": round(b / a, 4), "all_unset": [round(x, 4) for x in res["unset"]], "all_set": [round(x, 4) for x in res["set"]]}), flush=True)
         del bufs, groups, dm, sweep
 
