@@ -28,6 +28,8 @@ from ._core import (  # noqa: E402,F401
     hudson_fst_sites,
     hudson_fst_with_sites,
     inversion_allele_frequency,
+    ld_prune,
+    ld_r2,
     nucleotide_diversity,
     pairwise_differences,
     per_chromosome_pca,

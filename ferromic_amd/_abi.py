@@ -91,6 +91,10 @@ class PairDiversitySites(C.Structure):
     _fields_ = [("d_pi", C.c_void_p), ("d_theta", C.c_void_p)]
 
 
+class LdBandOut(C.Structure):
+    _fields_ = [("r2", C.c_void_p), ("n_ab", C.c_void_p), ("n_joint", C.c_void_p), ("over", C.c_void_p)]
+
+
 class WcTotals(C.Structure):
     _fields_ = [
         ("sum_a", C.c_double * (1 + MAX_PAIRS)),
@@ -144,6 +148,10 @@ SYMBOLS = {
     "fmh_pca_gram": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "fmh_pca_eigen_scores": (_i, [_i, _vp, _sz, _sz, _vp, _vp]),
     "fmh_pca_eigen_host": (_i, [_vp, _sz, _vp]),
+    "fmh_ld_band": (_i, [_vp, _vp, _sz, _sz, _sz, _sz, _d, _P(LdBandOut), _vp, _vp, _vp]),
+    "fmh_ld_prune": (_i, [_vp, _vp, _sz, _sz, _sz, _d, _vp, _vp]),
+    "fmh_ld_prune_chunked": (_i, [_vp, _vp, _sz, _sz, _sz, _d, _vp, _sz, _vp]),
+    "fmh_ld_prune_bits": (_i, [_vp, _sz, _sz, _vp]),
     "fmh_hudson_totals_pack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_hudson_totals_unpack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_pop_totals_pack": (_i, [_P(PopTotals), _i, _P(_d), _P(_u64)]),

@@ -1,0 +1,121 @@
+// pymodule_ld.inc — ferromic.ld_r2 / ld_prune and Population.ld_r2 / ld_prune (included inside pymodule_stats.inc's namespace, after the
+// statistics whose argument handling they share).  An addition to the reference's surface: it has no linkage-disequilibrium code; the
+// definition is include/ferromic_hip.h's (fmh_ld_band, fmh_ld_prune).  Sites are the rows of one resident matrix, the columns the haplotypes
+// asked for; every number comes from the device, the GIL is released around the calls.
+
+void ld_validate(size_t n_haplotypes, int64_t sites_apart, const char* what, const double* threshold) {
+  if (n_haplotypes < 2) value_error("at least two haplotypes are required for linkage disequilibrium");
+  if (sites_apart <= 0) value_error(string(what) + " must be a positive integer");
+  if (threshold && !(*threshold >= 0.0 && *threshold <= 1.0)) value_error("r2_threshold must lie in [0, 1]");  // NaN fails both comparisons
+}
+
+py::array_t<double> ld_r2_rows(const DevMatrix& dm, const vector<uint8_t>& mask, size_t r0, size_t rc, size_t band) {
+  py::array_t<double> out(std::vector<py::ssize_t>{(py::ssize_t)rc, (py::ssize_t)band});
+  if (rc == 0) return out;
+  const shared_ptr<Groups> gp = groups_for(dm, {mask});
+  DevBuf d_r2(dm.device, rc * band * sizeof(double));
+  fmh_ld_band_out bufs;
+  memset(&bufs, 0, sizeof bufs);
+  bufs.r2 = (double*)d_r2.p;
+  double* host = out.mutable_data();
+  int status;
+  {
+    py::gil_scoped_release nogil;
+    status = fmh_ld_band(dm.h, gp->h, r0, rc, r0 + rc, band, 0.0, &bufs, nullptr, nullptr, nullptr);
+    if (status == FMH_OK) status = fmh_copy_to_host(dm.device, host, d_r2.p, rc * band * sizeof(double), nullptr);
+  }
+  fmh_check(status);
+  return out;
+}
+
+py::array_t<bool> ld_prune_rows(const DevMatrix& dm, const vector<uint8_t>& mask, size_t r0, size_t rc, size_t window, double threshold) {
+  py::array_t<bool> out((py::ssize_t)rc);
+  if (rc == 0) return out;
+  const shared_ptr<Groups> gp = groups_for(dm, {mask});
+  vector<uint8_t> keep(rc, 0);
+  int status;
+  {
+    py::gil_scoped_release nogil;
+    status = fmh_ld_prune(dm.h, gp->h, r0, rc, window, threshold, keep.data(), nullptr);
+  }
+  fmh_check(status);
+  bool* o = out.mutable_data();
+  for (size_t i = 0; i < rc; ++i) o[i] = keep[i] != 0;
+  return out;
+}
+
+// the rows of `region` (every variant when None) of a variant list, resident: (matrix, first row, rows, column mask); rows == 0 = nothing to do
+struct LdRows {
+  shared_ptr<DevMatrix> dm;
+  size_t r0 = 0, rc = 0;
+  vector<uint8_t> mask;
+};
+LdRows ld_rows_from_variants(const py::object& variants, const vector<Hap>& haps, const py::object& region) {
+  LdRows out;
+  auto store = store_from_python(variants);
+  if (store->S == 0) return out;
+  shared_ptr<const Store> sub = store;
+  if (!region.is_none()) {
+    const Region reg = build_region(region);
+    if (region_len(reg) <= 0) return out;
+    const vector<int64_t> rows = region_rows(*store, reg.start, reg.end);
+    if (rows.empty()) return out;
+    sub = store_subset(store, rows);
+  }
+  out.mask = store->mask_for(haps, store->first_sample_count());  // membership from the FIRST variant's sample count, as per_site_diversity
+  auto [dm, r0, rc] = sub->device_rows();
+  out.dm = dm; out.r0 = r0; out.rc = rc;
+  return out;
+}
+
+py::array_t<double> ld_r2(const py::object& variants, const py::object& haplotypes, int64_t max_sites_apart, const py::object& region) {
+  const vector<Hap> haps = parse_haplotypes(haplotypes);
+  ld_validate(haps.size(), max_sites_apart, "max_sites_apart", nullptr);
+  const LdRows rows = ld_rows_from_variants(variants, haps, region);
+  if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
+  return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
+}
+
+py::array_t<bool> ld_prune(const py::object& variants, const py::object& haplotypes, int64_t window_sites, double r2_threshold, const py::object& region) {
+  const vector<Hap> haps = parse_haplotypes(haplotypes);
+  ld_validate(haps.size(), window_sites, "window_sites", &r2_threshold);
+  const LdRows rows = ld_rows_from_variants(variants, haps, region);
+  if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
+  return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
+}
+
+// a Population's own haplotypes over its resident matrix: the dense one of from_numpy, else the variant store's
+LdRows ld_rows_from_population(const Population& pop) {
+  LdRows out;
+  if (pop.dense) {
+    if (pop.dense->variants == 0) return out;
+    out.mask = pop.dense->mask_for(pop.haplotypes);
+    out.dm = pop.dense->device_matrix();
+    out.rc = out.dm->variants;
+    return out;
+  }
+  if (pop.store->S == 0) return out;
+  out.mask = pop.store->mask_for(pop.haplotypes, pop.store->first_sample_count());
+  auto [dm, r0, rc] = pop.store->device_rows();
+  out.dm = dm; out.r0 = r0; out.rc = rc;
+  return out;
+}
+
+py::array_t<double> population_ld_r2(const Population& pop, int64_t max_sites_apart) {
+  ld_validate(pop.haplotypes.size(), max_sites_apart, "max_sites_apart", nullptr);
+  const LdRows rows = ld_rows_from_population(pop);
+  if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
+  return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
+}
+
+py::array_t<bool> population_ld_prune(const Population& pop, int64_t window_sites, double r2_threshold) {
+  ld_validate(pop.haplotypes.size(), window_sites, "window_sites", &r2_threshold);
+  const LdRows rows = ld_rows_from_population(pop);
+  if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
+  return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
+}
+
+void bind_ld(py::module_& m) {
+  m.def("ld_r2", &ld_r2, py::arg("variants"), py::arg("haplotypes"), py::arg("max_sites_apart"), py::arg("region") = py::none());
+  m.def("ld_prune", &ld_prune, py::arg("variants"), py::arg("haplotypes"), py::arg("window_sites"), py::arg("r2_threshold"), py::arg("region") = py::none());
+}

@@ -442,3 +442,53 @@ def pca_eigen_scores(device: int, gram, n_components: int):
     values, scores = np.empty(n_components, dtype=np.float64), np.empty((n, n_components), dtype=np.float64)
     _abi.check(_abi.load().fmh_pca_eigen_scores(device, buf.ptr, n, n_components, _ptr(values), _ptr(scores)))
     return values, scores
+
+
+# ---- linkage disequilibrium ------------------------------------------------------------------------------------------------------
+@dataclass
+class LdBandResult:
+    r2: Optional[np.ndarray]       # [rows][band] float64
+    n_ab: Optional[np.ndarray]     # [rows][band] uint32
+    n_joint: Optional[np.ndarray]
+    over: Optional[np.ndarray]     # [rows][ceil(band / 32)] uint32
+    site_n: Optional[np.ndarray]   # [rows] uint32
+    site_alt: Optional[np.ndarray]
+
+
+def ld_band(m: DeviceMatrix, g: Optional[Groups], band: int, threshold: float = 0.0, row_begin: int = 0, row_count: Optional[int] = None,
+            partner_end: Optional[int] = None, want=("r2", "n_ab", "n_joint", "over", "site_n", "site_alt")) -> LdBandResult:
+    """fmh_ld_band: r^2 and its counts between rows [row_begin, row_begin + row_count) and their next `band` rows below partner_end
+    (default: the end of the rows asked for); `want` names the outputs to ask for."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    pend = row_begin + rows if partner_end is None else partner_end
+    band, words = int(band), (int(band) + 31) // 32
+    sizes = {"r2": 8 * rows * band, "n_ab": 4 * rows * band, "n_joint": 4 * rows * band, "over": 4 * rows * words, "site_n": 4 * rows, "site_alt": 4 * rows}
+    bufs = {k: DeviceBuffer(m.device, max(sizes[k], 4)) for k in want}
+    out = _abi.LdBandOut(*(bufs[k].ptr if k in bufs else None for k in ("r2", "n_ab", "n_joint", "over")))
+    _abi.check(_abi.load().fmh_ld_band(m._h, g._h if g is not None else None, row_begin, rows, pend, band, float(threshold), C.byref(out),
+                                       bufs["site_n"].ptr if "site_n" in bufs else None, bufs["site_alt"].ptr if "site_alt" in bufs else None, None))
+
+    def fetch(k, dtype, shape):
+        return bufs[k].to_numpy(dtype, int(np.prod(shape))).reshape(shape) if k in bufs else None
+
+    return LdBandResult(fetch("r2", np.float64, (rows, band)), fetch("n_ab", np.uint32, (rows, band)), fetch("n_joint", np.uint32, (rows, band)),
+                        fetch("over", np.uint32, (rows, words)), fetch("site_n", np.uint32, (rows,)), fetch("site_alt", np.uint32, (rows,)))
+
+
+def ld_prune(m: DeviceMatrix, g: Optional[Groups], window: int, threshold: float, row_begin: int = 0, row_count: Optional[int] = None,
+             chunk_rows: int = 0) -> np.ndarray:
+    """fmh_ld_prune (fmh_ld_prune_chunked when chunk_rows is given): the forward greedy keep flags of the rows, as bool."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    keep = np.zeros(rows, dtype=np.uint8)
+    _abi.check(_abi.load().fmh_ld_prune_chunked(m._h, g._h if g is not None else None, row_begin, rows, int(window), float(threshold), _ptr(keep),
+                                                int(chunk_rows), None))
+    return keep.astype(bool)
+
+
+def ld_prune_bits(over: np.ndarray, band: int) -> np.ndarray:
+    """fmh_ld_prune_bits: the greedy rule over an `over` band [rows][ceil(band / 32)] on the host (no device)."""
+    over = np.ascontiguousarray(over, dtype=np.uint32)
+    rows = over.shape[0]
+    keep = np.zeros(rows, dtype=np.uint8)
+    _abi.check(_abi.load().fmh_ld_prune_bits(_ptr(over), rows, int(band), _ptr(keep)))
+    return keep.astype(bool)

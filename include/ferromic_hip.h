@@ -397,6 +397,59 @@ int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t n_componen
                          double* h_scores /* n x n_components, row-major */);
 int fmh_pca_eigen_host(double* h_matrix, size_t n, double* h_eigenvalues);
 
+/* ---- linkage disequilibrium (the project's own definition: the reference has no LD code) ---------------------------- */
+/*
+ * r^2 between a site and the sites that follow it, and LD pruning, from the bit-packed image (one bit per haplotype and row: the
+ * haplotype counts of a site pair are popcounts of the AND of two rows).  Columns are the haplotypes of the matrix, restricted to the
+ * one group of `g_or_null` when given (mask M; all columns otherwise).  For site i: C_i = called & M, A_i = (allele >= 1) & C_i - the OR
+ * of the allele planes, so a multi-allelic site counts "non-reference".  For a pair i < j:
+ *   n = |C_i & C_j|   nA = |A_i & C_j|   nB = |A_j & C_i|   nAB = |A_i & A_j|
+ *   D = n * nAB - nA * nB                                               (64-bit integers, exact)
+ *   r2 = ((double)D * (double)D) / ((double)(nA * (n - nA)) * (double)(nB * (n - nB)))
+ * - the squared Pearson correlation of the two indicator vectors over the jointly called columns.  The integer products are formed in
+ * 64-bit integers and converted (each is below 2^53 for every row width the packed layout takes), which leaves three roundings and no
+ * fused multiply-add: the value can be reproduced bit for bit on a host.  r2 is a quiet NaN when nA * (n - nA) == 0 or
+ * nB * (n - nB) == 0: a site that is monomorphic among the jointly called columns, and n == 0.
+ *
+ * Band addressing: pairs are (i, d), partner j = i + d, 1 <= d <= band; a band buffer is [row_count][band], entry
+ * (i - row_begin) * band + (d - 1).  All index arithmetic is 64-bit.
+ *
+ * fmh_ld_band: rows [row_begin, row_begin + row_count), partners j < partner_end (row_begin + row_count <= partner_end <= variants: the
+ *   partners may reach beyond the rows asked for, which is how a caller walks a range in chunks).  Every output is optional.  Entries with
+ *   j >= partner_end are WRITTEN: r2 = NaN, counts 0, bit 0.  `over` holds bit (d - 1) & 31 of word (d - 1) >> 5 = r2 > threshold (NaN
+ *   never exceeds), whole words, the padding bits of the last word zero.  d_site_n / d_site_alt [row_count] = |C_i| / |A_i|.
+ *   One 256-thread workgroup per 64 rows x 64 values of d; no scratch memory and no atomics: two calls give the same bits.
+ *   Enqueues on `stream` and synchronises it, as fmh_pairwise_differences does.
+ * fmh_ld_prune: forward greedy thinning, deterministic: keep[*] = 1; for i ascending, if keep[i], every j = i + d (1 <= d <= window,
+ *   j < row_begin + row_count) with r2(i, j) > threshold gets keep[j] = 0.  A removed site removes nothing.  The band kernel runs with
+ *   only `over`, in row chunks whose threshold bits stay within 64 MiB of device scratch from the library's pool (and as much host
+ *   memory) - at least 64 rows per chunk - pairs reaching into the next chunk; the rule is applied chunk by chunk on the host, in order.
+ *   fmh_ld_prune_chunked is the same with the chunk length given (0 = the 64 MiB rule): what the tests force a chunk boundary with.
+ * fmh_ld_prune_bits: the greedy rule alone over the `over` band of one fmh_ld_band call with partner_end = row_begin + row_count
+ *   (bits of partners beyond row_count are ignored).  Host only, no device.
+ *
+ * Refusals, before anything is enqueued: a matrix without a packed image FMH_ERR_UNSUPPORTED (call fmh_matrix_pack first); band / window
+ * == 0, row_begin + row_count > partner_end, partner_end > variants, a group handle with n_groups != 1, a NULL output struct, a NaN
+ * threshold FMH_ERR_INVALID; no GPU FMH_ERR_NO_DEVICE.  row_count == 0 is FMH_OK.
+ */
+typedef struct {            /* all nullable; each [row_count][band] except over */
+  double*   r2;
+  uint32_t* n_ab;
+  uint32_t* n_joint;        /* n of the pair */
+  uint32_t* over;           /* [row_count][ceil(band/32)]: bit (d-1)&31 of word (d-1)>>5 = r2 > threshold */
+} fmh_ld_band_out;
+
+int fmh_ld_band(const fmh_matrix* m, const fmh_groups* g_or_null /* exactly 1 group */, size_t row_begin, size_t row_count,
+                size_t partner_end /* j < partner_end <= variants */, size_t band, double threshold,
+                const fmh_ld_band_out* d_out, uint32_t* d_site_n_or_null /* |C_i| */, uint32_t* d_site_alt_or_null /* |A_i| */,
+                void* stream);
+int fmh_ld_prune(const fmh_matrix* m, const fmh_groups* g_or_null, size_t row_begin, size_t row_count, size_t window,
+                 double threshold, uint8_t* h_keep /* [row_count] */, void* stream);
+int fmh_ld_prune_chunked(const fmh_matrix* m, const fmh_groups* g_or_null, size_t row_begin, size_t row_count, size_t window,
+                         double threshold, uint8_t* h_keep /* [row_count] */, size_t chunk_rows /* 0 = by the scratch bound */,
+                         void* stream);
+int fmh_ld_prune_bits(const uint32_t* h_over, size_t row_count, size_t band, uint8_t* h_keep);   /* host only, no device */
+
 /* ---- multi-GPU: region sharding + RCCL reduce of the regional accumulators -------------------------------- */
 /*
  * Sites are independent: rank r of G sweeps only its contiguous slab of the region and writes its own
