@@ -87,6 +87,10 @@ const OptionRow kOptionRows[] = {
     {"FMH_WC_BI_CHUNKS", &Options::wc_bi_chunks, 0, nullptr},
     {"FMH_ROW_HI", &Options::row_hi, 1, nullptr},
     {"FMH_COLUMN_WINDOW", &Options::column_window, 1, nullptr},
+    {"FMH_TILED_PLANES", &Options::tiled_planes, 1, nullptr},
+    {"FMH_TILED_BYTES", &Options::tiled_bytes, (long long)16 << 30, nullptr},
+    {"FMH_TILED", &Options::tiled, -1, nullptr},
+    {"FMH_TILED_BATCH", &Options::tiled_batch, 0, nullptr},
     {"FMH_PCA_EIGEN", &Options::pca_eigen, 0, "host=1,rocsolver=2,auto=0"},
     {"FMH_PCA_SPLITS", &Options::pca_splits, 0, nullptr},
     {"FMH_PCA_BUDGET_BYTES", &Options::pca_budget_bytes, (long long)16 << 30, nullptr},
@@ -408,9 +412,55 @@ static void free_planes(fmh_matrix* m) {
   pool_free(m->device, m->row_hi);
   pool_free(m->device, m->row_gap);
   pool_free(m->device, m->row_alt);
+  pool_free(m->device, m->p0t);
   m->p0 = m->p1 = m->p2 = m->pc = nullptr;
   m->row_hi = m->row_gap = nullptr;
   m->row_alt = nullptr;
+  m->p0t = nullptr;
+  m->p0t_bytes = 0;
+}
+// after the planes of a matrix have been written, beside the row totals and under the same eligibility: plane 0 once more, tile-transposed
+// (tile_planes_kernel), for the sweeps of sweep_tiled.hip.  FMH_TILED_PLANES=0: no image; 1 (default): matrices of at least 4 096 rows whose image fits under
+// FMH_TILED_BYTES and leaves as much again free on the device; 2: any size, no free-memory test (tests).  Rebuilt by EVERY call that wrote the
+// planes and dropped by every call that builds none, like the row totals; a refusal or a failed allocation leaves no image, and every sweep then
+// takes the row-major routes.
+static void drop_tiled_planes(fmh_matrix* m) {
+  pool_free(m->device, m->p0t);
+  m->p0t = nullptr;
+  m->p0t_bytes = 0;
+}
+static int build_tiled_planes(fmh_matrix* m) {
+  const long long mode = options().tiled_planes.load();
+  const size_t bytes = (m->variants + 63) / 64 * (size_t)m->pvec * 1024;
+  bool want = m->p0 && !m->p1 && !m->pc && m->max_allele <= 1 && !m->has_missing && m->variants != 0 && mode != 0 && (mode == 2 || m->variants >= 4096);
+  if (want && mode != 2) {
+    const long long limit = options().tiled_bytes.load();
+    if (limit < 0) drop_tiled_planes(m);
+    if (limit < 0) return fail(FMH_ERR_INVALID, "FMH_TILED_BYTES=%lld: a byte count cannot be negative (FMH_TILED_PLANES=0 keeps no image)", limit);
+    if (bytes > (size_t)limit) want = false;
+    else if (!m->p0t || m->p0t_bytes != bytes) {  // (an image kept from the last pack is memory already held)
+      size_t free_b = 0, total_b = 0;
+      FMH_TRY(use_device(m->device));  // hipMemGetInfo answers for the current device
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); want = false; }
+      else if (free_b / 2 < bytes) want = false;
+    }
+  }
+  if (!want) { drop_tiled_planes(m); return FMH_OK; }
+  if (m->p0t && m->p0t_bytes != bytes) drop_tiled_planes(m);
+  if (!m->p0t) {
+    if (pool_malloc(m->device, (void**)&m->p0t, bytes) != hipSuccess) { m->p0t = nullptr; (void)hipGetLastError(); return FMH_OK; }  // no image: the row-major routes
+    m->p0t_bytes = bytes;
+  }
+  const size_t items = (m->variants + 63) / 64 * (((size_t)m->pvec + kTileVecs - 1) / kTileVecs);
+  const int blocks = (int)std::min<size_t>(items, 1 << 20);
+  hipLaunchKernelGGL(tile_planes_kernel, dim3(blocks), dim3(256), 0, hipStreamPerThread, (const uint8_t*)m->p0, m->plane_pitch, m->variants, m->pvec, m->p0t);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(hipStreamPerThread);
+  if (e != hipSuccess) {
+    drop_tiled_planes(m);
+    return fail(FMH_ERR_HIP, "building the tile-transposed plane image failed: %s", hipGetErrorString(e));
+  }
+  return FMH_OK;
 }
 // after the planes of a matrix have been written: the row totals of a biallelic matrix with nothing missing (row_alt_kernel), from which a sweep
 // whose groups partition the columns derives one group's counts without reading that group's vectors (sweep_window).  FMH_COLUMN_WINDOW=0: no
@@ -444,6 +494,7 @@ static int build_row_totals(fmh_matrix* m) {
 // earlier pack left: the planes are re-used when max_allele is unchanged, and a table of other bytes would skip rows that need their planes.
 static int mark_upper_plane_rows(fmh_matrix* m) {
   FMH_TRY(build_row_totals(m));
+  FMH_TRY(build_tiled_planes(m));
   const long long mode = options().row_hi.load();
   if ((!m->p1 && !m->pc) || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) {
     pool_free(m->device, m->row_hi);
@@ -1024,6 +1075,28 @@ ColumnWindow fmhi::sweep_window(const fmh_matrix* m, const fmh_groups* g, int mo
   return w;
 }
 
+// The tile-transposed image: a sweep of one or two groups over a packed biallelic matrix with nothing missing that holds
+// the image can read its window from there - whole KiB per tile instead of pieces of 128-byte lines per row.  FMH_TILED: 1 = wherever the route
+// is built, 0 = never, -1 = where it measured ahead of the row-major routes (tiled_route_default: a window of at most seven eighths of the row); never where the flat route is forced.  The
+// window itself is sweep_window's, whichever route reads it.
+static bool tiled_route_taken(const fmh_matrix* m, const fmh_groups* g, int mode) {
+  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
+  const long long want = options().tiled.load();
+  if (!(packed && m->p0t && !m->has_missing && m->max_allele <= 1 && !m->p1 && !m->pc && want != 0 && (mode & kModeWc) == 0 && g->padded <= 2 &&
+        g->n_groups == g->padded && tiled_route_builds(g->padded, mode) && !flat_route_taken(m, g, mode)))
+    return false;
+  return want > 0 || tiled_route_default(sweep_window(m, g, mode).count, m->pvec);
+}
+
+extern "C" int fmh_sweep_tiled(const fmh_matrix* m, const fmh_groups* g, int mode, int* tiled, size_t* image_bytes) {
+  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
+  if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
+    return fail(FMH_ERR_INVALID, "groups were built for a different matrix geometry");
+  if (tiled) *tiled = tiled_route_taken(m, g, mode) ? 1 : 0;
+  if (image_bytes) *image_bytes = m->p0t ? m->p0t_bytes : 0;
+  return FMH_OK;
+}
+
 extern "C" int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_t* first_vec, uint32_t* n_vec, int* derived_group) {
   if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
   if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
@@ -1084,7 +1157,14 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
   const bool windowed = packed && (win.first != 0 || win.count != m->pvec || win.derived >= 0);
   a.derived_group = -1;
   a.row_alt = nullptr;
-  if (windowed) {
+  const bool tiled = tiled_route_taken(m, g, mode);
+  if (tiled) {  // the image at the window's first vector: 1 KiB per vector and tile; the masks and the derived group as below
+    a.mv.data = m->p0t + (size_t)win.first * 1024;
+    a.mv.nvec = win.count;
+    a.mask_bits = g->mask_bits + (size_t)win.first * 8;
+    a.derived_group = win.derived;
+    a.row_alt = win.derived >= 0 ? m->row_alt : nullptr;
+  } else if (windowed) {
     a.mv.data = m->p0 + (size_t)win.first * 16;
     a.mv.nvec = win.count;
     a.mask_bits = g->mask_bits + (size_t)win.first * 8;  // one 16-bit word per 16 columns: eight per vector
@@ -1226,7 +1306,8 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
     return fail(FMH_ERR_UNSUPPORTED, "%d group masks of %u columns exceed the LDS budget: sweep at most two groups at a time on rows this wide", P, m->columns);
   const bool flat = mask_mode == kMaskPacked && !windowed && !mfma && flat_route_taken(m, g, mode);
   int rc;
-  if (flat) rc = launch_sweep_flat(P, mode, a, st, ctx, &grid);
+  if (tiled) rc = launch_sweep_tiled(P, mode, a, st, ctx, &grid);
+  else if (flat) rc = launch_sweep_flat(P, mode, a, st, ctx, &grid);
   else if (mfma) rc = launch_sweep_mfma(P, mode, a, smem, st, ctx, &grid);
   else if (mask_mode == kMaskPacked && general && m->p2)  // alleles 4..7: three planes
     rc = lpr == 4 ? launch_sweep_packed4_3p(P, mode, missing, general, a, smem, st, ctx, &grid) : launch_sweep_packed16_3p(P, mode, missing, general, a, smem, st, ctx, &grid);

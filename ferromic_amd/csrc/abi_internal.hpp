@@ -77,6 +77,10 @@ struct Options {
   std::atomic<long long> wc_bi_chunks{0};        // FMH_WC_BI_CHUNKS: row chunks of the biallelic pair kernel (measurement); 0 = about 8 192 workgroups
   std::atomic<long long> row_hi{1};              // FMH_ROW_HI: 0 = packed matrices get no tables of the rows with alleles above 1 / with uncalled columns (every plane of every row is read); 2 = tables at any size
   std::atomic<long long> column_window{1};       // FMH_COLUMN_WINDOW: 0 = every sweep reads every vector of a row and no row totals are kept; 1 = sweeps read the vectors their groups have members in, row totals for packed biallelic matrices of >= 4 096 rows with nothing missing; 2 = row totals at any size
+  std::atomic<long long> tiled_planes{1};        // FMH_TILED_PLANES: the tile-transposed image of plane 0 (fmh_matrix::p0t): 0 = never built; 1 (default) = packed biallelic matrices of >= 4 096 rows with nothing missing, while the image fits under FMH_TILED_BYTES and as much again stays free; 2 = at any size, no free-memory test
+  std::atomic<long long> tiled_bytes{(long long)16 << 30};  // FMH_TILED_BYTES: the largest image FMH_TILED_PLANES=1 builds
+  std::atomic<long long> tiled{-1};              // FMH_TILED: 0 = sweeps take the row-major routes even where the image exists (the A side of every A/B); 1 = the tiled route wherever it is built; -1 = where it measured ahead (tiled_route_default)
+  std::atomic<long long> tiled_batch{0};         // FMH_TILED_BATCH = 10 | 5 | 2: the half batch of the tiled sweep (measurements); 0 = by the window (sweep_tiled.hip)
   std::atomic<long long> pca_eigen{0};           // FMH_PCA_EIGEN = host | rocsolver: the PCA's symmetric eigen solver; 0 = rocSOLVER, the host solver when it cannot be loaded
   std::atomic<long long> pca_splits{0};          // FMH_PCA_SPLITS: K splits of the PCA Gram (1 = none); 0 = by the tile count
   std::atomic<long long> pca_budget_bytes{(long long)16 << 30};  // FMH_PCA_BUDGET_BYTES: device memory one fmh_pca_gram call may use (Gram + bit words + slabs)
@@ -219,6 +223,14 @@ constexpr int kFlatMaskMaxVec = 32;
 bool flat_route_builds(int P, int mode);
 inline bool flat_route_default(int P, int mode, uint32_t pvec) { (void)P; (void)mode; (void)pvec; return false; }  // until measured
 int launch_sweep_flat(int P, int mode, const fmh::SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int* grid);
+// the sweep over the tile-transposed image of plane 0 (sweep_tiled.hip): packed, biallelic, nothing missing, one or two groups, not W&C
+bool tiled_route_builds(int P, int mode);
+// The default rule (FMH_TILED=-1), by measurement (profiles/tiled_planes/): at equal bytes the tiled kernel is about 7 % behind
+// the four-lane ones (the whole row at 5 000 haplotypes), so it is taken where it reads clearly fewer: a window of at most seven eighths of the row.
+// Measured ahead at 20 and 9 of 40 vectors with a group derived (1.11-1.65x), 27 of 40 without (1.28-1.36x), 10 of 20 and 4 of 8 (1.08-1.58x);
+// measured behind at 39 and 40 of 40 (3-9 % at 2.5 M sites and more), which therefore keep the row-major routes.
+inline bool tiled_route_default(uint32_t window_vecs, uint32_t pvec) { return (uint64_t)window_vecs * 8 <= (uint64_t)pvec * 7; }
+int launch_sweep_tiled(int P, int mode, const fmh::SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int* grid);
 // counts on the int8 matrix cores (sweep_mfma.hip): u8 rows, biallelic, nothing missing, at most 4 (padded) groups
 int launch_sweep_mfma(int P, int mode, const fmh::SweepArgs& a, size_t smem, hipStream_t st, const LaunchCtx& ctx, int* grid);
 
@@ -241,6 +253,11 @@ struct fmh_matrix {
   uint8_t *p0 = nullptr, *p1 = nullptr, *p2 = nullptr, *pc = nullptr;
   uint8_t* row_gap = nullptr; // with pc: one byte per row, non-zero when some column of the row is not called (written wherever the planes are)
   uint32_t* row_alt = nullptr;  // biallelic with nothing missing: popcount of plane 0 over the row's columns (rebuilt or dropped wherever the planes are written)
+  // plane 0 tile-transposed: the 16 bytes of row r, vector v at byte (((r >> 6) * pvec + v) * 64 + (r & 63)) * 16, rows past
+  // `variants` in the last tile zero; biallelic with nothing missing only.  It DOUBLES the resident planes (6.4 GB at 10 M x 5 000); rebuilt or dropped
+  // wherever row_alt is.  A column window of a sweep is then whole KiB of every tile: no fetched line holds a byte the sweep does not need.
+  uint8_t* p0t = nullptr;
+  size_t p0t_bytes = 0;
   uint8_t* row_hi = nullptr;  // with p1: one byte per row, non-zero when the row has a bit in plane 1 or 2 (written wherever the planes are)
   size_t plane_pitch = 0;
   uint32_t pvec = 0;

@@ -220,6 +220,34 @@ __global__ __launch_bounds__(256) void row_alt_kernel(const uint8_t* __restrict_
   }
 }
 
+// plane 0 row-major -> tile-transposed (fmh_matrix::p0t): the 16 bytes of row r, vector v go to byte (((r >> 6) * pvec + v) * 64 + (r & 63)) * 16; rows
+// past the last one of the last tile are written as zero.  One workgroup per (64-row tile, kTileVecs vectors): 64 x 256 contiguous bytes in (sixteen
+// lanes per row), transposed through LDS (rows of 17 vectors: the column reads of a wave start in different banks), kTileVecs whole KiB out.
+constexpr uint32_t kTileVecs = 16;
+__global__ __launch_bounds__(256) void tile_planes_kernel(const uint8_t* __restrict__ p0, size_t plane_pitch, size_t rows, uint32_t pvec,
+                                                          uint8_t* __restrict__ p0t) {
+  __shared__ uint4 s[64 * (kTileVecs + 1)];
+  const uint32_t chunks = (pvec + kTileVecs - 1) / kTileVecs;
+  const size_t items = (rows + 63) / 64 * chunks;
+  for (size_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const size_t tile = it / chunks;
+    const uint32_t v0 = (uint32_t)(it - tile * chunks) * kTileVecs;
+#pragma unroll
+    for (uint32_t k = 0; k < 64 * kTileVecs / 256; ++k) {
+      const uint32_t i = threadIdx.x + 256 * k, r = i / kTileVecs, vv = i % kTileVecs;
+      const size_t row = tile * 64 + r;
+      s[r * (kTileVecs + 1) + vv] = row < rows && v0 + vv < pvec ? *reinterpret_cast<const uint4*>(p0 + row * plane_pitch + (size_t)(v0 + vv) * 16) : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 64 * kTileVecs / 256; ++k) {
+      const uint32_t j = threadIdx.x + 256 * k, vv = j / 64, r = j % 64;
+      if (v0 + vv < pvec) *reinterpret_cast<uint4*>(p0t + ((tile * pvec + v0 + vv) * 64 + r) * 16) = s[r * (kTileVecs + 1) + vv];
+    }
+    __syncthreads();
+  }
+}
+
 // row_hi[r] = 1 when row r of a packed multi-allelic matrix has a bit in plane 1 or plane 2 (a called allele above 1), else 0: the sweeps
 // read the upper planes of those rows only (MatrixView::row_hi).  Sixteen lanes per row, as many 16-byte vectors each as the row needs.
 __global__ __launch_bounds__(256) void row_hi_kernel(const uint8_t* __restrict__ p1, const uint8_t* __restrict__ p2, size_t plane_pitch, size_t rows,

@@ -210,6 +210,13 @@ def sweep_window(m: DeviceMatrix, g: Groups, mode: int):
     return first.value, count.value, derived.value
 
 
+def sweep_tiled(m: DeviceMatrix, g: Groups, mode: int):
+    """fmh_sweep_tiled: (whether the next sweep of `mode` reads the tile-transposed plane image, that image's bytes or 0)."""
+    tiled, image_bytes = C.c_int(), C.c_size_t()
+    _abi.check(_abi.load().fmh_sweep_tiled(m._h, g._h, mode, C.byref(tiled), C.byref(image_bytes)))
+    return bool(tiled.value), image_bytes.value
+
+
 def _pop_totals(t: _abi.PopTotals) -> Dict[str, float]:
     return dict(haplotype_capacity=int(t.haplotype_capacity), segregating_sites=int(t.segregating_sites),
                 uncallable_sites=int(t.uncallable_sites), pi_sum=float(t.pi_sum))

@@ -75,6 +75,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_PACKED_NO_PREFETCH   FMH_COUNTS_MFMA (1 | 2)   FMH_GRID_PER_CU   FMH_GRID_BLOCKS   FMH_MAX_OCC   FMH_UNROLL   FMH_PITCH_ALIGN
  *   FMH_COMM_TRANSPORT (host | rccl)   FMH_UPLOAD_THREADS   FMH_PD_TWO_PLANES   FMH_PD_INT8   FMH_PD_PLANES_BYTES   FMH_PD_KCHUNK
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
+ *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -192,6 +193,18 @@ int fmh_groups_sizes(const fmh_groups* g, int* n_groups, uint64_t* h_sizes /* [n
 #define FMH_SWEEP_REGION 7    /* fmh_pair_region_sweep */
 #define FMH_SWEEP_WC 8        /* fmh_wc_sweep */
 int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_t* first_vec, uint32_t* n_vec, int* derived_group);
+
+/* Host only: whether the next sweep of `mode` over these groups reads its window from the TILE-TRANSPOSED image of bit plane 0 (*tiled = 1) and
+ * the size of that image (*image_bytes, 0 when the matrix holds none).  The image stores the 16 bytes of row r, vector v at byte
+ * (((r >> 6) * vectors_per_row + v) * 64 + (r & 63)) * 16, so the 64 rows of a tile share the 128-byte lines of one vector column and a column
+ * window is read without a byte the sweep does not need.  It is built wherever the planes of a biallelic matrix with nothing missing are written,
+ * and it DOUBLES the resident planes of that matrix (6.4 GB at 10 M sites x 5 000 haplotypes).  FMH_TILED_PLANES: 0 = never built, 1 = default:
+ * matrices of at least 4 096 rows whose image fits under FMH_TILED_BYTES (default 16 GiB) and leaves as much again free on the device, 2 = at any
+ * size without the free-memory test; a negative FMH_TILED_BYTES is an error.  Without an image every sweep takes the row-major routes.  One or
+ * two groups, every sweep but W&C.  FMH_TILED: -1 = default: the tiled route where the window (fmh_sweep_window) is at most 7/8 of the row, 0 = the
+ * row-major routes with the image present, 1 = the tiled route wherever it is built.  Per-site results never depend on the route; regional f64
+ * sums are the same bits at equal grids and agree within 1e-9 otherwise (the routes differ in occupancy, hence in their default grids). */
+int fmh_sweep_tiled(const fmh_matrix* m, const fmh_groups* g, int mode, int* tiled, size_t* image_bytes);
 
 /* ---- per-population summary sweep ------------------------------------------------------------ */
 typedef struct {

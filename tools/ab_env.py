@@ -37,6 +37,9 @@ def main():
         if os.environ.get("AB_MASKS") == "interleaved":  # even samples | odd samples: no vector without members of both groups (the data keeps its two halves)
             even = (np.arange(H) // 2 % 2 == 0)
             masks = np.stack([even, ~even]).astype(np.uint8)
+        if os.environ.get("AB_MASKS", "").startswith("spans:"):  # spans:a-b,c-d = two groups of the columns [a, b) and [c, d) (the data keeps its two halves)
+            spans = [tuple(int(x) for x in sp.split("-")) for sp in os.environ["AB_MASKS"][6:].split(",")]
+            masks = np.stack([(np.arange(H) >= lo) & (np.arange(H) < hi) for lo, hi in spans]).astype(np.uint8)
         thr = bench.synthetic_thresholds(S, 0, S + N)
         missing = layout.endswith(":m")  # SITESxSAMPLES:packed:m = 1 % missing calls
         layout = layout.split(":")[0]

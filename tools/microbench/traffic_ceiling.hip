@@ -8,6 +8,8 @@
 // Modes: read only / read + tracks / tracks only.  The table goes to DESIGN.md section 3 as the ceiling the real kernels are held against.
 //   CEILING_WINDOW=first:count  reads only vectors [first, first + count) of every row (a column window of the sweep: DESIGN.md section 3.5b)
 //   plus one 4-byte row total per site, the tracks as above; the row pitch is unchanged, so the reads are `count * 16` bytes at a stride of `pitch`.
+//   CEILING_TILED=first:count   the same window of a tile-transposed image: the 64 rows of a tile share the lines of one vector
+//   column, so per tile the reads are `count` contiguous KiB out of every `pitch / 16` KiB, one coalesced 16-byte-per-lane load each; row totals and tracks as above.
 // Build: hipcc --offload-arch=gfx950 -O3 -o traffic_ceiling traffic_ceiling.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void ceiling_kernel(const uint8_t* __restrict_
 
 // A column window: of every row only vectors [V0, V0 + WV) are read (WV x 16 bytes at a stride of `pitch`), plus 4 bytes per row of a side table.
 // A tile's 64 x WV vectors are spread over the wave in row-major order, all in flight before the first is consumed.
-template <int WV, int DEFER>
+template <int WV, int DEFER, bool TILED = false>
 __global__ __launch_bounds__(256) void window_kernel(const uint8_t* __restrict__ data, size_t rows, size_t pitch, int v0, const uint32_t* __restrict__ row_total,
                                                      int n_f64, int n_u32, int n_u8, double* __restrict__ o64, uint32_t* __restrict__ o32, uint8_t* __restrict__ o8,
                                                      unsigned long long* __restrict__ sink) {
@@ -73,8 +75,12 @@ __global__ __launch_bounds__(256) void window_kernel(const uint8_t* __restrict__
       uint4 x[WV];
 #pragma unroll
       for (int c = 0; c < WV; ++c) {
-        const int idx = c * 64 + lane, r = idx / WV, v = idx - r * WV;
-        x[c] = *reinterpret_cast<const uint4*>(data + (tile * 64 + r) * pitch + (size_t)(v0 + v) * 16);
+        if (TILED) {
+          x[c] = *reinterpret_cast<const uint4*>(data + (tile * (pitch / 16) + (size_t)(v0 + c)) * 1024 + (size_t)lane * 16);
+        } else {
+          const int idx = c * 64 + lane, r = idx / WV, v = idx - r * WV;
+          x[c] = *reinterpret_cast<const uint4*>(data + (tile * 64 + r) * pitch + (size_t)(v0 + v) * 16);
+        }
       }
 #pragma unroll
       for (int c = 0; c < WV; ++c) acc += x[c].x ^ x[c].y ^ x[c].z ^ x[c].w;
@@ -93,7 +99,7 @@ __global__ __launch_bounds__(256) void window_kernel(const uint8_t* __restrict__
   if (acc == 0xFFFFFFFFu) sink[0] = acc;
 }
 
-template <int WV>
+template <int WV, bool TILED = false>
 void run_window(const uint8_t* data, size_t rows, size_t pitch, int v0, const uint32_t* row_total, int n_f64, int n_u32, int n_u8, double* o64, uint32_t* o32,
                 uint8_t* o8, unsigned long long* sink, int cus, int argc, char** argv) {
   hipEvent_t e0, e1;
@@ -107,18 +113,18 @@ void run_window(const uint8_t* data, size_t rows, size_t pitch, int v0, const ui
       float best = 1e9f;
       for (int rep = 0; rep < 30; ++rep) {
         CHECK(hipEventRecord(e0));
-        if (mode == 0) hipLaunchKernelGGL((window_kernel<WV, 1>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
-        if (mode == 1) hipLaunchKernelGGL((window_kernel<WV, 8>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
-        if (mode == 2) hipLaunchKernelGGL((window_kernel<WV, 16>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
+        if (mode == 0) hipLaunchKernelGGL((window_kernel<WV, 1, TILED>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
+        if (mode == 1) hipLaunchKernelGGL((window_kernel<WV, 8, TILED>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
+        if (mode == 2) hipLaunchKernelGGL((window_kernel<WV, 16, TILED>), dim3(grid), dim3(256), 0, 0, data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink);
         CHECK(hipEventRecord(e1));
         CHECK(hipEventSynchronize(e1));
         float ms;
         CHECK(hipEventElapsedTime(&ms, e0, e1));
         if (rep >= 10 && ms < best) best = ms;
       }
-      printf("{\"mode\": \"window+total+tracks defer %d\", \"rows\": %zu, \"pitch\": %zu, \"first_vec\": %d, \"n_vec\": %d, \"f64_tracks\": %d, \"u32_tracks\": %d, "
+      printf("{\"mode\": \"%s+total+tracks defer %d\", \"rows\": %zu, \"pitch\": %zu, \"first_vec\": %d, \"n_vec\": %d, \"f64_tracks\": %d, \"u32_tracks\": %d, "
              "\"u8_tracks\": %d, \"workgroups_per_cu\": %d, \"best_ms\": %.4f, \"GBs\": %.0f, \"frac_of_8TBs\": %.3f}\n",
-             mode == 0 ? 1 : mode == 1 ? 8 : 16, rows, pitch, v0, WV, n_f64, n_u32, n_u8, per_cu, best, bytes / best / 1e6, bytes / best / 1e6 / 8000.0);
+             TILED ? "tiled window" : "window", mode == 0 ? 1 : mode == 1 ? 8 : 16, rows, pitch, v0, WV, n_f64, n_u32, n_u8, per_cu, best, bytes / best / 1e6, bytes / best / 1e6 / 8000.0);
       fflush(stdout);
     }
   }
@@ -231,13 +237,15 @@ int main(int argc, char** argv) {
   hipDeviceProp_t prop;
   CHECK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount;
-  if (const char* w = getenv("CEILING_WINDOW")) {
+  const char* tiled = getenv("CEILING_TILED");
+  if (const char* w = tiled ? tiled : getenv("CEILING_WINDOW")) {
     int v0 = 0, wv = 0;
-    if (sscanf(w, "%d:%d", &v0, &wv) != 2 || v0 < 0 || wv < 1 || (size_t)(v0 + wv) * 16 > pitch) { printf("CEILING_WINDOW=first:count must lie inside the row\n"); return 1; }
+    if (sscanf(w, "%d:%d", &v0, &wv) != 2 || v0 < 0 || wv < 1 || (size_t)(v0 + wv) * 16 > pitch) { printf("CEILING_WINDOW / CEILING_TILED=first:count must lie inside the row\n"); return 1; }
     uint32_t* row_total;
     CHECK(hipMalloc(&row_total, rows * 4));
     CHECK(hipMemset(row_total, 0, rows * 4));
-#define RUNW(WV) run_window<WV>(data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink, cus, argc, argv)
+#define RUNW(WV) (tiled ? run_window<WV, true>(data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink, cus, argc, argv) \
+                       : run_window<WV>(data, rows, pitch, v0, row_total, n_f64, n_u32, n_u8, o64, o32, o8, sink, cus, argc, argv))
     if (wv == 20) RUNW(20);
     else if (wv == 24) RUNW(24);
     else if (wv == 16) RUNW(16);
