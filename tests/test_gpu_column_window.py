@@ -7,7 +7,10 @@ bit, regional f64 sums to 1e-9; the same sweeps with FMH_COLUMN_WINDOW=0 are a s
 asks fmh_sweep_window what the sweep reads and which group it derives, so that a case which silently fell back does not count.
 
 All cases: 64 * 70 + 37 rows, FMH_COLUMN_WINDOW=2 (row totals at any size), FMH_GRID_BLOCKS=1 (each wave walks about 18 tiles: one full
-16-deep deferral chunk and a partial one), and a second sweep over rows [13, 13 + 3 000)."""
+16-deep deferral chunk and a partial one), and a second sweep over rows [13, 13 + 3 000).
+
+These are hand-picked layouts; tests/test_gpu_window_geometry.py covers every window width 1 .. 64, first vectors on both ends and inside, row
+ranges around tile edges and other grids with the helpers of this file."""
 
 import ctypes as C
 import functools

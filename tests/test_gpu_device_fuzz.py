@@ -147,6 +147,158 @@ def test_random_geometry_hudson_and_diversity(dev, seed):
     close(dv.theta, theta, "site theta")
 
 
+WINDOW_CASES = max(1, CASES * 2 // 3)  # 40 at the default 60
+WINDOW_SHAPES = ("cut", "sandwich", "scattered", "pieces", "interval")
+
+
+def draw_window_geometry(seed):
+    """What a seed of test_random_geometry_windows_and_derived_groups draws before its data: the generator, the matrix geometry, the shape
+    of the membership (seed mod 5 - every shape meets both routes, seed mod 2), the grid and the membership itself."""
+    rng = np.random.default_rng(31000 + seed)
+    N = int(rng.choice([w for w in WIDTHS if w >= 64] + [4095, 6000]))
+    S = int(rng.choice(ROWS))
+    ploidy = int(rng.choice([1, 2, 2, 3]))
+    H = N * ploidy
+    grid = [None, 1, 2][int(rng.integers(0, 3))]
+    shape = WINDOW_SHAPES[seed % 5]
+    tiled = seed % 2 == 1
+    span = lambda lo, hi: ((np.arange(H) >= lo) & (np.arange(H) < hi)).astype(np.uint8)
+    if shape == "cut":  # two groups partition the columns at one cut
+        cut = int(rng.integers(1, H))
+        masks = np.stack([span(0, cut), span(cut, H)])
+    elif shape == "sandwich":  # a contiguous group and everything else
+        lo = int(rng.integers(0, H - 1))
+        hi = int(rng.integers(lo + 1, H + (1 if lo > 0 else 0)))
+        masks = np.stack([span(lo, hi), 1 - span(lo, hi)])
+    elif shape == "scattered":  # a partition with nothing to skip
+        one = (rng.random(H) < rng.choice([0.1, 0.5, 0.9])).astype(np.uint8)
+        one[0], one[-1] = 0, 1
+        masks = np.stack([1 - one, one])
+    elif shape == "pieces":  # two disjoint random pieces that leave columns out
+        p = np.sort(rng.choice(np.arange(1, H), size=3, replace=False))
+        keep = (rng.random(H) < rng.choice([0.3, 0.6, 1.0])).astype(np.uint8)
+        keep[p[0]] = keep[p[1]] = keep[p[2] - 1] = 1
+        masks = np.stack([keep * span(p[0], p[1]), keep * span(p[1] if rng.random() < 0.5 else (p[1] + p[2]) // 2, p[2])])
+    else:  # one group of a column interval
+        lo = int(rng.integers(0, H))
+        masks = span(lo, int(rng.integers(lo + 1, H + 1)))[None, :]
+    if masks.shape[0] == 2 and seed // 5 % 2:  # either order of every shape, so that both groups get derived
+        masks = masks[::-1].copy()
+    assert all(m.any() for m in masks)
+    return rng, N, S, ploidy, grid, shape, tiled, masks
+
+
+def test_random_geometry_windows_draws():
+    """The draws of test_random_geometry_windows_and_derived_groups, replayed without a device: each of the five membership shapes and both
+    routes occur at least five times (at the default case count), partitions do derive a group and pieces do leave columns out."""
+    from tests.test_gpu_column_window import expected_window
+
+    draws = [draw_window_geometry(seed) for seed in range(WINDOW_CASES)]
+    need = min(5, WINDOW_CASES // 8)
+    for shape in WINDOW_SHAPES:
+        assert sum(d[5] == shape for d in draws) >= need, shape
+    for tiled in (False, True):
+        assert sum(d[6] == tiled for d in draws) >= need, tiled
+    for grid in (None, 1, 2):
+        assert sum(d[4] == grid for d in draws) >= min(need, 3), grid
+    derived = [expected_window(d[7], True)[2] for d in draws]
+    if WINDOW_CASES >= 40:
+        assert sum(x == 0 for x in derived) >= 5 and sum(x == 1 for x in derived) >= 5 and sum(x < 0 for x in derived) >= 5
+    for d in draws:
+        if d[5] in ("cut", "sandwich", "scattered"):
+            assert (d[7].sum(axis=0) == 1).all()
+        elif d[5] == "pieces":
+            assert (d[7].sum(axis=0) <= 1).all() and (d[7].sum(axis=0) == 0).any()
+
+
+@pytest.mark.parametrize("seed", range(WINDOW_CASES))
+def test_random_geometry_windows_and_derived_groups(dev, fmh_opts, seed):
+    """Random biallelic cohorts with nothing missing under FMH_COLUMN_WINDOW=2 and FMH_TILED_PLANES=2 - the row totals and the plane image at
+    any size - on the tiled route (odd seeds) and the row-major one (even seeds): memberships that partition the columns (a group is derived),
+    leave columns out (the hull is read) or are a single interval, a random row range, a random grid.  Counts against numpy, per-site pi, theta
+    and D_xy against the formulas in numpy float64, per-site bits against the same sweeps without window or image, and the window the library
+    reports against the rule."""
+    from tests.test_gpu_column_window import expected_window
+
+    rng, N, S, ploidy, grid, shape, tiled, masks = draw_window_geometry(seed)
+    H = N * ploidy
+    G = masks.shape[0]
+    fmh_opts.setenv("FMH_COLUMN_WINDOW", "2")
+    fmh_opts.setenv("FMH_TILED_PLANES", "2")
+    fmh_opts.setenv("FMH_TILED", "1" if tiled else "0")
+    if grid is not None:
+        fmh_opts.setenv("FMH_GRID_BLOCKS", str(grid))
+    data = (rng.random((S, H)) < rng.beta(0.8, 0.8, size=(S, 1))).astype(np.uint8)
+    data[0, 0] = 1
+    dm = dev.DeviceMatrix.from_host(data.reshape(-1), None, S, N, ploidy, 1)
+    r0, r1 = (0, S) if seed % 3 else (int(rng.integers(0, S)), int(rng.integers(0, S)) + 1)
+    r0, r1 = min(r0, r1 - 1) if r1 > 0 else 0, max(r1, r0 + 1)
+    r1 = min(r1, S)
+    rows = r1 - r0
+    alt = np.stack([data[r0:r1][:, m != 0].sum(axis=1) for m in masks]).astype(np.float64)  # [G][rows]
+    n = np.repeat(masks.sum(axis=1).astype(np.float64)[:, None], rows, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        freq = np.stack([(n - alt) / n, alt / n])
+        pi = np.where(n >= 2, n / (n - 1.0) * (1.0 - (freq ** 2).sum(axis=0)), np.nan)
+        dxy = np.where((n[0] > 0) & (n[-1] > 0), np.clip(1.0 - (freq[:, 0] * freq[:, -1]).sum(axis=0), 0.0, 1.0), np.nan)
+    distinct = (alt > 0).astype(int) + (alt < n).astype(int)
+    harmonic = np.concatenate([[0.0], np.cumsum(1.0 / np.arange(1, H + 2))])
+    theta = np.where(n[0] >= 2, np.where(distinct[0] >= 2, 1.0 / harmonic[np.maximum(n[0].astype(int) - 1, 1)], 0.0), np.nan)
+
+    def close(got, exp, what):
+        assert np.array_equal(np.isnan(got), np.isnan(exp)), what
+        ok = ~np.isnan(exp)
+        assert np.allclose(got[ok], exp[ok], rtol=1e-12, atol=1e-13), what
+
+    def same(a, b, what):
+        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), what
+
+    g, g1 = dev.Groups(dm, masks), dev.Groups(dm, masks[:1])
+
+    def sweeps():
+        out = {"ps": dev.population_summaries(dm, g, dev.FORMULA_DENSE, r0, rows), "dv": dev.diversity_sites(dm, g1, r0, rows)}
+        if G == 2:
+            out["hs"] = dev.hudson_sweep(dm, g, dev.FORMULA_DENSE, r0, rows)
+        return out
+
+    whole = (0, (H + 127) // 128, -1)
+    image = (S + 63) // 64 * ((H + 127) // 128) * 1024
+    for mode in (dev.SWEEP_SUMMARY,) + ((dev.SWEEP_HUDSON,) if G == 2 else ()):
+        assert dev.sweep_window(dm, g, mode) == expected_window(masks, True), (shape, mode)
+        assert dev.sweep_tiled(dm, g, mode) == (tiled, image), (shape, mode)
+    assert dev.sweep_window(dm, g1, dev.SWEEP_DIVERSITY) == expected_window(masks[:1], True), shape
+    assert dev.sweep_tiled(dm, g1, dev.SWEEP_DIVERSITY) == (tiled, image), shape
+    got = sweeps()
+    assert np.array_equal(got["ps"].called, n.astype(np.uint32)) and np.array_equal(got["ps"].alt, alt.astype(np.uint32)), shape
+    for p in range(G):
+        assert got["ps"].totals[p]["segregating_sites"] == int((distinct[p] >= 2).sum())
+        assert got["ps"].totals[p]["uncallable_sites"] == int((n[p] < 2).sum())
+        assert got["ps"].totals[p]["haplotype_capacity"] == int(masks[p].sum())
+    dv = got["dv"]
+    assert np.array_equal(dv.called, n[0].astype(np.uint32)) and np.array_equal(dv.distinct, distinct[0].astype(np.uint32)), shape
+    close(dv.pi, pi[0], "site pi")
+    close(dv.theta, theta, "site theta")
+    if G == 2:
+        hs = got["hs"]
+        assert np.array_equal(hs.sites["called"], n.astype(np.uint32)) and np.array_equal(hs.sites["alt"], alt.astype(np.uint32)), shape
+        close(hs.sites["dxy"], dxy, "dxy")
+        close(hs.sites["pi1"], pi[0], "pi1")
+        close(hs.sites["pi2"], pi[1], "pi2")
+        for p in range(2):
+            assert hs.pop[p]["segregating_sites"] == int((distinct[p] >= 2).sum())
+    fmh_opts.setenv("FMH_COLUMN_WINDOW", "0")
+    fmh_opts.setenv("FMH_TILED", "0")
+    assert dev.sweep_window(dm, g, dev.SWEEP_SUMMARY) == whole and dev.sweep_tiled(dm, g, dev.SWEEP_SUMMARY) == (False, image)
+    ref = sweeps()
+    assert np.array_equal(got["ps"].alt, ref["ps"].alt) and np.array_equal(dv.distinct, ref["dv"].distinct), shape
+    same(dv.pi, ref["dv"].pi, "site pi bits")
+    same(dv.theta, ref["dv"].theta, "site theta bits")
+    if G == 2:
+        assert np.array_equal(hs.sites["alt"], ref["hs"].sites["alt"]), shape
+        for k in ("fst", "dxy", "pi1", "pi2", "num", "den"):
+            same(hs.sites[k], ref["hs"].sites[k], f"{k} bits")
+
+
 @pytest.mark.parametrize("N,S,max_allele,p_missing", [(600, 300, 1, 0.0), (513, 257, 3, 0.05), (300, 1000, 2, 0.0), (257, 129, 1, 0.2), (300, 200, 6, 0.03), (130, 700, 5, 0.0)])
 def test_pairwise_gram_multi_tile(dev, N, S, max_allele, p_missing):
     """fmh_pairwise_differences across several 256-sample tiles (diagonal and off-diagonal tile pairs, K slices, ragged edges)

@@ -9,7 +9,10 @@ sweep takes the tiled route, so a case that silently fell back does not count.
 
 All cases: 64 * 70 + 37 rows, FMH_TILED_PLANES=2 (the image at any size), FMH_TILED=1 (the route wherever it is built: by
 default only a window of at most seven eighths of the row takes it), FMH_COLUMN_WINDOW=2, FMH_GRID_BLOCKS=1, and a second sweep over
-rows [13, 13 + 3 000), whose 64-row tiles straddle two image tiles each."""
+rows [13, 13 + 3 000), whose 64-row tiles straddle two image tiles each.
+
+These are hand-picked layouts; tests/test_gpu_window_geometry.py covers every window width 1 .. 64, every FMH_TILED_BATCH, first vectors on both
+ends and inside, row ranges that start and end around image-tile edges and grids of 1, 3 and 7 workgroups on this route."""
 
 import ctypes as C
 import struct
