@@ -104,6 +104,7 @@ def test_gram_entry_by_entry(dev, fmh_opts, n, m, layout, splits):
 
 
 def test_scan_sites_flags_and_counts(dev, fmh_opts):
+    """(The per-row tables, rows wider than 4 096 columns, every upload route and row ranges: tests/test_gpu_pca_scan.py.)"""
     rng = np.random.default_rng(5)
     rows, n = 300, 70
     x = binary_rows(rng, rows, n)

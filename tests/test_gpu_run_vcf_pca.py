@@ -176,3 +176,34 @@ def test_sharded_when_the_first_slab_keeps_no_site(tmp_path):
     kept, _ = R.site_filter(diploid_entries(variants, samples), variant_rule=True)
     assert kept.size > 100 and kept.min() >= ((len(variants) + 63) // 64 // 3) * 64, (kept.min(), third)  # no kept site in slab 0
     check_file(tmp_path / "run" / "pca_per_chr_outputs" / "pca_chr_1.tsv", names, variants, 4, "first slab without kept sites")
+
+
+def test_chromosome_above_the_row_table_threshold(tmp_path):
+    """4 500 variants, of which more than 4 096 are PASS: the chromosome's matrix is uploaded with its per-row tables (row_gap / row_hi,
+    built from 4 096 rows up), so the site scan skips the called plane of complete rows and the upper plane of biallelic ones - what every
+    real chromosome does.  `./.` cells are rare here (a site with one is not PASS); the uncalled entries of the PCA matrix are the second
+    alleles of haploid cells.  FMH_ROW_HI=0 (no tables) must write the same bytes."""
+    samples = 40
+    names = [f"POP{i % 3}_S{i:03d}" for i in range(samples)]
+    g, miss, hap, low = structured_genotypes(4500, samples, 91, populations=3, missing=0.0005)
+    kw = write_structured_case(tmp_path, {"1": (g, miss, hap, low)}, names, seed=11)
+    variants, sample_names = oracle_pass_variants(kw)["1"]
+    assert sample_names == names
+    # not vacuous, on the oracle's parse alone: enough PASS rows for the tables, rows the filter must refuse, mostly clean rows
+    entries = diploid_entries(variants, samples).reshape(len(variants), -1)
+    uncalled, high = (entries < 0).any(axis=1), (entries > 1).any(axis=1)
+    assert 4096 <= len(variants) < 4500 and miss.any()
+    assert uncalled.sum() >= 50 and high.sum() >= 150 and (uncalled & high).sum() >= 1 and (~(uncalled | high)).sum() * 2 > len(variants)
+    freq = np.clip(entries[uncalled | high], 0, 1).sum(axis=1) / (2.0 * samples)
+    assert (np.minimum(freq, 1.0 - freq) >= 0.1).sum() >= 50  # refused for their flag alone: a flag the scan missed would keep them
+    args = ["--pca", "--pca_components", "4"]
+    stderr, _ = run(kw, tmp_path / "tables", args)
+    path = tmp_path / "tables" / "pca_per_chr_outputs" / "pca_chr_1.tsv"
+    complete, kept, total = check_file(path, names, variants, 4, "chr1, 4 500 variants")
+    assert total == len(variants) and complete < total
+    assert f"Found {complete} variants with complete data out of {total} total variants" in stderr
+    assert f"Keeping {kept}/{complete} variants with MAF >= 5% for PCA" in stderr
+    assert "PCA error" not in stderr
+    stderr0, _ = run(kw, tmp_path / "no_tables", args, env={"FMH_ROW_HI": "0"})
+    assert f"Keeping {kept}/{complete} variants with MAF >= 5% for PCA" in stderr0
+    assert (tmp_path / "no_tables" / "pca_per_chr_outputs" / "pca_chr_1.tsv").read_bytes() == path.read_bytes()
