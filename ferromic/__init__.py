@@ -15,8 +15,10 @@ from ._core import (  # noqa: E402,F401
     HudsonDxyResult,
     HudsonFstResult,
     HudsonFstSite,
+    JointSiteFrequencySpectrum,
     PairwiseDifference,
     Population,
+    SiteFrequencySpectrum,
     WcFstResult,
     WcFstSite,
     adjusted_sequence_length,
@@ -28,6 +30,7 @@ from ._core import (  # noqa: E402,F401
     hudson_fst_sites,
     hudson_fst_with_sites,
     inversion_allele_frequency,
+    joint_site_frequency_spectrum,
     ld_prune,
     ld_r2,
     nucleotide_diversity,
@@ -35,6 +38,7 @@ from ._core import (  # noqa: E402,F401
     per_chromosome_pca,
     per_site_diversity,
     segregating_sites,
+    site_frequency_spectrum,
     watterson_theta,
     wc_fst,
     wc_fst_components,

@@ -95,6 +95,22 @@ class LdBandOut(C.Structure):
     _fields_ = [("r2", C.c_void_p), ("n_ab", C.c_void_p), ("n_joint", C.c_void_p), ("over", C.c_void_p)]
 
 
+class SfsSkipped(C.Structure):
+    _fields_ = [("multiallelic", C.c_uint64), ("incomplete", C.c_uint64)]
+
+
+class SfsStatsOut(C.Structure):
+    _fields_ = [
+        ("sites", C.c_uint64),
+        ("segregating_sites", C.c_uint64),
+        ("pi_sum", C.c_double),
+        ("theta_w_sum", C.c_double),
+        ("theta_h_sum", C.c_double),
+        ("tajima_d", C.c_double),
+        ("fay_wu_h", C.c_double),
+    ]
+
+
 class WcTotals(C.Structure):
     _fields_ = [
         ("sum_a", C.c_double * (1 + MAX_PAIRS)),
@@ -153,6 +169,9 @@ SYMBOLS = {
     "fmh_ld_prune": (_i, [_vp, _vp, _sz, _sz, _sz, _d, _vp, _vp]),
     "fmh_ld_prune_chunked": (_i, [_vp, _vp, _sz, _sz, _sz, _d, _vp, _sz, _vp]),
     "fmh_ld_prune_bits": (_i, [_vp, _sz, _sz, _vp]),
+    "fmh_sfs": (_i, [_vp, _vp, _vp, _sz, _vp, _P(SfsSkipped), _vp]),
+    "fmh_sfs_joint": (_i, [_vp, _vp, _sz, _sz, _vp, _P(SfsSkipped), _vp]),
+    "fmh_sfs_stats": (_i, [_vp, _sz, _P(SfsStatsOut)]),
     "fmh_hudson_totals_pack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_hudson_totals_unpack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_pop_totals_pack": (_i, [_P(PopTotals), _i, _P(_d), _P(_u64)]),

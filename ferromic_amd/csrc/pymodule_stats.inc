@@ -906,6 +906,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 }
 
 #include "pymodule_ld.inc"
+#include "pymodule_sfs.inc"
 
 }  // namespace
 
@@ -1023,6 +1024,7 @@ PYBIND11_MODULE(_core, m) {
       .def("nucleotide_diversity", [](const Population& self) { return calculate_pi_for_population(self); })
       .def("ld_r2", &population_ld_r2, py::arg("max_sites_apart"))
       .def("ld_prune", &population_ld_prune, py::arg("window_sites"), py::arg("r2_threshold"))
+      .def("site_frequency_spectrum", &population_sfs, py::arg("windows") = py::none())
       .def_property_readonly("id", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::int_(p.id.group)) : py::object(py::str(p.id.name)); })
       .def_property_readonly("haplotype_group", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::int_(p.id.group)) : py::object(py::none()); })
       .def_property_readonly("label", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::none()) : py::object(py::str(p.id.name)); })
@@ -1042,6 +1044,7 @@ PYBIND11_MODULE(_core, m) {
   m.def("pairwise_differences", &pairwise_differences, py::arg("variants"), py::arg("sample_count"), py::arg("sequence_length"));
   m.def("per_site_diversity", &per_site_diversity, py::arg("variants"), py::arg("haplotypes"), py::arg("region") = py::none());
   bind_ld(m);
+  bind_sfs(m);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

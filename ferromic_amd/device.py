@@ -499,3 +499,59 @@ def ld_prune_bits(over: np.ndarray, band: int) -> np.ndarray:
     keep = np.zeros(rows, dtype=np.uint8)
     _abi.check(_abi.load().fmh_ld_prune_bits(_ptr(over), rows, int(band), _ptr(keep)))
     return keep.astype(bool)
+
+
+# ---- site frequency spectra --------------------------------------------------------------------------------------------------------
+SFS_DEFAULT_ITEM_ROWS = 4096         # FMH_SFS_ITEM_ROWS unset
+SFS_DEFAULT_LDS_BINS = 5120 - 4      # FMH_SFS_LDS_BINS unset: an eighth of a CU's 160 KiB in u32 bins less the kernel's 16-byte head
+SFS_MAX_LDS_BINS = 40960 - 4         # the largest cap the option takes: the whole 160 KiB, one 512-thread workgroup per CU
+
+
+@dataclass
+class SfsResult:
+    counts: np.ndarray         # [n_windows][n + 1] uint64
+    multiallelic: np.ndarray   # [n_windows] uint64
+    incomplete: np.ndarray
+
+
+@dataclass
+class SfsJointResult:
+    counts: np.ndarray         # [n0 + 1][n1 + 1] uint64
+    multiallelic: int
+    incomplete: int
+
+
+def _skipped_arrays(skipped, count: int):
+    flat = np.ctypeslib.as_array(skipped).view(np.uint64).reshape(count, 2) if count else np.zeros((0, 2), dtype=np.uint64)
+    return flat[:, 0].copy(), flat[:, 1].copy()
+
+
+def sfs(m: DeviceMatrix, g: Groups, windows=None) -> SfsResult:
+    """fmh_sfs: the 1-D spectra of the one group of `g` over row windows [(begin, end), ...] (default: one window, every row)."""
+    w = np.array([[0, m.variants]] if windows is None else windows, dtype=np.uint64).reshape(-1, 2)
+    n_windows, width = w.shape[0], g.sizes[0] + 1
+    skipped = (_abi.SfsSkipped * max(n_windows, 1))()
+    d_sfs = DeviceBuffer(m.device, max(8 * n_windows * width, 8))
+    _abi.check(_abi.load().fmh_sfs(m._h, g._h, _ptr(w), n_windows, d_sfs.ptr, skipped, None))
+    multi, incomplete = _skipped_arrays(skipped, n_windows)
+    return SfsResult(d_sfs.to_numpy(np.uint64, n_windows * width).reshape(n_windows, width), multi, incomplete)
+
+
+def sfs_joint(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None) -> SfsJointResult:
+    """fmh_sfs_joint: the joint spectrum [n0 + 1][n1 + 1] of the two groups of `g` over rows [row_begin, row_begin + row_count)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    shape = (g.sizes[0] + 1, g.sizes[1] + 1) if g.n_groups == 2 else (1, 1)
+    skipped = (_abi.SfsSkipped * 1)()
+    d_sfs = DeviceBuffer(m.device, 8 * shape[0] * shape[1])
+    _abi.check(_abi.load().fmh_sfs_joint(m._h, g._h, row_begin, rows, d_sfs.ptr, skipped, None))
+    return SfsJointResult(d_sfs.to_numpy(np.uint64, shape[0] * shape[1]).reshape(shape), int(skipped[0].multiallelic), int(skipped[0].incomplete))
+
+
+def sfs_stats(counts) -> Dict[str, float]:
+    """fmh_sfs_stats (host only): the statistics of one 1-D spectrum of n + 1 bins."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    if counts.size < 1:
+        raise ValueError("a spectrum has at least one bin")
+    out = _abi.SfsStatsOut()
+    _abi.check(_abi.load().fmh_sfs_stats(_ptr(counts), counts.size - 1, C.byref(out)))
+    return {name: getattr(out, name) for name, _ in _abi.SfsStatsOut._fields_}

@@ -76,6 +76,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_COMM_TRANSPORT (host | rccl)   FMH_UPLOAD_THREADS   FMH_PD_TWO_PLANES   FMH_PD_INT8   FMH_PD_PLANES_BYTES   FMH_PD_KCHUNK
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
+ *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -462,6 +463,54 @@ int fmh_ld_prune_chunked(const fmh_matrix* m, const fmh_groups* g_or_null, size_
                          double threshold, uint8_t* h_keep /* [row_count] */, size_t chunk_rows /* 0 = by the scratch bound */,
                          void* stream);
 int fmh_ld_prune_bits(const uint32_t* h_over, size_t row_count, size_t band, uint8_t* h_keep);   /* host only, no device */
+
+/* ---- site frequency spectra (an addition: the reference has none) ------------------------------------------------------------
+ * Counted from the bit-packed image.  A group is a 0/1 column mask with n >= 1 members (fmh_groups).  A row is handled against a group in
+ * this order of precedence:
+ *   1. multiallelic: some member is called and carries an allele above 1 - not binned, tallied in `multiallelic`;
+ *   2. incomplete:   some member is not called - not binned, tallied in `incomplete`;
+ *   3. usable:       binned at k = the number of members whose allele is 1, 0 <= k <= n.
+ * Bits of the allele planes under uncalled entries are undefined (fmh_matrix_create_packed accepts junk there): every plane is masked with
+ * the called plane.  Monomorphic rows land in bins 0 and n.  For every window  sum(bins) + multiallelic + incomplete == rows of the window.
+ * Joint spectrum of groups 0 and 1 (they may overlap and differ in size): a row is multiallelic if it is so for either group, otherwise
+ * incomplete if it is so for either group, otherwise binned at [k0][k1].  Rows with missing calls are NOT projected down to a smaller
+ * sample size; the tallies say how much was left out.
+ * Results are integers (u64) and never depend on a route, an option, the grid or the order in which anything ran.
+ *
+ * fmh_sfs: the 1-D spectra of ONE group over n_windows row ranges [h_windows[2w], h_windows[2w+1]) of the matrix.  Ranges may overlap, be
+ *   empty and come in any order; begin <= end <= variants.  d_sfs is [n_windows][n+1] u64 on the matrix's device, zero-filled by the call;
+ *   h_skipped [n_windows] or NULL.
+ * fmh_sfs_joint: the joint spectrum of EXACTLY two groups over rows [row_begin, row_begin + row_count): d_sfs [n0+1][n1+1] u64,
+ *   zero-filled by the call; h_skipped one entry or NULL.
+ * Both enqueue on `stream` and synchronise it.  row_count == 0, or all windows empty, is FMH_OK with a zeroed table.
+ * Refusals, before any device work, in this order: a NULL matrix, groups, table or windows pointer; a wrong group count (1 / 2); groups
+ * that were not made for this matrix; a group with no member; a window outside the matrix or with begin > end; n_windows == 0 - all
+ * FMH_ERR_INVALID; a table of more than 2^28 bins, and a matrix without the packed image (call fmh_matrix_pack first) - FMH_ERR_UNSUPPORTED.
+ * Options: FMH_SFS_ITEM_ROWS = rows per work item (default 4 096), FMH_SFS_LDS_BINS = cap on the on-chip tile in bins (default 5 116: an
+ * eighth of the device's 160 KiB per CU, eight workgroups resident; at most 40 956: all of it, eight waves resident); neither changes a result.
+ *
+ * fmh_sfs_stats (host only, no device): the statistics of one 1-D spectrum of sample size n (h_sfs has n + 1 entries), S = the sum of
+ * bins 1..n-1:
+ *   pi_sum = sum_k sfs[k] 2 k (n-k) / (n (n-1))     theta_w_sum = S / a1     theta_h_sum = sum_{0<k<n} sfs[k] 2 k^2 / (n (n-1))
+ *   a1 = sum_{i<n} 1/i   a2 = sum_{i<n} 1/i^2   b1 = (n+1) / (3 (n-1))   b2 = 2 (n^2+n+3) / (9 n (n-1))
+ *   c1 = b1 - 1/a1   c2 = b2 - (n+2) / (a1 n) + a2 / a1^2   e1 = c1 / a1   e2 = c2 / (a1^2 + a2)
+ *   tajima_d = (pi_sum - S/a1) / sqrt(e1 S + e2 S (S-1)),  NaN when S == 0 or n < 4 (at n = 2 and 3 the variance is zero on paper and
+ *   rounding noise in f64);  fay_wu_h = pi_sum - theta_h_sum (unnormalised).  n < 2: every f64 field is NaN.  No sum is divided by a
+ *   sequence length.
+ */
+typedef struct { uint64_t multiallelic, incomplete; } fmh_sfs_skipped;
+
+int fmh_sfs(const fmh_matrix* m, const fmh_groups* g /* exactly 1 group */, const uint64_t* h_windows /* [n_windows][2] */, size_t n_windows,
+            uint64_t* d_sfs /* [n_windows][n+1] */, fmh_sfs_skipped* h_skipped_or_null /* [n_windows] */, void* stream);
+int fmh_sfs_joint(const fmh_matrix* m, const fmh_groups* g /* exactly 2 groups */, size_t row_begin, size_t row_count,
+                  uint64_t* d_sfs /* [n0+1][n1+1] */, fmh_sfs_skipped* h_skipped_or_null, void* stream);
+
+typedef struct {
+  uint64_t sites, segregating_sites;          /* sum of all bins; sum of bins 1..n-1 */
+  double pi_sum, theta_w_sum, theta_h_sum;    /* not divided by any sequence length */
+  double tajima_d, fay_wu_h;                  /* fay_wu_h = pi_sum - theta_h_sum (unnormalised) */
+} fmh_sfs_stats_out;
+int fmh_sfs_stats(const uint64_t* h_sfs, size_t n, fmh_sfs_stats_out* h_out);   /* host only, no device */
 
 /* ---- multi-GPU: region sharding + RCCL reduce of the regional accumulators -------------------------------- */
 /*
