@@ -1,7 +1,8 @@
-// abi.hip — implementation of include/ferromic_hip.h: device memory, layout conversion, kernel
-// dispatch and totals collection.  No CPU compute path exists here: without a GPU every entry
-// point fails with FMH_ERR_NO_DEVICE.  The sweep kernels are instantiated in sweep_*.hip (one object per mask route),
-// the pairwise-differences path lives in pairwise.hip, the RCCL communicator in comm.hip.
+// abi.hip — implementation of include/ferromic_hip.h: options, device memory, matrix and group handles, layout conversion, the
+// per-device workspace, timing and the statistic entry points with their totals collection.  No CPU compute path exists here: without
+// a GPU every entry point fails with FMH_ERR_NO_DEVICE.  How a sweep reaches its kernel is sweep_plan.hpp (the decision) and
+// sweep_dispatch.hip (enqueue_sweep, run_sweep); the sweep kernels are instantiated in sweep_*.hip (one object per mask route), the
+// pairwise-differences path lives in pairwise.hip, the RCCL communicator in comm.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -18,7 +19,7 @@
 
 #include "abi_internal.hpp"
 #include "util_kernels.hpp"
-#include "sweep_mfma_kernels.hpp"
+#include "sweep_plan.hpp"
 #include "wc_counts_kernels.hpp"
 
 using namespace fmh;
@@ -327,26 +328,21 @@ extern "C" int fmh_stream_synchronize(int device, void* stream) {
 // ------------------------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------------------------
-// LDS the sweep needs for P (padded) groups of an `nvec`-vector row, masks as bytes (fast) or as bits (8x the width);
-// the kernels take at most 150 KiB.  sweep_lds_bytes() > limit means "does not fit in LDS in either form".
+// LDS the masks of a sweep may take: the kernels take at most 150 KiB (the two fit tests against it: sweep_plan.hpp).
 // The limit comes from the device: the LDS a workgroup may opt into, less the kernels' static arrays (block reduction, W&C reciprocal
 // table: about 6 KiB) - 150 KiB on gfx950's 160 KiB.  g_lds[device] is filled by workspace(); 150 KiB until then.
 static const size_t kSweepLdsLimit = 150 * 1024;
 static std::atomic<size_t> g_lds_optin[64], g_lds_per_cu[64];
-static size_t device_lds_limit(int device) {
+size_t fmhi::device_lds_limit(int device) {
   size_t optin = device >= 0 && device < 64 ? g_lds_optin[device].load(std::memory_order_relaxed) : 0;
   const size_t per_cu = device >= 0 && device < 64 ? g_lds_per_cu[device].load(std::memory_order_relaxed) : 0;
   if (optin < per_cu) optin = per_cu;  // runtimes that report the 64-KiB default as the opt-in limit: a workgroup may take the CU's LDS
   return optin >= (size_t)128 * 1024 ? optin - 10 * 1024 : kSweepLdsLimit;
 }
-static size_t device_lds_per_cu(int device) {
+size_t fmhi::device_lds_per_cu(int device) {
   const size_t v = device >= 0 && device < 64 ? g_lds_per_cu[device].load(std::memory_order_relaxed) : 0;
   return v ? v : (size_t)160 * 1024;
 }
-static size_t sweep_lds_limit(int device) { return device_lds_limit(device); }
-// the eight-group W&C kernels keep their regional sums through a static LDS scratch (sweep_kernels.hpp, wc_xpose_scratch): that much less for masks
-static size_t wc_lds_limit(int device, int padded) { return sweep_lds_limit(device) - (padded >= 5 ? fmh::kWcXposeLdsBytes + 1024 : 0); }
-static size_t sweep_lds_bytes(int padded, size_t nvec) { return (size_t)padded * round_up(nvec, 64) * 2; }
 
 static int check_dims(size_t variants, size_t samples, size_t ploidy) {
   if (ploidy == 0 || samples == 0) return fail(FMH_ERR_INVALID, "samples and ploidy must be positive");
@@ -829,14 +825,6 @@ extern "C" int fmh_matrix_generate(fmh_matrix* m, uint64_t seed, uint64_t first_
 // groups
 // ------------------------------------------------------------------------------------------------
 static int padded_groups(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8; }
-// The group count the W&C kernel of a sweep is instantiated with: the padded one (1, 2, 4, 8), or EXACTLY five, six or seven on a packed
-// biallelic matrix with nothing missing - the slots of the padding are then not even compiled in (sweep_launch.inc).
-int fmhi::wc_kernel_groups(const fmh_matrix* m, const fmh_groups* g) {
-  if (!m || !g) return 0;
-  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
-  if (g->n_groups >= 5 && g->n_groups <= 7 && packed && !m->has_missing && m->max_allele <= 1 && options().wc_exact.load() != 0) return g->n_groups;
-  return g->padded;
-}
 
 extern "C" int fmh_groups_create(const fmh_matrix* m, const uint8_t* h_mask, int n_groups, fmh_groups** out) {
   if (!out) return fail(FMH_ERR_INVALID, "out is NULL");
@@ -958,7 +946,7 @@ int fmhi::workspace(int device, Workspace** out) {
 }
 
 // H_k = sum_{i=1..k} 1/i summed ascending (harmonic(), stats.rs:4234-4240); table index k.
-static int ensure_harmonic(Workspace* w, size_t max_k, hipStream_t st) {
+int fmhi::ensure_harmonic(Workspace* w, size_t max_k, hipStream_t st) {
   if (w->harmonic && w->harmonic_len > max_k) return FMH_OK;
   std::vector<double> table(max_k + 2);
   double sum = 0.0;
@@ -978,7 +966,7 @@ static int ensure_harmonic(Workspace* w, size_t max_k, hipStream_t st) {
 }
 
 // one sweep's buffers, taken from / returned to the device's pool
-static int lease_acquire(Workspace* w, SweepLease** out) {
+int fmhi::lease_acquire(Workspace* w, SweepLease** out) {
   {
     std::lock_guard<std::mutex> lock(w->lease_mu);
     if (!w->idle_leases.empty()) { *out = w->idle_leases.back(); w->idle_leases.pop_back(); return FMH_OK; }
@@ -999,13 +987,12 @@ static int lease_acquire(Workspace* w, SweepLease** out) {
   *out = l;
   return FMH_OK;
 }
-struct LeaseHolder {
-  Workspace* w = nullptr;
-  SweepLease* l = nullptr;
-  ~LeaseHolder() {
-    if (w && l) { std::lock_guard<std::mutex> lock(w->lease_mu); w->idle_leases.push_back(l); }
-  }
-};
+// the block partials of a sweep's `grid` workgroups -> the 64 + 64 regional totals
+int fmhi::launch_finalize(const double* part_f64, const unsigned long long* part_u64, int grid, double* out_f64, unsigned long long* out_u64, hipStream_t st) {
+  hipLaunchKernelGGL(finalize_kernel, dim3(kMaxF64 + kMaxU64), dim3(256), 0, st, part_f64, part_u64, grid, out_f64, out_u64);
+  HIP_TRY(hipGetLastError());
+  return FMH_OK;
+}
 
 extern "C" int fmh_timing_enable(int on) { g_timing = on < 0 ? 0 : on; return FMH_OK; }
 extern "C" int fmh_timing_reset(void) {
@@ -1029,307 +1016,8 @@ extern "C" int fmh_timing_read(double* ms, uint64_t* launches) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// dispatch
+// timing of the sweep kernels (the sweeps themselves: sweep_dispatch.hip)
 // ------------------------------------------------------------------------------------------------
-struct SweepResult {
-  double f64[kMaxF64];
-  unsigned long long u64[kMaxU64];
-};
-
-// Column window.  A vector in which no group has a member adds zero to every count, so a sweep reads only the hull of
-// its groups' supports.  On a biallelic matrix with nothing missing the row's total alt count is a property of the resident image (row_alt), so
-// when one or two groups PARTITION the columns one of them need not be counted: alt[g] = row_alt - alt[other], integers, the same bits.  The
-// derived group is the one that leaves the shorter range to read (ties: the second group); nothing is derived when that saves no vector, e.g.
-// interleaved membership.  At least one vector is always read (the kernels' loops have no zero-trip form).
-// Short packed rows, biallelic, nothing missing: the LDS-staged flat-tile route (sweep_flat_kernels.hpp: one row per lane, scalar masks).
-// FMH_FLAT: 1 = wherever it is built, 0 = never, -1 = where it measured ahead of the four-lane route.
-static bool flat_route_taken(const fmh_matrix* m, const fmh_groups* g, int mode) {
-  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
-  const int P = mode == kModeWc ? wc_kernel_groups(m, g) : g->padded;
-  const long long want_flat = options().flat.load();
-  return packed && !m->has_missing && m->max_allele <= 1 && m->pvec <= (uint32_t)kFlatMaskMaxVec && g->mask_flat && flat_route_builds(P, mode) && want_flat != 0 &&
-         (want_flat > 0 || flat_route_default(P, mode, m->pvec));
-}
-ColumnWindow fmhi::sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode) {
-  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
-  ColumnWindow w{0, packed ? m->pvec : m->nvec, -1};
-  if (!packed || m->max_allele > 1 || m->has_missing || m->p1 || m->pc || options().column_window.load() == 0) return w;
-  if (flat_route_taken(m, g, mode)) return w;  // that route stages whole rows
-  auto hull = [&](int skip, uint32_t* first, uint32_t* count) {
-    uint32_t lo = UINT32_MAX, hi = 0;
-    for (int p = 0; p < g->n_groups; ++p) {
-      if (p == skip || g->vec_first[p] > g->vec_last[p]) continue;
-      lo = std::min(lo, g->vec_first[p]);
-      hi = std::max(hi, g->vec_last[p]);
-    }
-    if (lo == UINT32_MAX) { *first = 0; *count = 1; return; }  // no member anywhere: one vector, whose masks are zero
-    *first = lo;
-    *count = hi - lo + 1;
-  };
-  hull(-1, &w.first, &w.count);
-  if ((mode & kModeWc) == 0 && g->n_groups <= 2 && m->row_alt && g->disjoint && g->covers) {
-    for (int d = g->n_groups - 1; d >= 0; --d) {
-      uint32_t first, count;
-      hull(d, &first, &count);
-      if (count < w.count) { w.first = first; w.count = count; w.derived = d; }
-    }
-  }
-  return w;
-}
-
-// The tile-transposed image: a sweep of one or two groups over a packed biallelic matrix with nothing missing that holds
-// the image can read its window from there - whole KiB per tile instead of pieces of 128-byte lines per row.  FMH_TILED: 1 = wherever the route
-// is built, 0 = never, -1 = where it measured ahead of the row-major routes (tiled_route_default: a window of at most seven eighths of the row); never where the flat route is forced.  The
-// window itself is sweep_window's, whichever route reads it.
-static bool tiled_route_taken(const fmh_matrix* m, const fmh_groups* g, int mode) {
-  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
-  const long long want = options().tiled.load();
-  if (!(packed && m->p0t && !m->has_missing && m->max_allele <= 1 && !m->p1 && !m->pc && want != 0 && (mode & kModeWc) == 0 && g->padded <= 2 &&
-        g->n_groups == g->padded && tiled_route_builds(g->padded, mode) && !flat_route_taken(m, g, mode)))
-    return false;
-  return want > 0 || tiled_route_default(sweep_window(m, g, mode).count, m->pvec);
-}
-
-extern "C" int fmh_sweep_tiled(const fmh_matrix* m, const fmh_groups* g, int mode, int* tiled, size_t* image_bytes) {
-  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
-  if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
-    return fail(FMH_ERR_INVALID, "groups were built for a different matrix geometry");
-  if (tiled) *tiled = tiled_route_taken(m, g, mode) ? 1 : 0;
-  if (image_bytes) *image_bytes = m->p0t ? m->p0t_bytes : 0;
-  return FMH_OK;
-}
-
-extern "C" int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_t* first_vec, uint32_t* n_vec, int* derived_group) {
-  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
-  if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
-    return fail(FMH_ERR_INVALID, "groups were built for a different matrix geometry");
-  const ColumnWindow w = sweep_window(m, g, mode);
-  if (first_vec) *first_vec = w.first;
-  if (n_vec) *n_vec = w.count;
-  if (derived_group) *derived_group = w.derived;
-  return FMH_OK;
-}
-
-// Validates, fills the kernel arguments, picks the mask route and enqueues sweep + finalize on `st`: the 128 regional
-// accumulators land in b.out_f64 / b.out_u64 (device).  No synchronisation and no use of the shared workspace buffers, so
-// callers with private buffers (the pipelined sharded sweeps of comm.hip) need no device lock.  `*launched` = false when
-// the row range is empty (nothing was enqueued; the totals are all zero).
-int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, SweepArgs& a, hipStream_t st, const LaunchCtx& ctx,
-                        const SweepBuffers& b, const double* harmonic, bool* launched) {
-  *launched = false;
-  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
-  if (g->device != m->device || g->pitch != m->pitch || g->columns != m->columns)
-    return fail(FMH_ERR_INVALID, "groups were built for a different matrix geometry");
-  if (a.row_begin > m->variants || a.row_count > m->variants - a.row_begin)
-    return fail(FMH_ERR_INVALID, "row range [%zu, +%zu) exceeds %zu variants", a.row_begin, a.row_count, m->variants);
-  FMH_TRY(use_device(m->device));
-  // the packed image when there is one (FMH_LAYOUT=bytes keeps the byte kernels on matrices that still hold their bytes)
-  const bool packed = m->p0 && !(m->data && layout_bytes_forced());
-  if (packed) {
-    a.mv.data = m->p0;
-    a.mv.data1 = m->p1;
-    a.mv.data2 = m->p2;
-    a.mv.bits = m->pc;
-    a.mv.row_hi = m->row_hi;
-    a.mv.row_gap = m->row_gap;
-    a.mv.pitch = m->plane_pitch;
-    a.mv.bits_pitch = m->plane_pitch;
-    a.mv.nvec = m->pvec;
-  } else {
-    if (!m->data) return fail(FMH_ERR_INVALID, "matrix holds neither a byte nor a packed image");
-    a.mv.data = m->data;
-    a.mv.data1 = nullptr;
-    a.mv.data2 = nullptr;
-    a.mv.bits = m->bits;
-    a.mv.row_hi = nullptr;
-    a.mv.row_gap = nullptr;
-    a.mv.pitch = m->pitch;
-    a.mv.bits_pitch = m->bits_pitch;
-    a.mv.nvec = m->nvec;
-  }
-  a.mv.columns = m->columns;
-  a.masks = g->masks;
-  a.mask_pitch = g->mask_pitch;
-  a.mask_bits = g->mask_bits;
-  a.mask_flat = g->mask_flat;
-  // the column window: plane 0 and the bit masks advance to its first vector, the row is as long as the window; pitch and columns stay the row's.
-  // (The whole row and nothing derived: the launch is the one without a window, byte for byte.)
-  const ColumnWindow win = sweep_window(m, g, mode);
-  const uint32_t row_vecs = win.count;  // vectors a row of this sweep has: what sizes lanes per row, batch depth, LDS and deferral below
-  const bool windowed = packed && (win.first != 0 || win.count != m->pvec || win.derived >= 0);
-  a.derived_group = -1;
-  a.row_alt = nullptr;
-  const bool tiled = tiled_route_taken(m, g, mode);
-  if (tiled) {  // the image at the window's first vector: 1 KiB per vector and tile; the masks and the derived group as below
-    a.mv.data = m->p0t + (size_t)win.first * 1024;
-    a.mv.nvec = win.count;
-    a.mask_bits = g->mask_bits + (size_t)win.first * 8;
-    a.derived_group = win.derived;
-    a.row_alt = win.derived >= 0 ? m->row_alt : nullptr;
-  } else if (windowed) {
-    a.mv.data = m->p0 + (size_t)win.first * 16;
-    a.mv.nvec = win.count;
-    a.mask_bits = g->mask_bits + (size_t)win.first * 8;  // one 16-bit word per 16 columns: eight per vector
-    a.derived_group = win.derived;
-    a.row_alt = win.derived >= 0 ? m->row_alt : nullptr;
-  }
-  a.flat_slots = 0;
-  a.flat_defer = 1;
-  for (int p = 0; p < 8; ++p) a.group_size[p] = p < g->n_groups ? (uint32_t)g->sizes[p] : 0;
-  a.n_groups = g->n_groups;
-  a.max_allele = m->max_allele;
-  if (mode & kModeWc) {
-    // without missing data every site has n_i = group size: the allele-independent W&C terms are per launch
-    const int P = mode == kModeWc ? wc_kernel_groups(m, g) : g->padded;
-    uint32_t n8[8];
-    bool use8[8];
-    for (int i = 0; i < 8; ++i) { n8[i] = i < P ? a.group_size[i] : 0; use8[i] = n8[i] != 0; }
-    a.wc_shape[0] = wc_shape<8>(n8, use8);
-    int k = 1;
-    for (int i = 0; i < P; ++i)
-      for (int j = i + 1; j < P; ++j, ++k) {
-        const uint32_t pn[2] = {n8[i], n8[j]};
-        const bool pu[2] = {true, true};
-        a.wc_shape[k] = wc_shape<2>(pn, pu);
-      }
-    a.wc_live_mask = a.wc_s2ok_mask = 0;
-    for (int q = 0; q < k; ++q) {
-      if (a.wc_shape[q].live) a.wc_live_mask |= 1u << q;
-      if (a.wc_shape[q].s2_ok) a.wc_s2ok_mask |= 1u << q;
-    }
-  }
-  a.part_f64 = b.part_f64;
-  a.part_u64 = b.part_u64;
-  if (mode & kModeDiversity) {
-    if (!harmonic) return fail(FMH_ERR_INVALID, "diversity sweep without a harmonic table");
-    a.harmonic = harmonic;
-  }
-  if (a.row_count == 0) return FMH_OK;
-  const bool missing = m->has_missing;
-  const bool general = m->max_allele > 1;
-  const int P = mode == kModeWc ? wc_kernel_groups(m, g) : g->padded;
-  const Options& opt = options();  // one snapshot of the switches per enqueue (atomics; the environment is never read here)
-  a.unroll = opt.unroll.load() == 8 ? 8 : 4;
-  a.nvec_pad = (uint32_t)round_up(m->nvec, 16 * a.unroll);
-  size_t smem = (size_t)P * a.nvec_pad * 16;
-  int mask_mode = kMaskLdsBytes;
-  int lpr = 16;
-  const size_t lds_limit = mode == kModeWc ? wc_lds_limit(m->device, P) : sweep_lds_limit(m->device);
-  if (packed) {
-    // 128 columns per vector.  Rows of up to 32 vectors (4 096 columns) are shared by FOUR lanes (no idle vector slots
-    // on short rows, a two-step reduction: C2 0.081 -> 0.042 ms, C3 0.94 -> 0.63 ms), wider ones by the sixteen lanes of a
-    // DPP row (C4's 40 vectors: 1.32 vs 1.34 ms, 200 000 columns: 0.46 vs 0.66 ms); the batch depth U (vectors per lane in
-    // flight per trip) is the one with the fewest padded slots, ties to the deeper batch.  (Eight lanes per row measured between
-    // the two everywhere - C4 1.37 ms - and is not built.  Round 3 built it once more for the narrow rows, where eight lanes read whole
-    // 128-byte lines - 1 000 haplotypes: one contiguous KB per load instruction -: Hudson +4...+10 % at 1 000 haplotypes, +-1 % at 2 500; four-group
-    // W&C +3...+18 %, summaries -1...+8 % (profiles/r03/ab_eight_lanes_per_row.jsonl).  The 64-byte segments of the four-lane rows are not what holds them back.)
-    const int env_punroll = (int)opt.packed_unroll.load();
-    const int env_lpr = (int)opt.packed_lpr.load();
-    lpr = env_lpr == 4 || env_lpr == 16 ? env_lpr : (row_vecs <= 32 ? 4 : 16);
-    // eight groups: the row loop of many batches is built with the shallow batches only (deeper ones kept P x U mask vectors and subset sums live and
-    // spilled).  A biallelic row with nothing missing that ONE batch of loads per lane covers takes any depth: that loop (tile_rows_packed_prefetch,
-    // MREG = false) re-reads its masks from LDS per row, and a 2 500-haplotype row is then one batch of five loads per lane instead of five trips
-    // of one with a single vector in flight (five groups, which run the eight-group kernel: DESIGN.md section 3).
-    const int us4[4] = {1, 2, 3, 5}, us16[3] = {2, 3, 4};
-    const int* us = lpr != 16 ? us4 : us16;
-    auto pick = [&](bool shallow) {
-      const int nus = shallow ? (lpr != 16 ? 2 : 1) : (lpr != 16 ? 4 : 3);
-      int best_u = us[0];
-      size_t best = SIZE_MAX;
-      for (int k = 0; k < nus; ++k) {
-        const size_t slots = round_up(row_vecs, (size_t)lpr * us[k]);
-        if (slots <= best) { best = slots; best_u = us[k]; }
-      }
-      a.unroll = best_u;
-      for (int k = 0; k < nus; ++k) if (env_punroll == us[k]) a.unroll = env_punroll;
-      a.nvec_pad = (uint32_t)round_up(row_vecs, (size_t)lpr * a.unroll);
-    };
-    const bool no_prefetch = opt.packed_no_prefetch.load() != 0;
-    pick(P >= 5 && (general || missing || no_prefetch));
-    if (P >= 5 && a.nvec_pad != (uint32_t)(lpr * a.unroll)) pick(true);  // not one batch per row: the shallow set
-    // The prefetching row loop (tile_rows_packed_prefetch) is taken when one batch of loads covers a row.  Same-process A/Bs (tools/ab_env.py
-    // FMH_PACKED_NO_PREFETCH=1): on four-lane rows (1 000 and 2 500 haplotypes) it is level or 1-6 % ahead at every launch size; on sixteen-lane
-    // rows with two groups (5 000 haplotypes) it was 2.4-2.9 % ahead at 625 k sites, level at 1 M and 0.6-2.4 % behind from 1.25 M to 10 M sites -
-    // those kernels (one and two groups, sixteen lanes) have since dropped it altogether for the deferred-epilogue loop (sweep_kernel, defer_kernel()).
-    a.single_trip = a.nvec_pad == (uint32_t)(lpr * a.unroll) && !no_prefetch;
-    smem = (size_t)P * a.nvec_pad * 16;
-    mask_mode = kMaskPacked;
-    if (smem > lds_limit)
-      return fail(FMH_ERR_UNSUPPORTED, "%d group masks of %u columns exceed the LDS budget: sweep fewer groups at a time on rows this wide", P, m->columns);
-  } else if (smem > lds_limit) {  // byte masks do not fit LDS: bits in LDS if those fit, else bytes in global memory (L2)
-    smem = (size_t)P * a.nvec_pad * 2;
-    mask_mode = kMaskLdsBits;
-    if (smem > lds_limit) { smem = 0; mask_mode = kMaskGlobalBytes; }
-  }
-  // BASELINE config C5: the counts as an int8 matrix-core contraction (sweep_mfma_kernels.hpp), for u8 rows that are biallelic with
-  // nothing missing and at most four (padded) groups.  An alternative route: the contraction has <= 4 output rows and stays HBM-bound,
-  // so it is measured beside the dot4 route, not chosen by default.  Read per call: tests flip it.
-  const int env_mfma = (int)opt.counts_mfma.load();
-  const int mfma_unroll = env_mfma == 2 ? 2 : 4;
-  // (rows whose byte masks do not fit LDS stay on the dot4 routes)
-  const bool fused_region = (mode & kModeDiversity) != 0 && P == 2;  // not built on the matrix-core route
-  const bool mfma = !packed && !fused_region && env_mfma != 0 && !missing && !general && P <= 4 &&
-                    (size_t)P * mfma_mask_stride(m->nvec, mfma_unroll) * 16 <= lds_limit;
-  if (mfma) {
-    a.unroll = mfma_unroll;
-    a.nvec_pad = mfma_mask_stride(m->nvec, a.unroll);
-    smem = (size_t)P * a.nvec_pad * 16;
-  }
-  const int want = packed || mfma ? -1 : (int)opt.mask_mode.load();
-  if (want >= 0) {  // tests and measurements: take a slower mask route than needed
-    const bool global_ok = P <= 2 && mode != kModeWc;
-    if (want == kMaskLdsBits && mask_mode == kMaskLdsBytes) { smem = (size_t)P * a.nvec_pad * 2; mask_mode = kMaskLdsBits; }
-    if (want == kMaskGlobalBytes && global_ok) { smem = 0; mask_mode = kMaskGlobalBytes; }
-  }
-  // Deferred epilogues (sweep_kernel, defer_kernel()): room behind the mask image for the counts a wave parks, as deep as leaves three workgroups
-  // per CU their LDS (wide rows: the mask image takes it, and a tile of megabytes has nothing to gain from deferral anyway; measured: 200 000
-  // columns fell from 3 to 2 workgroups per CU, 0.45 -> 0.69 ms, before the cap).  The deferring kernels have no other tile loop, so one tile's
-  // room is always added.
-  if (!mfma && defer_rule(P, mode, missing, general, lpr)) {  // the rule the kernel template is instantiated with
-    const int e = (int)opt.defer_tiles.load();  // measurements (1 = the undeferred order); default -1 = by the launch size (launch_one)
-    a.defer_tiles = e >= 1 && e <= kDeferTiles ? e : -1;
-    smem = round_up(smem, 16);
-    int depth = defer_depth_host(P, mode, missing);
-    while (depth > 1 && smem + defer_lds_bytes(P, mode, missing, depth) > device_lds_per_cu(m->device) / 3 - 1024) depth /= 2;
-    a.defer_cap = depth;
-    a.defer_offset = (uint32_t)smem;
-    smem += defer_lds_bytes(P, mode, missing, depth);
-  }
-  int grid = 0;
-  // argument checks shared by every route, then the route's own launcher (sweep_*.hip)
-  if (mode == (kModeSummary | kModeHudson) && P != 2) return fail(FMH_ERR_INVALID, "Hudson sweep needs exactly 2 groups");
-  if (mode == (kModeSummary | kModeDiversity) && P > 2) return fail(FMH_ERR_INVALID, "diversity sweep needs 1 group (or the 2 of a fused region sweep)");
-  if (mode == (kModeSummary | kModeHudson | kModeDiversity) && P != 2) return fail(FMH_ERR_INVALID, "the fused region sweep needs exactly 2 groups");
-  if (mode == kModeWc && P == 1) return fail(FMH_ERR_INVALID, "W&C sweep needs at least 2 groups");
-  if (mode != kModeSummary && mode != (kModeSummary | kModeHudson) && mode != (kModeSummary | kModeDiversity) && mode != (kModeSummary | kModeHudson | kModeDiversity) &&
-      mode != kModeWc)
-    return fail(FMH_ERR_UNSUPPORTED, "unsupported sweep mode %d", mode);
-  if (mask_mode == kMaskGlobalBytes && (P > 2 || mode == kModeWc))
-    return fail(FMH_ERR_UNSUPPORTED, "%d group masks of %u columns exceed the LDS budget: sweep at most two groups at a time on rows this wide", P, m->columns);
-  const bool flat = mask_mode == kMaskPacked && !windowed && !mfma && flat_route_taken(m, g, mode);
-  int rc;
-  if (tiled) rc = launch_sweep_tiled(P, mode, a, st, ctx, &grid);
-  else if (flat) rc = launch_sweep_flat(P, mode, a, st, ctx, &grid);
-  else if (mfma) rc = launch_sweep_mfma(P, mode, a, smem, st, ctx, &grid);
-  else if (mask_mode == kMaskPacked && general && m->p2)  // alleles 4..7: three planes
-    rc = lpr == 4 ? launch_sweep_packed4_3p(P, mode, missing, general, a, smem, st, ctx, &grid) : launch_sweep_packed16_3p(P, mode, missing, general, a, smem, st, ctx, &grid);
-  else if (mask_mode == kMaskPacked) rc = lpr == 4 ? launch_sweep_packed4(P, mode, missing, general, a, smem, st, ctx, &grid) : launch_sweep_packed16(P, mode, missing, general, a, smem, st, ctx, &grid);
-  else if (mask_mode == kMaskGlobalBytes) rc = launch_sweep_global(P, mode, missing, general, a, smem, st, ctx, &grid);
-  else if (mask_mode == kMaskLdsBits) rc = launch_sweep_bits(P, mode, missing, general, a, smem, st, ctx, &grid);
-  else rc = launch_sweep_bytes(P, mode, missing, general, a, smem, st, ctx, &grid);
-  FMH_TRY(rc);
-  hipStream_t fin = st;
-  if (b.finalize_stream && b.swept) {
-    HIP_TRY(hipEventRecord(b.swept, st));
-    HIP_TRY(hipStreamWaitEvent(b.finalize_stream, b.swept, 0));
-    fin = b.finalize_stream;
-  }
-  hipLaunchKernelGGL(finalize_kernel, dim3(kMaxF64 + kMaxU64), dim3(256), 0, fin, b.part_f64, b.part_u64, grid, b.out_f64, b.out_u64);
-  HIP_TRY(hipGetLastError());
-  *launched = true;
-  return FMH_OK;
-}
-
 void fmhi::timing_add(double ms) {
   std::lock_guard<std::mutex> lock(g_ws_mutex);
   if (g_timing_launches == 0 || ms < g_timing_min) g_timing_min = ms;
@@ -1343,45 +1031,6 @@ bool fmhi::timing_enabled() {
   const int n = g_timing.load();
   if (n <= 0) return false;
   return n == 1 || g_timing_seq.fetch_add(1) % (uint64_t)n == 0;
-}
-
-static int run_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, SweepArgs& a, void* stream, SweepResult* res) {
-  if (!m || !g) return fail(FMH_ERR_INVALID, "matrix or groups is NULL");
-  FMH_TRY(use_device(m->device));
-  Workspace* w = nullptr;
-  FMH_TRY(workspace(m->device, &w));
-  LeaseHolder hold;
-  hold.w = w;
-  FMH_TRY(lease_acquire(w, &hold.l));
-  SweepLease* l = hold.l;
-  // The caller's stream, or - for the NULL stream - the lease's own (blocking: ordered against the legacy default stream like the NULL
-  // stream itself, but not against the other leases), so that sweeps of different host threads (run_vcf's region workers) overlap on the device.
-  hipStream_t st = stream ? (hipStream_t)stream : l->stream;
-  const bool timing = timing_enabled();  // one snapshot per sweep: another thread may flip the switch while this one runs
-  const double* harmonic = nullptr;
-  if (mode & kModeDiversity) {
-    std::lock_guard<std::mutex> grow(w->in_use);
-    FMH_TRY(ensure_harmonic(w, m->columns + 1, st));
-    harmonic = w->harmonic;
-  }
-  memset(res, 0, sizeof *res);
-  const LaunchCtx ctx{w->cus, w->max_grid, l->ev0, l->ev1, timing};
-  // finalize_kernel writes the 64 + 64 totals straight into the lease's PINNED host vectors (device-visible): a blocking sweep is then two
-  // launches and one stream synchronisation.  (Two hipMemcpyAsync of 512 B behind the kernels cost more than the kernels on a small cohort:
-  // a lone 512-byte copy_to_host is 22 us on the GPU box, tools/measure_call_overheads.py.)
-  const SweepBuffers bufs{l->part_f64, l->part_u64, l->h_f64, l->h_u64};
-  bool launched = false;
-  FMH_TRY(enqueue_sweep(m, g, mode, a, st, ctx, bufs, harmonic, &launched));
-  if (!launched) return FMH_OK;
-  HIP_TRY(hipStreamSynchronize(st));
-  memcpy(res->f64, l->h_f64, sizeof res->f64);
-  memcpy(res->u64, l->h_u64, sizeof res->u64);
-  if (timing) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, l->ev0, l->ev1) == hipSuccess) timing_add(ms);  // a timing failure never fails a sweep that has its results
-    else (void)hipGetLastError();
-  }
-  return FMH_OK;
 }
 
 static void fill_pop_totals(const uint64_t* capacity, const SweepResult& r, int p, fmh_pop_totals* t) {
@@ -1424,10 +1073,10 @@ extern "C" int fmh_population_summaries(const fmh_matrix* m, const fmh_groups* g
   a.formula = formula;
   a.alt = d_alt;
   a.called = d_called;
-  if (m && g && sweep_lds_bytes(g->padded, m->nvec) > sweep_lds_limit(m->device) && g->n_groups > 2) {
+  if (m && g && !summaries_single_sweep(m, g)) {
     // rows too wide for all masks at once: the populations are independent, sweep them in smaller batches
     int batch = g->n_groups;
-    while (batch > 2 && sweep_lds_bytes(padded_groups(batch), m->nvec) > sweep_lds_limit(m->device)) batch = (batch + 1) / 2;
+    while (batch > 2 && masks_lds_bits_bytes(padded_groups(batch), m->nvec) > device_lds_limit(m->device)) batch = (batch + 1) / 2;
     for (int p0 = 0; p0 < g->n_groups; p0 += batch) {
       const int cnt = std::min(batch, g->n_groups - p0);
       fmh_groups* sub = nullptr;
@@ -1609,16 +1258,6 @@ void fmhi::wc_slot_map(const fmh_matrix* m, const fmh_groups* g, SweepArgs& a) {
       }
     }
 }
-// true when fmh_wc_sweep runs ONE fused kernel that keeps the regional sums itself (2..8 groups, masks in LDS; registers up to four groups,
-// the per-wave LDS transposition beyond): the route the pipelined sharded sweep can finalise and reduce on the device; everything else
-// (alleles beyond 3 with five to eight groups, rows too wide for all masks) goes through the counts route
-bool fmhi::wc_fused_lane_totals(const fmh_matrix* m, const fmh_groups* g) {
-  if (!m || !g || (g->padded == 8 && m->max_allele > 3)) return false;
-  return sweep_lds_bytes(g->padded, m->nvec) <= wc_lds_limit(m->device, g->padded);
-}
-bool fmhi::summaries_single_sweep(const fmh_matrix* m, const fmh_groups* g) {
-  return m && g && !(sweep_lds_bytes(g->padded, m->nvec) > sweep_lds_limit(m->device) && g->n_groups > 2);
-}
 
 extern "C" int fmh_wc_sweep(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_t row_count, double* d_a,
                             double* d_b, uint8_t* d_state, uint32_t* d_group_called, fmh_wc_totals* h_totals,
@@ -1634,8 +1273,7 @@ extern "C" int fmh_wc_sweep(const fmh_matrix* m, const fmh_groups* g, size_t row
   a.called = d_group_called;
   wc_slot_map(m, g, a);
   // the fused kernel for 5..8 groups keeps the counts of alleles 0..3 per site; cohorts with alleles beyond 3 take the counts route
-  const bool many_alleles8 = m && g && g->padded == 8 && m->max_allele > 3;
-  if (m && g && (many_alleles8 || sweep_lds_bytes(g->padded, m->nvec) > wc_lds_limit(m->device, g->padded))) {
+  if (m && g && !wc_fused_lane_totals(m, g)) {
     // (or: rows too wide for all groups' masks to sit in LDS at once) count in smaller batches, components from the count tables
     const size_t nslots = 1 + (size_t)g->n_groups * (g->n_groups - 1) / 2;
     std::vector<double> sa(nslots), sb(nslots);
@@ -1734,7 +1372,7 @@ extern "C" int fmh_wc_sweep_many(const fmh_matrix* m, const uint8_t* h_column_ma
   (void)all_alt;
   // (2) counts of every group, eight groups per sweep
   size_t batch = FMH_MAX_GROUPS;  // as many groups per sweep as the LDS holds masks for
-  while (batch > 2 && sweep_lds_bytes((int)batch, m->nvec) > sweep_lds_limit(m->device)) batch /= 2;  // two groups fit any width (global-mask route)
+  while (batch > 2 && masks_lds_bits_bytes((int)batch, m->nvec) > device_lds_limit(m->device)) batch /= 2;  // two groups fit any width (global-mask route)
   for (size_t g0 = 0; g0 < G; g0 += batch) {
     const int cnt = (int)std::min<size_t>(batch, G - g0);
     fmh_groups* g = nullptr;

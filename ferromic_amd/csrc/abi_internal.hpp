@@ -1,5 +1,5 @@
-// abi_internal.hpp — host-side internals shared by the translation units of libferromic_hip.so (abi.hip, pairwise.hip,
-// comm.hip and the sweep_*.hip files that hold the kernel instantiations).  Nothing here is part of the C-ABI: the library
+// abi_internal.hpp — host-side internals shared by the translation units of libferromic_hip.so (abi.hip, sweep_dispatch.hip,
+// pairwise.hip, comm.hip and the sweep_*.hip files that hold the kernel instantiations).  Nothing here is part of the C-ABI: the library
 // is built with -fvisibility=hidden and only include/ferromic_hip.h's functions are exported.
 #pragma once
 
@@ -145,6 +145,19 @@ struct Workspace {
   std::mutex in_use;  // the harmonic table's growth and the pairwise scratch: one holder at a time per device
 };
 int workspace(int device, Workspace** out);
+// the device's two LDS figures (abi.hip, filled by workspace()): what a workgroup's masks may take, and the LDS of a CU
+size_t device_lds_limit(int device);
+size_t device_lds_per_cu(int device);
+// one sweep's buffers, taken from / returned to the device's pool; the device's harmonic table grown to index max_k (abi.hip)
+int lease_acquire(Workspace* w, SweepLease** out);
+struct LeaseHolder {
+  Workspace* w = nullptr;
+  SweepLease* l = nullptr;
+  ~LeaseHolder() {
+    if (w && l) { std::lock_guard<std::mutex> lock(w->lease_mu); w->idle_leases.push_back(l); }
+  }
+};
+int ensure_harmonic(Workspace* w, size_t max_k, hipStream_t st);
 
 // measurement (fmh_timing_*): accumulated HIP-event time of the sweep kernels
 void timing_add(double ms);
@@ -180,11 +193,18 @@ int upload_planes_from_planes(fmh_matrix* m, const uint8_t* const h_planes[4], s
 void upload_release(int device);
 // planes rows [row0, row0 + rows) of a packed matrix -> byte rows of `pitch` bytes (abi.hip)
 hipError_t unpack_rows(const fmh_matrix* m, size_t row0, size_t rows, uint8_t* data, size_t pitch, hipStream_t st);
-// sweep + finalize enqueued on `st`, no synchronisation (abi.hip)
+// sweep + finalize enqueued on `st`, no synchronisation (sweep_dispatch.hip)
 int enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, fmh::SweepArgs& a, hipStream_t st, const LaunchCtx& ctx,
                   const SweepBuffers& b, const double* harmonic, bool* launched);
+// the blocking form the statistic entry points use: a lease of the device's workspace, enqueue_sweep, synchronise, the totals on the host
+struct SweepResult {
+  double f64[fmh::kMaxF64];
+  unsigned long long u64[fmh::kMaxU64];
+};
+int run_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, fmh::SweepArgs& a, void* stream, SweepResult* res);
+int launch_finalize(const double* part_f64, const unsigned long long* part_u64, int grid, double* out_f64, unsigned long long* out_u64, hipStream_t st);  // abi.hip
 
-// What a sweep of `mode` over these groups reads of every row (abi.hip): vectors [first, first + count) of plane 0, and the
+// What a sweep of `mode` over these groups reads of every row (sweep_plan.hpp): vectors [first, first + count) of plane 0, and the
 // group whose alt count comes from the matrix's row totals instead of being counted (-1: none).  The whole row and -1 unless the image is
 // packed, biallelic and has nothing missing.
 struct ColumnWindow {
@@ -197,7 +217,8 @@ ColumnWindow sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode);
 int pair_region_args(const fmh_groups* g, size_t row_begin, size_t row_count, int summary_formula, int hudson_formula, const fmh_pair_diversity_sites* div,
                      const fmh_hudson_sites* sites, fmh::SweepArgs& a, int* mode);
 int harmonic_table(int device, size_t max_k, hipStream_t st, const double** out);
-// W&C slot order of the padded kernel -> the caller's pair order; which W&C / summaries calls are one fused sweep (abi.hip)
+// W&C slot order of the padded kernel -> the caller's pair order (abi.hip); the kernel's group count and which W&C / summaries calls
+// are one fused sweep (sweep_dispatch.hip, from the predicates of sweep_plan.hpp)
 void wc_slot_map(const fmh_matrix* m, const fmh_groups* g, fmh::SweepArgs& a);
 int wc_kernel_groups(const fmh_matrix* m, const fmh_groups* g);
 bool wc_fused_lane_totals(const fmh_matrix* m, const fmh_groups* g);
@@ -222,11 +243,25 @@ int launch_sweep_bits(int P, int mode, bool missing, bool general, const fmh::Sw
 int launch_sweep_global(int P, int mode, bool missing, bool general, const fmh::SweepArgs& a, size_t smem, hipStream_t st, const LaunchCtx& ctx, int* grid);
 // the LDS-staged flat-tile route (sweep_flat.hip): packed rows of at most kFlatMaskMaxVec vectors, biallelic, nothing missing
 constexpr int kFlatMaskMaxVec = 32;
-bool flat_route_builds(int P, int mode);
+// The (P, mode) pairs each of the three routes is built for, ONE list per route: *_route_builds (what the plan asks) and the route's
+// dispatcher (what is instantiated) are both written from it.
+#define FMH_FLAT_BUILDS(X)                                                                                                         \
+  X(1, fmh::kModeSummary) X(2, fmh::kModeSummary) X(4, fmh::kModeSummary) X(2, fmh::kModeSummary | fmh::kModeHudson)                  \
+  X(1, fmh::kModeSummary | fmh::kModeDiversity) X(2, fmh::kModeSummary | fmh::kModeDiversity)                                        \
+  X(2, fmh::kModeSummary | fmh::kModeHudson | fmh::kModeDiversity) X(2, fmh::kModeWc) X(4, fmh::kModeWc)
+#define FMH_TILED_BUILDS(X)                                                                                                        \
+  X(1, fmh::kModeSummary) X(2, fmh::kModeSummary) X(2, fmh::kModeSummary | fmh::kModeHudson)                                         \
+  X(1, fmh::kModeSummary | fmh::kModeDiversity) X(2, fmh::kModeSummary | fmh::kModeDiversity)                                        \
+  X(2, fmh::kModeSummary | fmh::kModeHudson | fmh::kModeDiversity)
+#define FMH_MFMA_BUILDS(X)                                                                                                         \
+  X(1, fmh::kModeSummary) X(2, fmh::kModeSummary) X(4, fmh::kModeSummary) X(2, fmh::kModeSummary | fmh::kModeHudson)                  \
+  X(1, fmh::kModeSummary | fmh::kModeDiversity) X(2, fmh::kModeWc) X(4, fmh::kModeWc)
+#define FMH_ROUTE_BUILDS_ROW(PV, MODEV) if (P == PV && mode == (MODEV)) return true;
+inline bool flat_route_builds(int P, int mode) { FMH_FLAT_BUILDS(FMH_ROUTE_BUILDS_ROW) return false; }
 inline bool flat_route_default(int P, int mode, uint32_t pvec) { (void)P; (void)mode; (void)pvec; return false; }  // until measured
 int launch_sweep_flat(int P, int mode, const fmh::SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int* grid);
 // the sweep over the tile-transposed image of plane 0 (sweep_tiled.hip): packed, biallelic, nothing missing, one or two groups, not W&C
-bool tiled_route_builds(int P, int mode);
+inline bool tiled_route_builds(int P, int mode) { FMH_TILED_BUILDS(FMH_ROUTE_BUILDS_ROW) return false; }
 // The default rule (FMH_TILED=-1), by measurement (profiles/tiled_planes/): at equal bytes the tiled kernel is about 7 % behind
 // the four-lane ones (the whole row at 5 000 haplotypes), so it is taken where it reads clearly fewer: a window of at most seven eighths of the row.
 // Measured ahead at 20 and 9 of 40 vectors with a group derived (1.11-1.65x), 27 of 40 without (1.28-1.36x), 10 of 20 and 4 of 8 (1.08-1.58x);

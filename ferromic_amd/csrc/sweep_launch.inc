@@ -6,6 +6,7 @@
 //   FMH_ROUTE_NPL  (optional) 3: ONLY the multi-allelic kernels of a three-plane packed matrix (alleles 4..7)
 // defined, so that the routes compile in parallel and a host-side edit of abi.hip does not rebuild any kernel.
 #include "abi_internal.hpp"
+#include "sweep_grid.hpp"
 
 using namespace fmh;
 
@@ -32,33 +33,15 @@ int launch_one(const SweepArgs& args, size_t smem, hipStream_t st, const LaunchC
   void (*kern)(const SweepArgs);
   if constexpr (PIPE) kern = sweep_kernel_pipe<P, MODE, LPR>;
   else kern = sweep_kernel<P, MODE, MISSING, GENERAL, MM, LPR, GENERAL ? FMH_ROUTE_NPL : 2>;
-  static thread_local int cached_occ[64];
-  static thread_local size_t cached_smem[64];
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
+  static thread_local OccupancyCache cache;  // keyed by the dynamic LDS
   if (smem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  if (cached_occ[dev] == 0 || cached_smem[dev] != smem) {
-    int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kBlock, smem));
-    if (occ < 1) occ = 1;
-    if (occ > 8) occ = 8;
-    // sixteen-lane packed rows: three workgroups per CU whatever the occupancy allows - round 2 measured 2, 4, 6 and 8 per CU 14-22 % / 17-22 % /
-    // 0-5 % / 1.5-6 % behind 3 on the C4 sweep, and the one-instruction popcount chain left these kernels at 93-119 VGPRs (4-5 waves per SIMD)
-    if constexpr (MM == kMaskPacked && LPR == 16 && !GENERAL) { if (occ > 3) occ = 3; }
-    cached_occ[dev] = occ;
-    cached_smem[dev] = smem;
-  }
-  // FMH_MAX_OCC is applied per launch, outside the cache: fmh_set_option may change it at any time (tools/ab_env.py alternates it)
-  int occ_now = cached_occ[dev];
-  if (const int env_occ = (int)options().max_occ.load(); env_occ > 0 && occ_now > env_occ) occ_now = env_occ;
+  // sixteen-lane packed rows: three workgroups per CU whatever the occupancy allows - round 2 measured 2, 4, 6 and 8 per CU 14-22 % / 17-22 % /
+  // 0-5 % / 1.5-6 % behind 3 on the C4 sweep, and the one-instruction popcount chain left these kernels at 93-119 VGPRs (4-5 waves per SIMD)
+  constexpr int kCeiling = MM == kMaskPacked && LPR == 16 && !GENERAL ? 3 : 8;
+  int occ = 0;
+  FMH_TRY(cached_occupancy(kern, kBlock, smem, kCeiling, false, cache, smem, &occ));
   const size_t ntiles = (args.row_count + kTileRows - 1) / kTileRows;
-  size_t blocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-  size_t cap = (size_t)ctx.cus * occ_now;
-  if (const long long v = options().grid_per_cu.load(); v > 0) cap = (size_t)ctx.cus * (size_t)v;  // measurements
-  if (const long long v = options().grid_blocks.load(); v > 0) cap = (size_t)v;                     // tests: many tile rounds on small inputs
-  if (blocks > cap) blocks = cap;  // persistent grid (equalising the tile rounds per workgroup was measured: fewer resident waves, slower)
-  if (blocks > (size_t)ctx.max_grid) blocks = ctx.max_grid;
-  if (blocks < 1) blocks = 1;
+  const size_t blocks = persistent_grid(occ, args.row_count, kWavesPerBlock, ctx);
   SweepArgs launch_args = args;
   if (launch_args.defer_tiles < 0) {
     // Deferred epilogues (sweep_kernel, kDefer): how many of its tiles a wave counts before it runs their epilogues, by the tiles it sweeps in
@@ -81,12 +64,7 @@ int launch_one(const SweepArgs& args, size_t smem, hipStream_t st, const LaunchC
     else ch = tile_bytes >= (32u << 10) ? 2 : 1;
     launch_args.defer_tiles = ch;
   }
-  if (ctx.timing) HIP_TRY(hipEventRecord(ctx.ev0, st));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), smem, st, launch_args);
-  HIP_TRY(hipGetLastError());
-  if (ctx.timing) HIP_TRY(hipEventRecord(ctx.ev1, st));
-  *grid_out = (int)blocks;
-  return FMH_OK;
+  return timed_launch(kern, blocks, kBlock, smem, st, ctx, launch_args, grid_out);
 }
 
 template <int P, int MODE>
