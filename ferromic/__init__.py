@@ -12,6 +12,7 @@ from ._core import (  # noqa: E402,F401
     ChromosomePcaResult,
     DiversitySite,
     FstEstimate,
+    HaplotypeWindows,
     HudsonDxyResult,
     HudsonFstResult,
     HudsonFstSite,
@@ -24,6 +25,7 @@ from ._core import (  # noqa: E402,F401
     adjusted_sequence_length,
     chromosome_pca,
     chromosome_pca_to_file,
+    garud_h,
     global_pca,
     hudson_dxy,
     hudson_fst,

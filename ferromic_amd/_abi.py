@@ -111,6 +111,20 @@ class SfsStatsOut(C.Structure):
     ]
 
 
+class HapWindow(C.Structure):
+    _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
+
+
+class HapStatsOut(C.Structure):
+    _fields_ = [
+        ("h1", C.c_double),
+        ("h12", C.c_double),
+        ("h123", C.c_double),
+        ("h2_h1", C.c_double),
+        ("haplotype_diversity", C.c_double),
+    ]
+
+
 class WcTotals(C.Structure):
     _fields_ = [
         ("sum_a", C.c_double * (1 + MAX_PAIRS)),
@@ -172,6 +186,9 @@ SYMBOLS = {
     "fmh_sfs": (_i, [_vp, _vp, _vp, _sz, _vp, _P(SfsSkipped), _vp]),
     "fmh_sfs_joint": (_i, [_vp, _vp, _sz, _sz, _vp, _P(SfsSkipped), _vp]),
     "fmh_sfs_stats": (_i, [_vp, _sz, _P(SfsStatsOut)]),
+    "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
+    "fmh_haplotype_max_members": (_u32, []),
     "fmh_hudson_totals_pack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_hudson_totals_unpack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_pop_totals_pack": (_i, [_P(PopTotals), _i, _P(_d), _P(_u64)]),

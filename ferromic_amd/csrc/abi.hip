@@ -97,6 +97,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_PCA_BUDGET_BYTES", &Options::pca_budget_bytes, (long long)16 << 30, nullptr},
     {"FMH_SFS_ITEM_ROWS", &Options::sfs_item_rows, 0, nullptr},
     {"FMH_SFS_LDS_BINS", &Options::sfs_lds_bins, 0, nullptr},
+    {"FMH_HAP_THREADS", &Options::hap_threads, 0, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

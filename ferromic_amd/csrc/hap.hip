@@ -1,0 +1,158 @@
+// hap.hip — haplotype homozygosity windows: fmh_haplotype_windows (the identical-haplotype classes of one group per row window, as
+// integers), fmh_haplotype_stats (Garud's H1, H12, H123, H2/H1 and haplotype diversity of a window record, host only) and
+// fmh_haplotype_max_members.  Kernel in hap_kernels.hpp; definition in include/ferromic_hip.h, scheme in DESIGN.md section 3.13.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <limits>
+
+#include "abi_internal.hpp"
+#include "hap_kernels.hpp"
+
+using namespace fmh;
+using namespace fmhi;
+
+static_assert(sizeof(fmh_hap_window) == 24 && sizeof(HapWindow) == sizeof(fmh_hap_window), "fmh_hap_window is 24 bytes");
+
+namespace {
+
+struct Window { size_t begin, end; };
+
+// every refusal, in the header's order; none needs a device
+int check_args(const fmh_matrix* m, const fmh_groups* g, const Window* windows, size_t n_windows, const void* d_out, bool want_first) {
+  if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
+  if (!g) return fail(FMH_ERR_INVALID, "NULL groups");
+  if (!windows) return fail(FMH_ERR_INVALID, "h_windows is NULL");
+  if (!d_out) return fail(FMH_ERR_INVALID, "d_out is NULL");
+  if (g->n_groups != 1) return fail(FMH_ERR_INVALID, "the haplotype windows take exactly 1 group, got %d", g->n_groups);
+  if (g->device != m->device || g->columns != m->columns) return fail(FMH_ERR_INVALID, "the groups were not made for this matrix");
+  if (g->sizes[0] == 0) return fail(FMH_ERR_INVALID, "group 0 has no member");
+  for (size_t w = 0; w < n_windows; ++w)
+    if (windows[w].begin > windows[w].end || windows[w].end > m->variants)
+      return fail(FMH_ERR_INVALID, "rows [%zu, %zu) of window %zu exceed the matrix's %zu variants", windows[w].begin, windows[w].end, w, m->variants);
+  if (n_windows == 0) return fail(FMH_ERR_INVALID, "n_windows is 0");
+  if (g->sizes[0] > kHapMaxMembers)
+    return fail(FMH_ERR_UNSUPPORTED, "a group of %llu members exceeds the %u the haplotype kernel holds on chip (fmh_haplotype_max_members)",
+                (unsigned long long)g->sizes[0], kHapMaxMembers);
+  if (want_first && n_windows > ((size_t)1 << 32) / (size_t)g->sizes[0])
+    return fail(FMH_ERR_UNSUPPORTED, "a partition table of %zu windows x %llu members exceeds 2^32 entries", n_windows, (unsigned long long)g->sizes[0]);
+  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the haplotype windows read the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  return FMH_OK;
+}
+
+// Threads of a workgroup: the option, else by measurement (profiles/haplotypes/).  With a window for every compute unit
+// throughput counts, and at 2 500 and 5 000 members 256 threads - six to eight workgroups per CU - ran ahead of 512 (1.4-1.6x) and of 1 024;
+// with fewer windows than compute units a window's own latency counts, and 512 (2 500 members) and 1 024 (5 000) ran ahead of 256 (1.3-1.7x).
+// The ends of both scales (64 threads for the smallest groups, more threads where LDS leaves a CU one or two workgroups) are not measured.
+unsigned pick_threads(uint32_t n, size_t n_windows, int cus) {
+  const long long opt = options().hap_threads.load(std::memory_order_relaxed);
+  if (opt == 64 || opt == 256 || opt == 512 || opt == 1024) return (unsigned)opt;
+  if (n <= 256) return 64;
+  if (n_windows < (size_t)std::max(cus, 1)) return n <= 1024 ? 256 : n <= 4096 ? 512 : 1024;
+  return n <= 8192 ? 256 : n <= 16384 ? 512 : 1024;
+}
+
+}  // namespace
+
+extern "C" uint32_t fmh_haplotype_max_members(void) { return kHapMaxMembers; }
+
+extern "C" int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g, const uint64_t* h_windows, size_t n_windows, fmh_hap_window* d_out,
+                                     uint32_t* d_first_or_null, void* stream) {
+  static_assert(sizeof(Window) == 2 * sizeof(uint64_t), "a window is two u64");
+  const Window* windows = reinterpret_cast<const Window*>(h_windows);
+  FMH_TRY(check_args(m, g, windows, n_windows, d_out, d_first_or_null != nullptr));
+  FMH_TRY(use_device(m->device));
+  Workspace* ws = nullptr;
+  FMH_TRY(workspace(m->device, &ws));
+  hipStream_t st = (hipStream_t)stream;
+
+  // the members' columns, ascending: member rank -> column
+  const uint32_t n = (uint32_t)g->sizes[0];
+  std::vector<uint32_t> cols;
+  cols.reserve(n);
+  for (uint32_t c = 0; c < g->columns; ++c)
+    if (g->host_mask[c]) cols.push_back(c);
+  if (cols.size() != n) return fail(FMH_ERR_INVALID, "the group's mask and size disagree");
+
+  const size_t lds_bytes = hap_lds_bytes(n);
+  int lds_max = 0;
+  HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device));
+  if (lds_bytes > (size_t)std::max(lds_max, 0))
+    return fail(FMH_ERR_UNSUPPORTED, "a group of %u members needs %zu bytes of LDS, this device gives a workgroup %d", n, lds_bytes, lds_max);
+
+  // launch shape: the workgroups a CU holds by LDS and by its 2 048 thread slots (at most eight), FMH_GRID_PER_CU / FMH_GRID_BLOCKS override
+  const unsigned threads = pick_threads(n, n_windows, ws->cus);
+  size_t per_cu = std::max<size_t>(1, std::min<size_t>({(size_t)8, kHapLdsPerCu / lds_bytes, (size_t)2048 / threads}));
+  const long long opt_per_cu = options().grid_per_cu.load(std::memory_order_relaxed);
+  if (opt_per_cu > 0) per_cu = (size_t)std::min<long long>(opt_per_cu, 32);
+  size_t grid = (size_t)std::max(ws->cus, 1) * per_cu;
+  const long long opt_blocks = options().grid_blocks.load(std::memory_order_relaxed);
+  if (opt_blocks > 0) grid = (size_t)std::min<long long>(opt_blocks, 1 << 20);
+  grid = std::min(grid, n_windows);
+
+  DeviceScratch scratch;
+  scratch.device = m->device;
+  scratch.stream = st;
+  uint32_t* d_cols = nullptr;
+  unsigned long long* d_windows = nullptr;
+  FMH_TRY(scratch.get(&d_cols, cols.size()));
+  FMH_TRY(scratch.get(&d_windows, n_windows * 2));
+  HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_windows, h_windows, n_windows * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+
+  HapArgs a{};
+  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
+  a.row_gap = m->pc ? m->row_gap : nullptr;
+  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
+  a.plane_pitch = m->plane_pitch;
+  a.cols = d_cols;
+  a.n = n;
+  a.touch_first = (cols.front() >> 5) * 4;
+  a.touch_last = (cols.back() >> 5) * 4;
+  a.windows = d_windows;
+  a.n_windows = n_windows;
+  a.out = reinterpret_cast<HapWindow*>(d_out);
+  a.first = d_first_or_null;
+
+  const int planes = m->p2 ? 3 : m->p1 ? 2 : 1;
+  void (*kernel)(const HapArgs) = m->pc ? (planes == 3 ? hap_kernel<3, true> : planes == 2 ? hap_kernel<2, true> : hap_kernel<1, true>)
+                                        : (planes == 3 ? hap_kernel<3, false> : planes == 2 ? hap_kernel<2, false> : hap_kernel<1, false>);
+  if (lds_bytes > ((size_t)64 << 10))
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+
+  const bool timing = timing_enabled();
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
+  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds_bytes, st, a);
+  HIP_TRY(hipGetLastError());
+  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if (timing) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    timing_add(ms);
+  }
+  return FMH_OK;
+}
+
+extern "C" int fmh_haplotype_stats(const fmh_hap_window* h_windows, size_t n_windows, uint64_t n, fmh_hap_stats_out* h_out) {
+  if (!h_windows || !h_out) return fail(FMH_ERR_INVALID, "NULL argument");
+  if (n == 0 || n >= ((uint64_t)1 << 26)) return fail(FMH_ERR_INVALID, "n must be 1 .. 2^26 - 1, got %llu", (unsigned long long)n);
+  // each value is ONE division of two integers of at most n^2 < 2^52 (the pooled sums are at most (c1 + c2 + ...)^2 = n^2): both convert exactly
+  const uint64_t n2 = n * n;
+  for (size_t w = 0; w < n_windows; ++w) {
+    const fmh_hap_window& r = h_windows[w];
+    const uint64_t c1 = r.top[0], c2 = r.top[1], c3 = r.top[2];
+    if (r.sum_sq == 0 || r.sum_sq > n2 || c1 * c1 > r.sum_sq || c1 + c2 + c3 > n)
+      return fail(FMH_ERR_INVALID, "window %zu is not a partition of %llu members", w, (unsigned long long)n);
+    fmh_hap_stats_out& o = h_out[w];
+    o.h1 = (double)r.sum_sq / (double)n2;
+    o.h12 = (double)(r.sum_sq + 2 * c1 * c2) / (double)n2;
+    o.h123 = (double)(r.sum_sq + 2 * (c1 * c2 + c1 * c3 + c2 * c3)) / (double)n2;
+    o.h2_h1 = (double)(r.sum_sq - c1 * c1) / (double)r.sum_sq;
+    o.haplotype_diversity = n == 1 ? std::numeric_limits<double>::quiet_NaN() : (double)(n2 - r.sum_sq) / (double)(n * (n - 1));
+  }
+  return FMH_OK;
+}

@@ -907,6 +907,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 
 #include "pymodule_ld.inc"
 #include "pymodule_sfs.inc"
+#include "pymodule_hap.inc"
 
 }  // namespace
 
@@ -1025,6 +1026,8 @@ PYBIND11_MODULE(_core, m) {
       .def("ld_r2", &population_ld_r2, py::arg("max_sites_apart"))
       .def("ld_prune", &population_ld_prune, py::arg("window_sites"), py::arg("r2_threshold"))
       .def("site_frequency_spectrum", &population_sfs, py::arg("windows") = py::none())
+      .def("garud_h", &population_garud_h, py::arg("windows") = py::none(), py::arg("size") = py::none(), py::arg("step") = py::none(),
+           py::arg("partition") = false)
       .def_property_readonly("id", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::int_(p.id.group)) : py::object(py::str(p.id.name)); })
       .def_property_readonly("haplotype_group", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::int_(p.id.group)) : py::object(py::none()); })
       .def_property_readonly("label", [](const Population& p) -> py::object { return p.id.is_group ? py::object(py::none()) : py::object(py::str(p.id.name)); })
@@ -1045,6 +1048,7 @@ PYBIND11_MODULE(_core, m) {
   m.def("per_site_diversity", &per_site_diversity, py::arg("variants"), py::arg("haplotypes"), py::arg("region") = py::none());
   bind_ld(m);
   bind_sfs(m);
+  bind_hap(m);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

@@ -555,3 +555,50 @@ def sfs_stats(counts) -> Dict[str, float]:
     out = _abi.SfsStatsOut()
     _abi.check(_abi.load().fmh_sfs_stats(_ptr(counts), counts.size - 1, C.byref(out)))
     return {name: getattr(out, name) for name, _ in _abi.SfsStatsOut._fields_}
+
+
+# ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
+HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
+HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")
+HAP_THREADS = (64, 256, 512, 1024)   # the values FMH_HAP_THREADS takes
+
+
+@dataclass
+class HapWindowsResult:
+    sum_sq: np.ndarray           # [n_windows] uint64
+    distinct: np.ndarray         # [n_windows] uint32
+    top: np.ndarray              # [n_windows][3] uint32
+    first: Optional[np.ndarray]  # [n_windows][n] uint32, or None when the partition was not asked for
+
+
+def haplotype_max_members() -> int:
+    """fmh_haplotype_max_members: the largest group fmh_haplotype_windows takes (needs no device)."""
+    return int(_abi.load().fmh_haplotype_max_members())
+
+
+def haplotype_windows(m: DeviceMatrix, g: Groups, windows=None, partition: bool = False, stream=None, fill: Optional[int] = None) -> HapWindowsResult:
+    """fmh_haplotype_windows: the identical-haplotype classes of the one group of `g` over row windows [(begin, end), ...] (default: one
+    window, every row).  `fill` pre-fills the outputs with that byte (tests: the call must write every entry)."""
+    w = np.array([[0, m.variants]] if windows is None else windows, dtype=np.uint64).reshape(-1, 2)
+    n_windows, n = w.shape[0], g.sizes[0]
+    junk = None if fill is None else np.full(max(HAP_WINDOW_DTYPE.itemsize * n_windows, 4 * n_windows * n, 8), fill, dtype=np.uint8)
+    out_bytes = max(HAP_WINDOW_DTYPE.itemsize * n_windows, 8)
+    d_out = DeviceBuffer(m.device, out_bytes) if junk is None else DeviceBuffer.from_numpy(m.device, junk[:out_bytes])
+    d_first = None
+    if partition:
+        first_bytes = max(4 * n_windows * n, 8)
+        d_first = DeviceBuffer(m.device, first_bytes) if junk is None else DeviceBuffer.from_numpy(m.device, junk[:first_bytes])
+    _abi.check(_abi.load().fmh_haplotype_windows(m._h, g._h, _ptr(w), n_windows, d_out.ptr, None if d_first is None else d_first.ptr, stream))
+    rec = d_out.to_numpy(np.uint8, HAP_WINDOW_DTYPE.itemsize * n_windows).view(HAP_WINDOW_DTYPE)
+    first = None if d_first is None else d_first.to_numpy(np.uint32, n_windows * n).reshape(n_windows, n)
+    return HapWindowsResult(rec["sum_sq"].copy(), rec["distinct"].copy(), rec["top"].copy(), first)
+
+
+def haplotype_stats(sum_sq, distinct, top, n: int) -> Dict[str, np.ndarray]:
+    """fmh_haplotype_stats (host only): h1, h12, h123, h2_h1 and haplotype_diversity of window records of a group of n members."""
+    sum_sq = np.ascontiguousarray(sum_sq, dtype=np.uint64).reshape(-1)
+    rec = np.zeros(sum_sq.size, dtype=HAP_WINDOW_DTYPE)
+    rec["sum_sq"], rec["distinct"], rec["top"] = sum_sq, np.asarray(distinct).reshape(-1), np.asarray(top).reshape(-1, 3)
+    out = np.zeros((sum_sq.size, len(HAP_STATS)), dtype=np.float64)
+    _abi.check(_abi.load().fmh_haplotype_stats(_ptr(rec), sum_sq.size, int(n), _ptr(out)))
+    return {name: out[:, i].copy() for i, name in enumerate(HAP_STATS)}

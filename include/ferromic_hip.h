@@ -76,7 +76,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_COMM_TRANSPORT (host | rccl)   FMH_UPLOAD_THREADS   FMH_PD_TWO_PLANES   FMH_PD_INT8   FMH_PD_PLANES_BYTES   FMH_PD_KCHUNK
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
- *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS
+ *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -511,6 +511,56 @@ typedef struct {
   double tajima_d, fay_wu_h;                  /* fay_wu_h = pi_sum - theta_h_sum (unnormalised) */
 } fmh_sfs_stats_out;
 int fmh_sfs_stats(const uint64_t* h_sfs, size_t n, fmh_sfs_stats_out* h_out);   /* host only, no device */
+
+/* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
+ * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
+ * A group is a 0/1 column mask with n >= 1 members (fmh_groups); members are ranked 0 .. n-1 by ascending column.  A window is a row range
+ * [begin, end).  An entry's STATE is `uncalled`, or its allele 0 .. 7 when called.  Bits of the allele planes under uncalled entries are
+ * undefined (fmh_matrix_create_packed accepts junk there): every plane is masked with the called plane, as for the spectra.
+ * Two members are IDENTICAL IN A WINDOW iff their states are equal at every row of the window: two uncalled entries are equal, an uncalled
+ * entry and a called one are not (scikit-allel's convention of treating -1 as a value).  The classes of this equivalence have sizes
+ * c_1 >= c_2 >= c_3 >= ...; they sum to n and there are K of them.  An empty window has one class of size n.
+ * Per window the device produces integers only, a record fmh_hap_window:
+ *   sum_sq = sum_i c_i^2     distinct = K     top[0..2] = c_1, c_2, c_3 (0 where K is smaller)
+ * and, when d_first is given, the partition itself in canonical form: d_first[w][i] = the rank of the FIRST (lowest-ranked) member
+ * identical to member i in window w - so d_first[w][i] <= i, == i exactly for one member of each class, and two members are identical iff
+ * their entries are equal.  Results never depend on an option, the grid or the order in which anything ran.
+ *
+ * fmh_haplotype_windows: ONE group over n_windows row ranges [h_windows[2w], h_windows[2w+1]) of the matrix.  Ranges may overlap, be empty
+ *   and come in any order; begin <= end <= variants.  d_out [n_windows] and d_first_or_null [n_windows][n] u32 are on the matrix's device
+ *   and need not be zeroed: every entry is written.  The call enqueues on `stream` and synchronises it.
+ * Refusals, before any device work, in this order: a NULL matrix, groups, windows or d_out pointer; a group count other than 1; groups that
+ * were not made for this matrix; a group with no member; a window outside the matrix or with begin > end; n_windows == 0 - all
+ * FMH_ERR_INVALID; then n > fmh_haplotype_max_members() (the message names the cap); n_windows * n above 2^32 entries when d_first is
+ * given; a matrix without the packed image (call fmh_matrix_pack first) - FMH_ERR_UNSUPPORTED.
+ * fmh_haplotype_max_members (needs no device): the largest group the kernel takes, 34 304 - the partition of a window lives in the 160 KiB
+ *   of LDS of one compute unit, 4.75 bytes per member plus a 512-byte head.  A device that gives a workgroup less LDS than a group needs
+ *   refuses that group with FMH_ERR_UNSUPPORTED.
+ * Option: FMH_HAP_THREADS = 64 | 256 | 512 | 1024 threads per workgroup (other values count as unset).  Default, by measurement: 64 up to 256
+ * members; with at least one window per compute unit 256 up to 8 192 members, 512 up to 16 384, 1 024 beyond; with fewer windows than
+ * compute units 256 up to 1 024 members, 512 up to 4 096, 1 024 beyond.  FMH_GRID_PER_CU / FMH_GRID_BLOCKS size the persistent grid as for
+ * the sweeps.
+ * None changes a result.
+ *
+ * fmh_haplotype_stats (host only, no device): the statistics of n_windows records of a group of n members (1 <= n < 2^26).  Each value is
+ * ONE f64 division of two integers, both below 2^53 and converted exactly, so the quotient is the correctly rounded one:
+ *   h1 = sum_sq / n^2                                  (haplotype homozygosity)
+ *   h12 = (sum_sq + 2 c1 c2) / n^2                     (the two largest classes pooled)
+ *   h123 = (sum_sq + 2 (c1 c2 + c1 c3 + c2 c3)) / n^2  (the three largest pooled)
+ *   h2_h1 = (sum_sq - c1^2) / sum_sq
+ *   haplotype_diversity = (n^2 - sum_sq) / (n (n - 1)),  NaN when n == 1
+ * A record with sum_sq == 0 or sum_sq > n^2, c1^2 > sum_sq or c1 + c2 + c3 > n is no partition of n members: FMH_ERR_INVALID.
+ */
+typedef struct { uint64_t sum_sq;            /* sum of c_i^2 */
+                 uint32_t distinct;          /* K */
+                 uint32_t top[3];            /* c_1, c_2, c_3; 0 where K is smaller */ } fmh_hap_window;   /* 24 bytes */
+typedef struct { double h1, h12, h123, h2_h1, haplotype_diversity; } fmh_hap_stats_out;
+
+int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g /* exactly 1 group */, const uint64_t* h_windows /* [n_windows][2] */,
+                          size_t n_windows, fmh_hap_window* d_out /* [n_windows] */, uint32_t* d_first_or_null /* [n_windows][n] */,
+                          void* stream);
+int fmh_haplotype_stats(const fmh_hap_window* h_windows, size_t n_windows, uint64_t n, fmh_hap_stats_out* h_out);   /* host only, no device */
+uint32_t fmh_haplotype_max_members(void);   /* the largest group the kernel takes; needs no device */
 
 /* ---- multi-GPU: region sharding + RCCL reduce of the regional accumulators -------------------------------- */
 /*
