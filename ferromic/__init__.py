@@ -12,6 +12,7 @@ from ._core import (  # noqa: E402,F401
     ChromosomePcaResult,
     DiversitySite,
     FstEstimate,
+    HaplotypeScan,
     HaplotypeWindows,
     HudsonDxyResult,
     HudsonFstResult,
@@ -25,16 +26,19 @@ from ._core import (  # noqa: E402,F401
     adjusted_sequence_length,
     chromosome_pca,
     chromosome_pca_to_file,
+    ehh_scan,
     garud_h,
     global_pca,
     hudson_dxy,
     hudson_fst,
     hudson_fst_sites,
     hudson_fst_with_sites,
+    ihs,
     inversion_allele_frequency,
     joint_site_frequency_spectrum,
     ld_prune,
     ld_r2,
+    nsl,
     nucleotide_diversity,
     pairwise_differences,
     per_chromosome_pca,

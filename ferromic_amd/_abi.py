@@ -125,6 +125,20 @@ class HapStatsOut(C.Structure):
     ]
 
 
+class EhhParams(C.Structure):
+    _fields_ = [("min_ehh_num", C.c_uint32), ("min_ehh_den", C.c_uint32), ("max_extent", C.c_uint32), ("max_gap", C.c_uint32),
+                ("min_core", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EhhSide(C.Structure):
+    _fields_ = [("area2", C.c_uint64 * 2), ("pair_steps", C.c_uint64 * 2), ("steps", C.c_uint32 * 2), ("core", C.c_uint32 * 2),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EhhStatsOut(C.Structure):
+    _fields_ = [("ihh", C.c_double * 2), ("sl", C.c_double * 2), ("ihs", C.c_double), ("nsl", C.c_double)]
+
+
 class WcTotals(C.Structure):
     _fields_ = [
         ("sum_a", C.c_double * (1 + MAX_PAIRS)),
@@ -189,6 +203,9 @@ SYMBOLS = {
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),
+    "fmh_ehh_scan": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _vp, _P(EhhParams), _vp, _vp, _vp]),
+    "fmh_ehh_stats": (_i, [_vp, _sz, _i, _vp]),
+    "fmh_ehh_max_members": (_u32, []),
     "fmh_hudson_totals_pack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_hudson_totals_unpack": (_i, [_P(HudsonTotals), _P(_d), _P(_u64)]),
     "fmh_pop_totals_pack": (_i, [_P(PopTotals), _i, _P(_d), _P(_u64)]),

@@ -8,6 +8,7 @@
 
 #include "abi_internal.hpp"
 #include "hap_kernels.hpp"
+#include "hap_launch.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -40,18 +41,6 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, const Window* windows, 
   return FMH_OK;
 }
 
-// Threads of a workgroup: the option, else by measurement (profiles/haplotypes/).  With a window for every compute unit
-// throughput counts, and at 2 500 and 5 000 members 256 threads - six to eight workgroups per CU - ran ahead of 512 (1.4-1.6x) and of 1 024;
-// with fewer windows than compute units a window's own latency counts, and 512 (2 500 members) and 1 024 (5 000) ran ahead of 256 (1.3-1.7x).
-// The ends of both scales (64 threads for the smallest groups, more threads where LDS leaves a CU one or two workgroups) are not measured.
-unsigned pick_threads(uint32_t n, size_t n_windows, int cus) {
-  const long long opt = options().hap_threads.load(std::memory_order_relaxed);
-  if (opt == 64 || opt == 256 || opt == 512 || opt == 1024) return (unsigned)opt;
-  if (n <= 256) return 64;
-  if (n_windows < (size_t)std::max(cus, 1)) return n <= 1024 ? 256 : n <= 4096 ? 512 : 1024;
-  return n <= 8192 ? 256 : n <= 16384 ? 512 : 1024;
-}
-
 }  // namespace
 
 extern "C" uint32_t fmh_haplotype_max_members(void) { return kHapMaxMembers; }
@@ -80,15 +69,10 @@ extern "C" int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g, c
   if (lds_bytes > (size_t)std::max(lds_max, 0))
     return fail(FMH_ERR_UNSUPPORTED, "a group of %u members needs %zu bytes of LDS, this device gives a workgroup %d", n, lds_bytes, lds_max);
 
-  // launch shape: the workgroups a CU holds by LDS and by its 2 048 thread slots (at most eight), FMH_GRID_PER_CU / FMH_GRID_BLOCKS override
-  const unsigned threads = pick_threads(n, n_windows, ws->cus);
-  size_t per_cu = std::max<size_t>(1, std::min<size_t>({(size_t)8, kHapLdsPerCu / lds_bytes, (size_t)2048 / threads}));
-  const long long opt_per_cu = options().grid_per_cu.load(std::memory_order_relaxed);
-  if (opt_per_cu > 0) per_cu = (size_t)std::min<long long>(opt_per_cu, 32);
-  size_t grid = (size_t)std::max(ws->cus, 1) * per_cu;
-  const long long opt_blocks = options().grid_blocks.load(std::memory_order_relaxed);
-  if (opt_blocks > 0) grid = (size_t)std::min<long long>(opt_blocks, 1 << 20);
-  grid = std::min(grid, n_windows);
+  // launch shape (hap_launch.hpp; the kernel's 44-46 VGPRs never bound the workgroups a CU holds, so LDS and thread slots decide)
+  const unsigned threads = hap_pick_threads(n, n_windows, ws->cus);
+  size_t grid = 0;
+  FMH_TRY(hap_grid(nullptr, threads, lds_bytes, n_windows, ws->cus, &grid));
 
   DeviceScratch scratch;
   scratch.device = m->device;

@@ -908,6 +908,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_ld.inc"
 #include "pymodule_sfs.inc"
 #include "pymodule_hap.inc"
+#include "pymodule_ehh.inc"
 
 }  // namespace
 
@@ -997,7 +998,8 @@ PYBIND11_MODULE(_core, m) {
       .def_readonly("fst_type", &WcFstResult::fst_type)
       .def("__repr__", &WcFstResult::repr);
 
-  py::class_<Population, shared_ptr<Population>>(m, "Population")
+  py::class_<Population, shared_ptr<Population>> population(m, "Population");
+  population
       .def(py::init([](const py::object& id, const py::object& variants, const py::object& haplotypes, const py::object& sequence_length,
                        const py::object& sample_names) {
              const int64_t L = positive_length(sequence_length);
@@ -1049,6 +1051,7 @@ PYBIND11_MODULE(_core, m) {
   bind_ld(m);
   bind_sfs(m);
   bind_hap(m);
+  bind_ehh(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

@@ -602,3 +602,56 @@ def haplotype_stats(sum_sq, distinct, top, n: int) -> Dict[str, np.ndarray]:
     out = np.zeros((sum_sq.size, len(HAP_STATS)), dtype=np.float64)
     _abi.check(_abi.load().fmh_haplotype_stats(_ptr(rec), sum_sq.size, int(n), _ptr(out)))
     return {name: out[:, i].copy() for i, name in enumerate(HAP_STATS)}
+
+
+# ---- extended haplotype homozygosity scans -------------------------------------------------------------------------------------------
+EHH_SIDE_DTYPE = np.dtype([("area2", np.uint64, (2,)), ("pair_steps", np.uint64, (2,)), ("steps", np.uint32, (2,)), ("core", np.uint32, (2,)),
+                           ("flags", np.uint32), ("reserved", np.uint32)])
+EHH_STATS = ("ihh", "sl", "ihs", "nsl")
+EHH_EDGE0, EHH_EDGE1, EHH_GAP0, EHH_GAP1, EHH_SKIPPED = 1, 2, 4, 8, 16   # fmh_ehh_side.flags
+
+
+@dataclass
+class EhhScanResult:
+    sides: np.ndarray            # [n_focal][2] of EHH_SIDE_DTYPE, the left side first
+    pairs: Optional[np.ndarray]  # [n_focal][2 sides][2 cores][max_extent] uint32, or None when the curve was not asked for
+
+
+def ehh_max_members() -> int:
+    """fmh_ehh_max_members: the largest group fmh_ehh_scan takes (needs no device)."""
+    return int(_abi.load().fmh_ehh_max_members())
+
+
+def ehh_scan(m: DeviceMatrix, g: Groups, focal, row_begin: int = 0, row_end: Optional[int] = None, positions=None, min_ehh=(0, 1),
+             max_extent: int = 0, max_gap: int = 0, min_core: int = 0, curve: bool = False, stream=None, fill: Optional[int] = None) -> EhhScanResult:
+    """fmh_ehh_scan: per focal row and side the integer record of the extended haplotype homozygosity scan of the one group of `g` inside
+    rows [row_begin, row_end) (default: every row).  `positions` [variants] uint32 or None (x(r) = r); min_ehh = (num, den).  `fill`
+    pre-fills the outputs with that byte (tests: the call must write every entry)."""
+    row_end = m.variants if row_end is None else row_end
+    f = np.ascontiguousarray(focal, dtype=np.uint64).reshape(-1)
+    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+    if pos is not None and pos.size != m.variants:
+        raise ValueError("positions must hold one entry per variant of the matrix")
+    params = _abi.EhhParams(int(min_ehh[0]), int(min_ehh[1]), int(max_extent), int(max_gap), int(min_core), 0)
+    out_bytes = max(EHH_SIDE_DTYPE.itemsize * 2 * f.size, 8)
+    pair_count = 4 * f.size * int(max_extent)
+    pair_bytes = max(4 * pair_count, 8)
+
+    def buffer(nbytes):
+        return DeviceBuffer(m.device, nbytes) if fill is None else DeviceBuffer.from_numpy(m.device, np.full(nbytes, fill, dtype=np.uint8))
+
+    d_out = buffer(out_bytes)
+    d_pairs = buffer(pair_bytes) if curve else None
+    _abi.check(_abi.load().fmh_ehh_scan(m._h, g._h, int(row_begin), int(row_end), _ptr(f), f.size, None if pos is None else _ptr(pos), C.byref(params),
+                                        d_out.ptr, None if d_pairs is None else d_pairs.ptr, stream))
+    sides = d_out.to_numpy(np.uint8, EHH_SIDE_DTYPE.itemsize * 2 * f.size).view(EHH_SIDE_DTYPE).reshape(f.size, 2).copy()
+    pairs = None if d_pairs is None else d_pairs.to_numpy(np.uint32, pair_count).reshape(f.size, 2, 2, int(max_extent))
+    return EhhScanResult(sides, pairs)
+
+
+def ehh_stats(sides, include_edges: bool = False) -> Dict[str, np.ndarray]:
+    """fmh_ehh_stats (host only): ihh [F][2], sl [F][2], ihs [F] and nsl [F] of records [F][2] of EHH_SIDE_DTYPE."""
+    sides = np.ascontiguousarray(sides, dtype=EHH_SIDE_DTYPE).reshape(-1, 2)
+    out = np.zeros((sides.shape[0], 6), dtype=np.float64)
+    _abi.check(_abi.load().fmh_ehh_stats(_ptr(sides), sides.shape[0], int(bool(include_edges)), _ptr(out)))
+    return dict(ihh=out[:, 0:2].copy(), sl=out[:, 2:4].copy(), ihs=out[:, 4].copy(), nsl=out[:, 5].copy())

@@ -562,6 +562,72 @@ int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g /* exactly 1 
 int fmh_haplotype_stats(const fmh_hap_window* h_windows, size_t n_windows, uint64_t n, fmh_hap_stats_out* h_out);   /* host only, no device */
 uint32_t fmh_haplotype_max_members(void);   /* the largest group the kernel takes; needs no device */
 
+/* ---- extended haplotype homozygosity scans: the integers behind iHS and nSL (an addition: the reference has none) -----------------
+ * How far identity extends around a site.  Matrix, group (exactly one, n members), member ranks and an entry's STATE are those of
+ * fmh_haplotype_windows: uncalled, or allele 0 .. 7 under the called plane; two uncalled entries are equal.
+ * Per call: a row range [row_begin, row_end) that no scan leaves; h_focal[n_focal], u64 rows inside the range, in any order, repeats
+ * allowed; h_positions_or_null[variants] u32, non-decreasing over the range - x(r) = h_positions[r], NULL means x(r) = r; and
+ * fmh_ehh_params: min_ehh_num / min_ehh_den (den >= 1, num <= den; num == 0 = no threshold), max_extent (0 = unlimited), max_gap (0 = none),
+ * min_core.
+ * CORE CLASSES of focal row f: core 0 = the members whose state at f is called allele 0, core 1 = those with called allele 1; every other
+ * member (uncalled, allele >= 2) belongs to neither and counts nowhere.  n_a = the size of core a, P_a(0) = n_a (n_a - 1) / 2.
+ * PAIR COUNTS: for side s in {-1 (left), +1 (right)} and d >= 1, r_d = f + s d; P_a(d) = the number of unordered pairs of core-a members
+ * whose states agree at every row f, r_1, .., r_d.  Every flanking row counts whatever it holds (uncalled and alleles >= 2 are states).
+ * STOP RULES, per side and core, with alive_a = P_a(0) > 0 and gap_d = |x(r_d) - x(r_{d-1})| (r_0 = f): for d = 1, 2, .. while a core is
+ * alive, d <= max_extent (when that is not 0) and r_d is inside the range, for each alive a in this order:
+ *   1. if max_gap > 0 and gap_d > max_gap: flag GAP_a, the core is finished;
+ *   2. else if P_a(d) den < P_a(0) num: the core is finished (the normal end; the step is not counted);
+ *   3. else area2_a += (P_a(d-1) + P_a(d)) gap_d, pair_steps_a += P_a(d), steps_a = d; if P_a(d) == 0 the core is finished.
+ * A core still alive when the loop ends gets flag EDGE_a.  If min(n_0, n_1) < min_core the item writes flag SKIPPED, zeros and n_0, n_1
+ * and scans nothing.  All products fit u64: P < 2^30, den < 2^32, the span of positions < 2^32, area2 <= 2 P(0) span < 2^63.
+ * The record fmh_ehh_side, one per (focal, side), d_out[n_focal][2] with the left side first (56 bytes), is integers only; optional
+ * d_pairs_or_null[n_focal][2 sides][2 cores][max_extent] u32: entry d-1 holds P_a(d) for 1 <= d <= steps_a, every other entry is 0.  Every
+ * entry of both is written: nothing needs zeroing beforehand.  Results never depend on an option, the grid, the thread count or the order
+ * in which anything ran.  The call enqueues on `stream` and synchronises it.
+ *
+ * Refusals of fmh_ehh_scan, before any device work, in this order: a NULL matrix, groups, h_focal, params or d_out pointer; a group count
+ * other than 1; groups that were not made for this matrix; a group with no member; row_begin > row_end or row_end > variants; a focal row
+ * outside the range; n_focal == 0; min_ehh_den == 0; min_ehh_num > min_ehh_den; positions that descend inside the range; d_pairs given
+ * with max_extent == 0 - all FMH_ERR_INVALID; then n > fmh_ehh_max_members() (the message names the cap); d_pairs above 2^32 entries; a
+ * matrix without the packed image (call fmh_matrix_pack first) - FMH_ERR_UNSUPPORTED.
+ * fmh_ehh_max_members (needs no device): 34 304, the cap of fmh_haplotype_windows - the scan keeps the same state per member in LDS (one
+ *   u32: the label, and in turn the parked row state and the class size) and needs nothing more.
+ * Options: FMH_HAP_THREADS, FMH_GRID_PER_CU and FMH_GRID_BLOCKS as for fmh_haplotype_windows, with items (focal, side) in place of windows.
+ *
+ * fmh_ehh_stats (host only, no device): per focal, from its two records and for a in {0, 1}:
+ *   ihh_a = (double)(area2_L + area2_R) / (double)(2 P_a(0))
+ *   sl_a  = (double)(P_a(0) + pair_steps_L + pair_steps_R) / (double)P_a(0)
+ * each two exact-or-correctly-rounded u64 -> f64 conversions and one division; then ihs = log(ihh_1 / ihh_0), nsl = log(sl_1 / sl_0).
+ * ihh_a and sl_a are NaN where P_a(0) == 0, where the item is SKIPPED, and - unless include_edges != 0 - where any EDGE or GAP flag of
+ * either side and core is set; ihs and nsl are NaN where one of their operands is NaN or 0.  Two records of a focal that disagree in
+ * core[] or in SKIPPED are FMH_ERR_INVALID.
+ */
+#define FMH_EHH_EDGE0 1u     /* core 0 was still alive at max_extent or at the end of the range */
+#define FMH_EHH_EDGE1 2u
+#define FMH_EHH_GAP0 4u      /* core 0 met a gap above max_gap */
+#define FMH_EHH_GAP1 8u
+#define FMH_EHH_SKIPPED 16u  /* min(n_0, n_1) < min_core: nothing was scanned */
+typedef struct { uint32_t min_ehh_num, min_ehh_den;   /* the threshold num / den on P(d) / P(0); num == 0 = none */
+                 uint32_t max_extent;                 /* rows a side may walk; 0 = unlimited */
+                 uint32_t max_gap;                    /* 0 = none */
+                 uint32_t min_core;
+                 uint32_t reserved;                   /* 0 */ } fmh_ehh_params;
+typedef struct { uint64_t area2[2];        /* per core: sum of (P(d-1) + P(d)) gap_d over the counted steps */
+                 uint64_t pair_steps[2];   /* per core: sum of P(d) over the counted steps */
+                 uint32_t steps[2];        /* per core: the last counted d */
+                 uint32_t core[2];         /* n_0, n_1 */
+                 uint32_t flags;           /* FMH_EHH_* */
+                 uint32_t reserved;        /* 0 */ } fmh_ehh_side;   /* 56 bytes */
+typedef struct { double ihh[2], sl[2], ihs, nsl; } fmh_ehh_stats_out;
+
+int fmh_ehh_scan(const fmh_matrix* m, const fmh_groups* g /* exactly 1 group */, size_t row_begin, size_t row_end,
+                 const uint64_t* h_focal /* [n_focal] */, size_t n_focal, const uint32_t* h_positions_or_null /* [variants] */,
+                 const fmh_ehh_params* params, fmh_ehh_side* d_out /* [n_focal][2] */,
+                 uint32_t* d_pairs_or_null /* [n_focal][2][2][max_extent] */, void* stream);
+int fmh_ehh_stats(const fmh_ehh_side* h_sides /* [n_focal][2] */, size_t n_focal, int include_edges,
+                  fmh_ehh_stats_out* h_out /* [n_focal] */);   /* host only, no device */
+uint32_t fmh_ehh_max_members(void);   /* the largest group the scan takes; needs no device */
+
 /* ---- multi-GPU: region sharding + RCCL reduce of the regional accumulators -------------------------------- */
 /*
  * Sites are independent: rank r of G sweeps only its contiguous slab of the region and writes its own
