@@ -11,6 +11,8 @@ _abi.load()
 from ._core import (  # noqa: E402,F401
     ChromosomePcaResult,
     DiversitySite,
+    FStatEstimate,
+    FStatistics,
     FstEstimate,
     HaplotypeScan,
     HaplotypeWindows,
@@ -27,6 +29,7 @@ from ._core import (  # noqa: E402,F401
     chromosome_pca,
     chromosome_pca_to_file,
     ehh_scan,
+    f_statistics,
     garud_h,
     global_pca,
     hudson_dxy,

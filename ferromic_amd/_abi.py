@@ -111,6 +111,10 @@ class SfsStatsOut(C.Structure):
     ]
 
 
+class JackknifeOut(C.Structure):
+    _fields_ = [("estimate", C.c_double), ("jackknife_estimate", C.c_double), ("se", C.c_double), ("z", C.c_double), ("blocks", C.c_uint64)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -200,6 +204,10 @@ SYMBOLS = {
     "fmh_sfs": (_i, [_vp, _vp, _vp, _sz, _vp, _P(SfsSkipped), _vp]),
     "fmh_sfs_joint": (_i, [_vp, _vp, _sz, _sz, _vp, _P(SfsSkipped), _vp]),
     "fmh_sfs_stats": (_i, [_vp, _sz, _P(SfsStatsOut)]),
+    "fmh_fstat_moments": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _P(SfsSkipped), _vp]),
+    "fmh_fstat_moment_count": (_sz, [_i]),
+    "fmh_fstat_f4": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _P(_d)]),
+    "fmh_block_jackknife": (_i, [_vp, _vp, _vp, _sz, _P(JackknifeOut)]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

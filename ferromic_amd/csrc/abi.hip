@@ -98,6 +98,8 @@ const OptionRow kOptionRows[] = {
     {"FMH_SFS_ITEM_ROWS", &Options::sfs_item_rows, 0, nullptr},
     {"FMH_SFS_LDS_BINS", &Options::sfs_lds_bins, 0, nullptr},
     {"FMH_HAP_THREADS", &Options::hap_threads, 0, nullptr},
+    {"FMH_FSTAT_ITEM_ROWS", &Options::fstat_item_rows, 0, nullptr},
+    {"FMH_FSTAT_LDS_MASK_BYTES", &Options::fstat_lds_mask_bytes, 0, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -909,6 +909,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_sfs.inc"
 #include "pymodule_hap.inc"
 #include "pymodule_ehh.inc"
+#include "pymodule_fstat.inc"
 
 }  // namespace
 
@@ -1052,6 +1053,7 @@ PYBIND11_MODULE(_core, m) {
   bind_sfs(m);
   bind_hap(m);
   bind_ehh(m, population);
+  bind_fstat(m);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

@@ -557,6 +557,62 @@ def sfs_stats(counts) -> Dict[str, float]:
     return {name: getattr(out, name) for name, _ in _abi.SfsStatsOut._fields_}
 
 
+# ---- Patterson f-statistics ----------------------------------------------------------------------------------------------------------
+FSTAT_DEFAULT_ITEM_ROWS = 4096       # FMH_FSTAT_ITEM_ROWS unset
+FSTAT_DEFAULT_LDS_MASK_BYTES = 8192  # FMH_FSTAT_LDS_MASK_BYTES unset
+
+
+@dataclass
+class FstatMoments:
+    moments: np.ndarray        # [n_blocks][M] uint64
+    multiallelic: np.ndarray   # [n_blocks] uint64
+    incomplete: np.ndarray
+    sizes: np.ndarray          # [G] uint64
+
+
+def fstat_moment_count(n_groups: int) -> int:
+    """fmh_fstat_moment_count: M = 1 + G + G (G + 1) / 2, 0 when G is outside 2..32 (needs no device)."""
+    return int(_abi.load().fmh_fstat_moment_count(int(n_groups)))
+
+
+def fstat_moments(m: DeviceMatrix, masks: np.ndarray, blocks=None, stream=None) -> FstatMoments:
+    """fmh_fstat_moments: the moment slices of the G groups `masks` [G][columns] over row blocks [(begin, end), ...] (default: one block,
+    every row)."""
+    masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    b = np.array([[0, m.variants]] if blocks is None else blocks, dtype=np.uint64).reshape(-1, 2)
+    n_blocks, width = b.shape[0], fstat_moment_count(masks.shape[0])
+    skipped = (_abi.SfsSkipped * max(n_blocks, 1))()
+    d_moments = DeviceBuffer(m.device, max(8 * n_blocks * width, 8))
+    _abi.check(_abi.load().fmh_fstat_moments(m._h, _ptr(masks), masks.shape[0], _ptr(b), n_blocks, d_moments.ptr, skipped, stream))
+    multi, incomplete = _skipped_arrays(skipped, n_blocks)
+    return FstatMoments(d_moments.to_numpy(np.uint64, n_blocks * width).reshape(n_blocks, width), multi, incomplete,
+                        masks.astype(bool).sum(axis=1).astype(np.uint64))
+
+
+def fstat_f4(moments, sizes, a: int, b: int, c: int, d: int, unbiased: bool = True) -> float:
+    """fmh_fstat_f4 (host only): the block's sum of the estimator of (p_a - p_b)(p_c - p_d) from one slice."""
+    moments = np.ascontiguousarray(moments, dtype=np.uint64).reshape(-1)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    if moments.size != fstat_moment_count(sizes.size):
+        raise ValueError("one block's slice has 1 + G + G (G + 1) / 2 entries for the G sample sizes")
+    out = C.c_double()
+    _abi.check(_abi.load().fmh_fstat_f4(_ptr(moments), _ptr(sizes), sizes.size, a, b, c, d, int(bool(unbiased)), C.byref(out)))
+    return out.value
+
+
+def block_jackknife(num, den, weight=None) -> Dict[str, float]:
+    """fmh_block_jackknife (host only): the weighted delete-one-block jackknife of sum(num) / sum(den)."""
+    num = np.ascontiguousarray(num, dtype=np.float64).reshape(-1)
+    den = np.ascontiguousarray(den, dtype=np.float64).reshape(-1)
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    if den.size != num.size or (weight is not None and weight.size != num.size):
+        raise ValueError("num, den and weight have one entry per block")
+    out = _abi.JackknifeOut()
+    _abi.check(_abi.load().fmh_block_jackknife(_ptr(num), _ptr(den), _ptr(weight), num.size, C.byref(out)))
+    return {name: getattr(out, name) for name, _ in _abi.JackknifeOut._fields_}
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

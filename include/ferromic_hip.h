@@ -76,7 +76,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_COMM_TRANSPORT (host | rccl)   FMH_UPLOAD_THREADS   FMH_PD_TWO_PLANES   FMH_PD_INT8   FMH_PD_PLANES_BYTES   FMH_PD_KCHUNK
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
- *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)
+ *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -511,6 +511,71 @@ typedef struct {
   double tajima_d, fay_wu_h;                  /* fay_wu_h = pi_sum - theta_h_sum (unnormalised) */
 } fmh_sfs_stats_out;
 int fmh_sfs_stats(const uint64_t* h_sfs, size_t n, fmh_sfs_stats_out* h_out);   /* host only, no device */
+
+/* ---- Patterson f-statistics: f2, f3, f4 from exact moment blocks (an addition: the reference has none) ------------------------
+ * The device returns integers only: per block of rows, the sums of the groups' allele counts and of their pairwise products.  Every f2, f3
+ * and f4 over a block, biased or unbiased, is a fixed rational function of those sums and of the constant sample sizes, evaluated once on
+ * the host (fmh_fstat_f4).
+ * GROUPS: G column masks, h_column_mask[g*columns + c], 0/1 bytes on the host (as fmh_wc_sweep_many takes them), 2 <= G <=
+ * FMH_FSTAT_MAX_GROUPS.  Every group has n_g >= 1 members; groups may overlap.
+ * ROW CLASSIFICATION, against all G groups at once, in this order of precedence (the joint spectrum's rule):
+ *   1. multiallelic: a called member of any group carries an allele above 1;
+ *   2. incomplete:   a member of any group is not called;
+ *   3. usable:       a_g = the members of g whose allele is 1, 0 <= a_g <= n_g.
+ * Every allele plane is masked with the called plane (junk under uncalled entries is allowed); columns no group holds never matter.
+ * Monomorphic rows are usable.
+ * BLOCKS: row ranges [h_blocks[2b], h_blocks[2b+1]); they may overlap, be empty and come in any order.  For each block the call fills a
+ * slice of M = 1 + G + G (G + 1) / 2 u64 (fmh_fstat_moment_count):
+ *   [0]             usable rows
+ *   [1 + g]         sum of a_g over the usable rows
+ *   [1 + G + t]     sum of a_i a_j for i <= j, t = i G - i (i - 1) / 2 + (j - i): the upper triangle row-major, diagonal included
+ * and the {multiallelic, incomplete} tallies of the block (fmh_sfs_skipped): usable + multiallelic + incomplete == rows of the block.
+ * Results never depend on a route, an option, the grid or the order in which anything ran.
+ *
+ * fmh_fstat_moments: d_moments is [n_blocks][M] u64 on the matrix's device, zero-filled by the call; h_skipped [n_blocks] or NULL.  The call
+ *   enqueues on `stream` and synchronises it.  All blocks empty is FMH_OK with a zeroed table.
+ * Refusals, before any device work, in this order: a NULL matrix, mask, blocks or table pointer; n_groups outside 2..32; a group with no
+ * member; a block outside the matrix or with begin > end; n_blocks == 0 - all FMH_ERR_INVALID; a block with rows * max(n_g)^2 >= 2^63 (a
+ * u64 moment could wrap); a matrix without the packed image (call fmh_matrix_pack first) - FMH_ERR_UNSUPPORTED.
+ * Options: FMH_FSTAT_ITEM_ROWS = the most rows of a work item (default 4 096; a longer block is cut into equal items); FMH_FSTAT_LDS_MASK_BYTES = the bytes of a workgroup's LDS the groups'
+ * mask entries may take (default 8 192, with which eight workgroups still share a compute unit; a set of groups that needs more is read
+ * from global memory; 1 forces that).  Neither changes a result.
+ *
+ * fmh_fstat_f4 (host only, no device): from ONE block's slice and the G sample sizes, the sum over the block's usable rows of the
+ * estimator of (p_A - p_B)(p_C - p_D), p_X = a_X / n_X.  Indices may repeat: f2(A,B) = (A,B;A,B), f3(C;A,B) = (C,A;C,B).  With S_XY the
+ * product moments
+ *   biased sum = S_AC/(nA nC) - S_AD/(nA nD) - S_BC/(nB nC) + S_BD/(nB nD),
+ * evaluated as ONE exact 128-bit integer numerator over the common denominator nA nB nC nD and divided once in f64 (a moment is below
+ * 2^63, each term's cofactor at most 2^34 with sizes up to 2^17; beyond that the call refuses).  With `unbiased`, every coincidence
+ * of indices removes the bias of p_X^2 with  h_X = (n_X S_X - S_XX) / (n_X^2 (n_X - 1)),  S_X the sum of a_X:
+ *   -h_A if A == C,  +h_A if A == D,  +h_B if B == C,  -h_B if B == D;
+ * each h_X is one exact integer numerator, one exact integer denominator and one division.  The result is NaN if a needed n_X < 2.  No sum
+ * is divided by a site count here.  A NULL pointer, n_groups outside 2..32, an index outside 0..n_groups-1 or a size of 0: FMH_ERR_INVALID;
+ * a size above 2^17: FMH_ERR_UNSUPPORTED.
+ *
+ * fmh_block_jackknife (host only, no device): the weighted delete-one-block jackknife (Busing et al. 1999, as ADMIXTOOLS uses it) of
+ * theta = sum(num) / sum(den) over n_blocks blocks of weight m_j = h_weight[j] (NULL: m_j = den_j).  Blocks of weight 0 are dropped; g are
+ * left, n = sum m_j, and with the sums over those g blocks
+ *   theta_(-j) = (sum num - num_j) / (sum den - den_j)        theta_J = g theta - sum_j (1 - m_j / n) theta_(-j)
+ *   h_j = n / m_j      tau_j = h_j theta - (h_j - 1) theta_(-j)      var = (1 / g) sum_j (tau_j - theta_J)^2 / (h_j - 1)
+ * Output {estimate = theta, jackknife_estimate = theta_J, se = sqrt(var), z = theta / se, blocks = g}; se and z are NaN when g < 2 (and
+ * theta_J = theta at g == 1: the one block's factor 1 - m / n is 0), every f64 field is NaN when sum(den) == 0.  A NULL num, den or output pointer, or a negative or non-finite weight: FMH_ERR_INVALID.
+ *
+ * Out of scope here: Patterson's D normalisation (its denominator is fourth-order in the counts: u64 sums wrap at n = 5 000 after 8 192
+ * rows, it needs 128-bit accumulation; f4 and its Z are the admixture test delivered), projection over missing calls, u8-row matrices,
+ * sharding over devices (the tables are integers: a caller adds them).
+ */
+#define FMH_FSTAT_MAX_GROUPS 32
+typedef struct { double estimate, jackknife_estimate, se, z; uint64_t blocks; } fmh_jackknife_out;
+
+int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_mask /* [n_groups][columns] */, int n_groups,
+                      const uint64_t* h_blocks /* [n_blocks][2] */, size_t n_blocks, uint64_t* d_moments /* [n_blocks][M] */,
+                      fmh_sfs_skipped* h_skipped_or_null /* [n_blocks] */, void* stream);
+size_t fmh_fstat_moment_count(int n_groups);   /* M; 0 when n_groups is outside 2..32; needs no device */
+int fmh_fstat_f4(const uint64_t* h_moments /* one block: [M] */, const uint64_t* h_sizes /* [n_groups] */, int n_groups,
+                 int A, int B, int C, int D, int unbiased, double* h_sum);   /* host only, no device */
+int fmh_block_jackknife(const double* h_num, const double* h_den, const double* h_weight_or_null /* NULL = den */, size_t n_blocks,
+                        fmh_jackknife_out* h_out);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
