@@ -20,6 +20,7 @@ from ._core import (  # noqa: E402,F401
     HudsonFstResult,
     HudsonFstSite,
     JointSiteFrequencySpectrum,
+    Kinship,
     PairwiseDifference,
     Population,
     SiteFrequencySpectrum,
@@ -39,6 +40,7 @@ from ._core import (  # noqa: E402,F401
     ihs,
     inversion_allele_frequency,
     joint_site_frequency_spectrum,
+    kinship,
     ld_prune,
     ld_r2,
     nsl,

@@ -115,6 +115,10 @@ class JackknifeOut(C.Structure):
     _fields_ = [("estimate", C.c_double), ("jackknife_estimate", C.c_double), ("se", C.c_double), ("z", C.c_double), ("blocks", C.c_uint64)]
 
 
+class KinshipOut(C.Structure):
+    _fields_ = [("d_both", C.c_void_p), ("d_het_het", C.c_void_p), ("d_ibs0", C.c_void_p), ("d_het_hom", C.c_void_p)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -208,6 +212,9 @@ SYMBOLS = {
     "fmh_fstat_moment_count": (_sz, [_i]),
     "fmh_fstat_f4": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _P(_d)]),
     "fmh_block_jackknife": (_i, [_vp, _vp, _vp, _sz, _P(JackknifeOut)]),
+    "fmh_kinship_counts": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _P(KinshipOut), _P(_u64), _vp]),
+    "fmh_kinship_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "fmh_kinship_unrelated": (_i, [_vp, _sz, _d, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),
@@ -246,6 +253,7 @@ SYMBOLS = {
     "fmh_timing_read_reduce": (_i, [_P(_d), _P(_u64)]),
     "fmh_timing_reset_reduce": (_i, []),
     "fmh_timing_read_pca": (_i, [_P(_d)]),
+    "fmh_timing_read_gram": (_i, [_P(_d)]),
     "fmh_timing_enable": (_i, [_i]),
     "fmh_timing_reset": (_i, []),
     "fmh_timing_read": (_i, [_P(_d), _P(_u64)]),

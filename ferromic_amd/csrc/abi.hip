@@ -100,6 +100,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_HAP_THREADS", &Options::hap_threads, 0, nullptr},
     {"FMH_FSTAT_ITEM_ROWS", &Options::fstat_item_rows, 0, nullptr},
     {"FMH_FSTAT_LDS_MASK_BYTES", &Options::fstat_lds_mask_bytes, 0, nullptr},
+    {"FMH_KIN_BUDGET_BYTES", &Options::kin_budget_bytes, (long long)16 << 30, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -89,6 +89,7 @@ struct Options {
   std::atomic<long long> hap_threads{0};         // FMH_HAP_THREADS = 64 | 256 | 512 | 1024: threads per workgroup of the haplotype window kernel (raised where a group needs more); 0 = by the group size
   std::atomic<long long> fstat_item_rows{0};     // FMH_FSTAT_ITEM_ROWS: rows per work item of the f-statistics moment kernel; 0 = 4 096
   std::atomic<long long> fstat_lds_mask_bytes{0};  // FMH_FSTAT_LDS_MASK_BYTES: LDS bytes that kernel's mask entries may take; 0 = 8 192 (eight workgroups per CU stay resident); entries that need more are read from global memory (1 forces that)
+  std::atomic<long long> kin_budget_bytes{(long long)16 << 30};  // FMH_KIN_BUDGET_BYTES: the Gram scratch one fmh_kinship_counts call may take
   std::atomic<long long> graph{0};               // FMH_GRAPH: 1 = replay a repeated pipelined sweep on a local communicator from a captured hipGraph
   std::atomic<unsigned long long> generation{0}; // bumped by every fmh_set_option: a captured launch is never replayed across an option change
 };

@@ -644,9 +644,10 @@ __global__ __launch_bounds__(kPdPhaseThreads) void pd_gram256p_kernel(const uint
   }
 }
 
+// (The plain kernels below are `static`: this header is included by pairwise.hip, which launches them, and by kinship.hip.)
 // Sums the slabs pd_gram256p_kernel wrote for one launch into the 64-bit outputs: one thread per (tile pair, wave, MFMA tile, lane) = four
 // elements, over every K slice that exists.  slab layout: [xcd][slice][tile pair][wave][m][n][lane][4] int32.
-__global__ __launch_bounds__(256) void pd_slab_reduce_kernel(const int* __restrict__ slabs, uint32_t nt, uint32_t slices_per_xcd, size_t k_chunk, size_t s_pad,
+static __global__ __launch_bounds__(256) void pd_slab_reduce_kernel(const int* __restrict__ slabs, uint32_t nt, uint32_t slices_per_xcd, size_t k_chunk, size_t s_pad,
                                                              uint32_t n_samples, int negate, unsigned long long* __restrict__ out,
                                                              unsigned long long* __restrict__ totals) {
   const uint32_t tiles = nt * (nt + 1) / 2;
@@ -677,7 +678,7 @@ __global__ __launch_bounds__(256) void pd_slab_reduce_kernel(const int* __restri
 
 // Without missing data every genotype has `ploidy` alleles: sum over sites of len_i * len_j = rows * ploidy^2 and every
 // site counts for every pair, so those two Gram products collapse into constants.
-__global__ void pd_constant_terms_kernel(unsigned long long* __restrict__ diff, unsigned long long* __restrict__ both,
+static __global__ void pd_constant_terms_kernel(unsigned long long* __restrict__ diff, unsigned long long* __restrict__ both,
                                          uint32_t n_samples, unsigned long long add_diff, unsigned long long add_both) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t total = (size_t)n_samples * n_samples;
@@ -687,7 +688,7 @@ __global__ void pd_constant_terms_kernel(unsigned long long* __restrict__ diff, 
 }
 
 // Single-plane mode: diff(i, j) += ploidy*(T_i + T_j) - 2*G(i, j), both(i, j) += sites.
-__global__ void pd_single_plane_finish_kernel(unsigned long long* __restrict__ diff, unsigned long long* __restrict__ both,
+static __global__ void pd_single_plane_finish_kernel(unsigned long long* __restrict__ diff, unsigned long long* __restrict__ both,
                                               const unsigned long long* __restrict__ gram, const unsigned long long* __restrict__ totals,
                                               uint32_t n_samples, unsigned long long ploidy, unsigned long long sites) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

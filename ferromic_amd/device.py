@@ -613,6 +613,76 @@ def block_jackknife(num, den, weight=None) -> Dict[str, float]:
     return {name: getattr(out, name) for name, _ in _abi.JackknifeOut._fields_}
 
 
+# ---- relatedness: KING-robust kinship ------------------------------------------------------------------------------------------------
+KINSHIP_TABLES = ("both", "het_het", "ibs0", "het_hom")
+
+
+@dataclass
+class KinshipCounts:
+    both: np.ndarray      # [n][n] uint64 each
+    het_het: np.ndarray
+    ibs0: np.ndarray
+    het_hom: np.ndarray   # [i][j]: i het, j hom
+    kept_rows: int
+
+
+class KinshipBuffers:
+    """The four [n][n] u64 device tables fmh_kinship_counts ADDS into, zero (or `fill`) on creation."""
+
+    def __init__(self, device: int, n: int, fill: Optional[np.ndarray] = None):
+        self.device, self.n = device, int(n)
+        fill = np.zeros(self.n * self.n, dtype=np.uint64) if fill is None else np.ascontiguousarray(fill, dtype=np.uint64)
+        self.bufs = [DeviceBuffer.from_numpy(device, fill) for _ in KINSHIP_TABLES]  # (a blocking copy: safe before a call on any stream)
+        self.out = _abi.KinshipOut(*[b.ptr for b in self.bufs])
+
+    def tables(self):
+        return [b.to_numpy(np.uint64, self.n * self.n).reshape(self.n, self.n) for b in self.bufs]
+
+
+def kinship_counts(m: DeviceMatrix, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+                   into: Optional[KinshipBuffers] = None, stream=None) -> KinshipCounts:
+    """fmh_kinship_counts: the four genotype-class tables of the samples `samples` (ascending sample numbers; None = the first n_samples,
+    default all) over the rows of [row_begin, row_begin + row_count) that `keep` keeps (None = all).  `into`: accumulate into these buffers."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    bufs = into if into is not None else KinshipBuffers(m.device, n)
+    kept = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_kinship_counts(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), C.byref(bufs.out), C.byref(kept), stream))
+    both, het_het, ibs0, het_hom = bufs.tables()
+    return KinshipCounts(both, het_het, ibs0, het_hom, int(kept.value))
+
+
+def kinship_stats(both, het_het, ibs0, het_hom, ibs_distance: bool = True):
+    """fmh_kinship_stats (host only): (kinship, ibs_distance or None) as [n][n] float64 from the four tables."""
+    tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in (both, het_het, ibs0, het_hom)]
+    n = tables[0].shape[0]
+    if any(t.shape != (n, n) for t in tables):
+        raise ValueError("the four tables are [n][n]")
+    phi = np.empty((n, n), dtype=np.float64)
+    dist = np.empty((n, n), dtype=np.float64) if ibs_distance else None
+    _abi.check(_abi.load().fmh_kinship_stats(*[_ptr(t) for t in tables], n, _ptr(phi), _ptr(dist)))
+    return phi, dist
+
+
+def kinship_unrelated(kinship, threshold: float) -> np.ndarray:
+    """fmh_kinship_unrelated (host only): the greedy unrelated subset's keep flags, as bool."""
+    phi = np.ascontiguousarray(kinship, dtype=np.float64)
+    n = phi.shape[0]
+    if phi.shape != (n, n):
+        raise ValueError("kinship is [n][n]")
+    keep = np.zeros(n, dtype=np.uint8)
+    _abi.check(_abi.load().fmh_kinship_unrelated(_ptr(phi), n, float(threshold), _ptr(keep)))
+    return keep.astype(bool)
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

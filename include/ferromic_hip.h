@@ -577,6 +577,55 @@ int fmh_fstat_f4(const uint64_t* h_moments /* one block: [M] */, const uint64_t*
 int fmh_block_jackknife(const double* h_num, const double* h_den, const double* h_weight_or_null /* NULL = den */, size_t n_blocks,
                         fmh_jackknife_out* h_out);   /* host only, no device */
 
+/* ---- relatedness: KING-robust kinship from exact genotype-class tables (an addition: the reference has none) ---------------------------
+ * The matrix must have ploidy 2.  Sample s owns columns 2s and 2s+1.
+ * At row r, the genotype of s is CALLED (c_s(r) = 1) iff both entries are called and both alleles are <= 1.  An entry with a bit in an
+ * upper allele plane makes that genotype not called.  Nothing else about the row changes, so no row pre-filter is needed and a
+ * multi-allelic row still serves the samples that are 0/1 there.
+ * The dosage is g_s(r) in {0, 1, 2}.  Indicator rows over the kept rows are: H for g = 1; R for g = 0; A for g = 2; V = R + A; W = R - A.
+ * For samples i, j of the selected list, taken over the kept rows, four u64 tables, row-major [n][n]:
+ *   both[i][j]     #{c_i and c_j}.  Diagonal: called genotypes of i
+ *   het_het[i][j]  H_i . H_j.  Diagonal: het genotypes of i
+ *   ibs0[i][j]     R_i . A_j + A_i . R_j.  Diagonal 0
+ *   het_hom[i][j]  H_i . V_j.  NOT symmetric: [i][j] is "i het, j hom".  Diagonal 0
+ * All four tables are filled for every i, j, both triangles included.  The call ADDS into the caller's buffers, so chromosomes held as
+ * separate matrices of the same samples accumulate.  The caller zeroes the buffers first, as for fmh_pairwise_differences.
+ *
+ * Host estimators come from those integers, with the operation order fixed (the library is built with -ffp-contract=off, so numpy
+ * reproduces the values bit for bit):
+ *   het_i = het_het + het_hom[i][j], het_j = het_het + het_hom[j][i], m = min(het_i, het_j).
+ *   KING-robust kinship (Manichaikul et al. 2010, between-family form):
+ *     phi = 0.5 - (double)(het_hom[i][j] + het_hom[j][i] + 4*ibs0) / (double)(4*m).  It is a quiet NaN when m == 0.  On the diagonal this
+ *     gives 0.5, or NaN for a sample without a het call.
+ *   IBS distance: (double)(het_hom[i][j] + het_hom[j][i] + 2*ibs0) / (double)(2*both).  It is NaN when both == 0.
+ *   Unrelated subset (host, deterministic): repeat the following until no remaining pair has phi > threshold.  Count, for every remaining
+ *     sample, its remaining partners with phi > threshold.  Remove the sample with the largest count, taking the highest index on a tie.
+ *     NaN never exceeds the threshold.  (Partner j of i is read from h_kinship[i][j].)
+ *
+ * fmh_kinship_counts: samples = h_samples_or_null (ascending, distinct matrix sample numbers) or the first n_samples (a list that is
+ *   0 .. n_samples-1 is recognised and handled as NULL: no list is uploaded, the planes kernel copies row pieces instead of gathering); rows = those of
+ *   [row_begin, row_begin + row_count) whose h_keep_or_null byte is non-zero (NULL: all of them; the bytes are what fmh_ld_prune writes).
+ *   *h_kept_rows (may be NULL) receives the NUMBER of kept rows.  With no kept row the call returns FMH_OK and adds nothing.  The bits of
+ *   the allele planes under uncalled entries are undefined: every class is masked with the called plane.  Enqueues on `stream` and
+ *   synchronises it.  The tables come from self-Grams of class operand planes (H and V stacked with an all-ones row; W, signed) on the
+ *   matrix cores, through the Gram kernels and launcher of fmh_pairwise_differences: FMH_PD_INT8, FMH_PD_PHASED, FMH_PD_SLABS,
+ *   FMH_PD_SLAB_BYTES, FMH_PD_PLANES_BYTES and FMH_PD_KCHUNK apply.  W runs as signed FP4 (e2m1 code 0xA = -1) unless FMH_PD_INT8 is set.
+ *   Scratch: (2n+1)^2 * 8 + n^2 * 8 bytes (a matrix with a called plane or an upper allele plane) or 2 * n^2 * 8 bytes, from the pool, plus
+ *   the planes workspace; more than FMH_KIN_BUDGET_BYTES (default 16 GiB) is refused.
+ * Refusals, all before any launch.  FMH_ERR_INVALID: NULL matrix, NULL out or NULL table; n_samples == 0; a sample index out of range, or
+ *   the list not strictly ascending; a row range past the matrix.  FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix without a
+ *   packed image (u8 rows only: alleles >= 8, FMH_LAYOUT=bytes; call fmh_matrix_pack first); over budget.
+ * fmh_kinship_stats / fmh_kinship_unrelated: NULL argument (h_ibs_distance_or_null excepted) FMH_ERR_INVALID; n == 0 is FMH_OK.
+ * Not built: sharding over devices (the tables are plain sums over rows: a caller adds row slabs), run_vcf wiring, u8 rows.
+ */
+typedef struct { unsigned long long *d_both, *d_het_het, *d_ibs0, *d_het_hom; } fmh_kinship_out;  /* each [n][n], device, ADDED into */
+int fmh_kinship_counts(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */,
+                       size_t n_samples, size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count], as fmh_ld_prune writes it */,
+                       const fmh_kinship_out* out, uint64_t* h_kept_rows /* may be NULL */, void* stream);
+int fmh_kinship_stats(const uint64_t* h_both, const uint64_t* h_het_het, const uint64_t* h_ibs0, const uint64_t* h_het_hom, size_t n,
+                      double* h_kinship /* [n][n] */, double* h_ibs_distance_or_null);          /* host only, no device */
+int fmh_kinship_unrelated(const double* h_kinship, size_t n, double threshold, uint8_t* h_keep);  /* host only, no device */
+
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
  * A group is a 0/1 column mask with n >= 1 members (fmh_groups); members are ranked 0 .. n-1 by ascending column.  A window is a row range
@@ -851,6 +900,10 @@ int fmh_timing_reset_reduce(void);
  * the last fmh_pca_gram; [3] the kernel of the last fmh_pca_scan_sites; [4] the eigen solver of the last fmh_pca_eigen_scores
  * (rocsolver_dsyevd by events, the host solver by the host clock); [5] which solver that was (1 = host, 2 = rocSOLVER; set always). */
 int fmh_timing_read_pca(double* h_stage_ms /*[6]*/);
+/* A measurement aid (tools/measure_kinship.py), inert unless timing is enabled: stage times of the calling thread's last fmh_pairwise_differences or fmh_kinship_counts while timing was enabled, ms by HIP events,
+ * summed over the call's row slabs: [0] the planes kernels, [1] the first Gram of a slab with its slab reduce (pairwise: all its Grams;
+ * kinship: the stacked [H; V] or H operand), [2] the second Gram (kinship: W), [3] the finish kernel. */
+int fmh_timing_read_gram(double* h_stage_ms /*[4]*/);
 
 #ifdef __cplusplus
 }
