@@ -14,6 +14,7 @@ from ._core import (  # noqa: E402,F401
     FStatEstimate,
     FStatistics,
     FstEstimate,
+    GenotypeQC,
     HaplotypeScan,
     HaplotypeWindows,
     HudsonDxyResult,
@@ -32,6 +33,7 @@ from ._core import (  # noqa: E402,F401
     ehh_scan,
     f_statistics,
     garud_h,
+    genotype_qc,
     global_pca,
     hudson_dxy,
     hudson_fst,

@@ -119,6 +119,23 @@ class KinshipOut(C.Structure):
     _fields_ = [("d_both", C.c_void_p), ("d_het_het", C.c_void_p), ("d_ibs0", C.c_void_p), ("d_het_hom", C.c_void_p)]
 
 
+class GenotypeSiteOut(C.Structure):
+    _fields_ = [("d_hom_ref", C.c_void_p), ("d_het", C.c_void_p), ("d_hom_alt", C.c_void_p)]
+
+
+class GenotypeSampleOut(C.Structure):
+    _fields_ = [("d_hom_ref", C.c_void_p), ("d_het", C.c_void_p), ("d_hom_alt", C.c_void_p), ("d_weighted_called", C.c_void_p)]
+
+
+class GenotypeSiteStatsOut(C.Structure):
+    _fields_ = [("h_call_rate", C.c_void_p), ("h_alt_frequency", C.c_void_p), ("h_maf", C.c_void_p), ("h_f_is", C.c_void_p),
+                ("h_expected_het", C.c_void_p)]
+
+
+class GenotypeSampleStatsOut(C.Structure):
+    _fields_ = [("h_call_rate", C.c_void_p), ("h_het_rate", C.c_void_p), ("h_f", C.c_void_p)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -215,6 +232,12 @@ SYMBOLS = {
     "fmh_kinship_counts": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _P(KinshipOut), _P(_u64), _vp]),
     "fmh_kinship_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "fmh_kinship_unrelated": (_i, [_vp, _sz, _d, _vp]),
+    "fmh_genotype_counts": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(GenotypeSiteOut), _P(GenotypeSampleOut), _P(_u64), _vp]),
+    "fmh_hwe_exact": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _vp]),
+    "fmh_hwe_exact_host": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "fmh_genotype_site_stats": (_i, [_vp, _vp, _vp, _sz, _u64, _P(GenotypeSiteStatsOut)]),
+    "fmh_genotype_site_weights": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "fmh_genotype_sample_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _u64, _P(GenotypeSampleStatsOut)]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

@@ -911,6 +911,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_ehh.inc"
 #include "pymodule_fstat.inc"
 #include "pymodule_kinship.inc"
+#include "pymodule_qc.inc"
 
 }  // namespace
 
@@ -1030,6 +1031,7 @@ PYBIND11_MODULE(_core, m) {
       .def("ld_r2", &population_ld_r2, py::arg("max_sites_apart"))
       .def("ld_prune", &population_ld_prune, py::arg("window_sites"), py::arg("r2_threshold"))
       .def("kinship", &population_kinship, py::arg("sites") = py::none())
+      .def("genotype_qc", &population_genotype_qc, py::arg("sites") = py::none(), py::arg("hwe") = true, py::arg("inbreeding") = true)
       .def("site_frequency_spectrum", &population_sfs, py::arg("windows") = py::none())
       .def("garud_h", &population_garud_h, py::arg("windows") = py::none(), py::arg("size") = py::none(), py::arg("step") = py::none(),
            py::arg("partition") = false)
@@ -1057,6 +1059,7 @@ PYBIND11_MODULE(_core, m) {
   bind_ehh(m, population);
   bind_fstat(m);
   bind_kinship(m);
+  bind_qc(m);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

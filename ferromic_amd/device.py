@@ -683,6 +683,128 @@ def kinship_unrelated(kinship, threshold: float) -> np.ndarray:
     return keep.astype(bool)
 
 
+# ---- genotype QC: class counts per site and per sample, HWE exact test -----------------------------------------------------------------
+QC_DEFAULT_ITEM_ROWS = 4096   # FMH_QC_ITEM_ROWS unset
+QC_CLASSES = ("hom_ref", "het", "hom_alt")
+QC_SITE_STATS = ("call_rate", "alt_frequency", "maf", "f_is", "expected_het")
+QC_SAMPLE_STATS = ("call_rate", "het_rate", "f")
+
+
+@dataclass
+class GenotypeCounts:
+    site: Optional[Dict[str, np.ndarray]]      # hom_ref, het, hom_alt: [row_count] uint32 (a track not asked for is absent), or None
+    sample: Optional[Dict[str, np.ndarray]]    # hom_ref, het, hom_alt and / or weighted_called: [n] uint64, or None
+    kept_rows: int
+
+
+class GenotypeSampleBuffers:
+    """The [n] u64 device tables fmh_genotype_counts ADDS into, zero (or `fill`) on creation; `names` picks the tables that exist."""
+
+    def __init__(self, device: int, n: int, names=QC_CLASSES, fill: Optional[np.ndarray] = None):
+        self.device, self.n, self.names = device, int(n), tuple(names)
+        fill = np.zeros(self.n, dtype=np.uint64) if fill is None else np.ascontiguousarray(fill, dtype=np.uint64)
+        self.bufs = {name: DeviceBuffer.from_numpy(device, fill) for name in self.names}
+        self.out = _abi.GenotypeSampleOut(*[self.bufs[k].ptr if k in self.bufs else None for k in QC_CLASSES + ("weighted_called",)])
+
+    def tables(self) -> Dict[str, np.ndarray]:
+        return {name: b.to_numpy(np.uint64, self.n) for name, b in self.bufs.items()}
+
+
+def genotype_counts(m: DeviceMatrix, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+                    weights=None, site=QC_CLASSES, sample=QC_CLASSES, into: Optional[GenotypeSampleBuffers] = None, stream=None,
+                    fill: Optional[int] = None) -> GenotypeCounts:
+    """fmh_genotype_counts over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all).  `site` / `sample`: the names of the tracks / tables to compute (empty or None: that side's pointer is NULL);
+    `weights` [rows] uint32 adds the table weighted_called.  `keep` [rows] restricts the sample tables.  `into`: accumulate into these
+    buffers.  `fill` pre-fills the site tracks with that byte (tests: the call must write every entry)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        if weights.size != rows:
+            raise ValueError("weights has one entry per row of the range")
+    site, sample = tuple(site or ()), tuple(sample or ())
+    tracks = {name: (DeviceBuffer(m.device, max(4 * rows, 4)) if fill is None else
+                     DeviceBuffer.from_numpy(m.device, np.full(max(4 * rows, 4), fill, dtype=np.uint8))) for name in site}
+    site_out = _abi.GenotypeSiteOut(*[tracks[k].ptr if k in tracks else None for k in QC_CLASSES])
+    bufs = into
+    if bufs is None and (sample or weights is not None):
+        bufs = GenotypeSampleBuffers(m.device, n, sample + (("weighted_called",) if weights is not None else ()))
+    kept = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_genotype_counts(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(weights), C.byref(site_out) if tracks else None,
+                                               C.byref(bufs.out) if bufs is not None else None, C.byref(kept), stream))
+    site_np = {name: t.to_numpy(np.uint32, rows) for name, t in tracks.items()} if tracks else None
+    return GenotypeCounts(site_np, None if bufs is None else bufs.tables(), int(kept.value))
+
+
+def hwe_exact(m_device: int, hom_ref, het, hom_alt, stream=None) -> np.ndarray:
+    """fmh_hwe_exact: the exact-test p of every site on device `m_device` from the three uint32 count arrays."""
+    arrays = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    n = arrays[0].size
+    if any(a.size != n for a in arrays):
+        raise ValueError("the three count arrays have one entry per site")
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    bufs = [DeviceBuffer.from_numpy(m_device, a) for a in arrays]
+    d_p = DeviceBuffer(m_device, 8 * n)
+    _abi.check(_abi.load().fmh_hwe_exact(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n, d_p.ptr, m_device, stream))
+    return d_p.to_numpy(np.float64, n)
+
+
+def _site_counts(hom_ref, het, hom_alt):
+    arrays = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    if any(a.size != arrays[0].size for a in arrays):
+        raise ValueError("the three count arrays have one entry per site")
+    return arrays
+
+
+def hwe_exact_host(hom_ref, het, hom_alt) -> np.ndarray:
+    """fmh_hwe_exact_host (host only): the same function as the device's, on host arrays."""
+    arrays = _site_counts(hom_ref, het, hom_alt)
+    p = np.zeros(arrays[0].size, dtype=np.float64)
+    _abi.check(_abi.load().fmh_hwe_exact_host(*[_ptr(a) for a in arrays], p.size, _ptr(p)))
+    return p
+
+
+def genotype_site_stats(hom_ref, het, hom_alt, n_samples: int) -> Dict[str, np.ndarray]:
+    """fmh_genotype_site_stats (host only): call_rate, alt_frequency, maf, f_is and expected_het per site."""
+    arrays = _site_counts(hom_ref, het, hom_alt)
+    out = {name: np.zeros(arrays[0].size, dtype=np.float64) for name in QC_SITE_STATS}
+    ptrs = _abi.GenotypeSiteStatsOut(*[out[name].ctypes.data for name in QC_SITE_STATS])
+    _abi.check(_abi.load().fmh_genotype_site_stats(*[_ptr(a) for a in arrays], arrays[0].size, int(n_samples), C.byref(ptrs)))
+    return out
+
+
+def genotype_site_weights(hom_ref, het, hom_alt) -> np.ndarray:
+    """fmh_genotype_site_weights (host only): w = rint(e * 2^31) per site, the row weights of the inbreeding coefficient."""
+    arrays = _site_counts(hom_ref, het, hom_alt)
+    w = np.zeros(arrays[0].size, dtype=np.uint32)
+    _abi.check(_abi.load().fmh_genotype_site_weights(*[_ptr(a) for a in arrays], w.size, _ptr(w)))
+    return w
+
+
+def genotype_sample_stats(hom_ref, het, hom_alt, kept_rows: int, weighted_called=None) -> Dict[str, np.ndarray]:
+    """fmh_genotype_sample_stats (host only): call_rate and het_rate per sample, and f when the weighted called sums are given."""
+    arrays = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    n = arrays[0].size
+    weighted = None if weighted_called is None else np.ascontiguousarray(weighted_called, dtype=np.uint64).reshape(-1)
+    if any(a.size != n for a in arrays) or (weighted is not None and weighted.size != n):
+        raise ValueError("the tables have one entry per sample")
+    names = QC_SAMPLE_STATS if weighted is not None else QC_SAMPLE_STATS[:2]
+    out = {name: np.zeros(n, dtype=np.float64) for name in names}
+    ptrs = _abi.GenotypeSampleStatsOut(*[out[name].ctypes.data if name in out else None for name in QC_SAMPLE_STATS])
+    _abi.check(_abi.load().fmh_genotype_sample_stats(*[_ptr(a) for a in arrays], _ptr(weighted), n, int(kept_rows), C.byref(ptrs)))
+    return out
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -77,6 +77,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
+ *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -625,6 +626,86 @@ int fmh_kinship_counts(const fmh_matrix* m, const uint32_t* h_samples_or_null /*
 int fmh_kinship_stats(const uint64_t* h_both, const uint64_t* h_het_het, const uint64_t* h_ibs0, const uint64_t* h_het_hom, size_t n,
                       double* h_kinship /* [n][n] */, double* h_ibs_distance_or_null);          /* host only, no device */
 int fmh_kinship_unrelated(const double* h_kinship, size_t n, double threshold, uint8_t* h_keep);  /* host only, no device */
+
+/* ---- genotype QC: per-site and per-sample genotype class counts, Hardy-Weinberg exact test (an addition: the reference has none) --------
+ * The first step of the cohort chain QC -> fmh_ld_prune -> fmh_kinship_counts -> PCA.
+ * The matrix must have ploidy 2 and a packed image.  Sample s owns columns 2s and 2s+1.  c_s(r) ("called") and g_s(r) in {0, 1, 2}
+ * ("dosage") are fmh_kinship_counts': the genotype of s at row r is called iff both entries are called and both alleles are <= 1.  The bits
+ * of the allele planes under uncalled entries are undefined: every class is masked with the called plane.
+ * The selected samples are h_samples_or_null (strictly ascending, distinct matrix sample numbers), or the first n_samples when it is NULL;
+ * n = n_samples.
+ *
+ * Site tracks (fmh_genotype_site_out).  For every row of [row_begin, row_begin + row_count) three u32: hom_ref, het, hom_alt = the number of
+ *   selected samples with c = 1 and g = 0, 1, 2.  Structure-of-arrays device buffers [row_count], WRITTEN (not added).  The keep mask does
+ *   not apply to them: a filter is derived from them.
+ * Sample tables (fmh_genotype_sample_out).  For every selected sample, at its position in the list, three u64: hom_ref, het, hom_alt = the
+ *   number of rows of the range whose h_keep_or_null byte is non-zero (NULL: every row; the bytes are what fmh_ld_prune writes) at which the
+ *   sample has c = 1 and g = 0, 1, 2.  Device buffers [n], ADDED into, as fmh_kinship_counts' tables are: chromosomes held as separate
+ *   matrices of the same samples accumulate; the caller zeroes the buffers first.
+ * Weighted called sum (optional).  With h_row_weight_or_null (u32 [row_count], any values) the call adds
+ *   sum over the kept rows r of w_r * c_s(r)  into d_weighted_called (u64 [n]), exactly.  The per-sample inbreeding coefficient needs the sum
+ *   of a real-valued per-site expectation e_r over the sites where the sample is called; the host hands it over as fixed point,
+ *   w_r = rint(e_r * 2^31) with e_r in [0, 1] (fmh_genotype_site_weights), so that the device sum stays an exact integer.
+ * Every output pointer may be NULL and that output is then not computed: with no site pointer no track is written and no row reduction is
+ *   paid for; with no sample pointer no vertical counter is kept.  *h_kept_rows (may be NULL) receives the number of kept rows.  With no
+ *   kept row nothing is added to the sample buffers and the call is FMH_OK.  Enqueues on `stream` and synchronises it.
+ * Refusals, all before any launch.  FMH_ERR_INVALID: NULL matrix; n_samples == 0; a sample index out of range, or the list not strictly
+ *   ascending; a row range past the matrix; every output NULL; row weights without d_weighted_called, or the reverse.  FMH_ERR_UNSUPPORTED,
+ *   with a message: ploidy != 2; a matrix without a packed image (u8 rows only: call fmh_matrix_pack first).
+ * Option: FMH_QC_ITEM_ROWS = the most rows of a work item (default 4 096).  It changes no result, nor do FMH_GRID_PER_CU and FMH_GRID_BLOCKS.
+ *
+ * Hardy-Weinberg exact test (Wigginton, Cutler & Abecasis 2005), array-free.  This is the DEFINITION; device, host twin and a plain Python
+ * loop over floats agree bit for bit (the library is built with -ffp-contract=off; f64 division and subnormals are IEEE):
+ *   N = hom_ref + het + hom_alt.  N == 0: a quiet NaN.
+ *   rare = 2 * min(hom_ref, hom_alt) + het, common = 2N - rare.  rare == 0: 1.0.
+ *   mid = rare * common / (2N) in u64 integer division, + 1 if its parity differs from rare's.  The relative weight at mid is t = 1.0.
+ *   Walking DOWN (x = mid, r = (rare - mid) / 2, c = N - x - r; while x >= 2):
+ *     t = (t * (double)(x * (x - 1))) / (double)(4 * (r + 1) * (c + 1)), then x -= 2, r += 1, c += 1: t is the weight at the new x.
+ *   Walking UP from mid again with t = 1.0 (while x + 2 <= rare):
+ *     t = (t * (double)(4 * r * c)) / (double)((x + 2) * (x + 1)), then x += 2, r -= 1, c -= 1.
+ *   The integer products are formed in u64 and converted; they stay below 2^53 while N <= 2^26.
+ *   Pass 1: S = the sum of all weights in the order mid, down, up (starting from 0.0); t_obs = the weight at x == het (0.0 if never met).
+ *   Pass 2: the same walk; P = the sum, in that order, of the weights with t <= t_obs.
+ *   p = P / S, replaced by 1.0 if greater.  A walk stops once t == 0.0: every later term is zero too.
+ *   A site with N > 2^26: fmh_hwe_exact_host refuses the call (FMH_ERR_UNSUPPORTED); fmh_hwe_exact, which cannot look before its launch,
+ *   writes a quiet NaN there.
+ * fmh_hwe_exact: one thread per site, d_p[i] from the three device tracks; enqueues on `stream` and synchronises it.  n_sites == 0 is FMH_OK;
+ *   a NULL pointer FMH_ERR_INVALID.  fmh_hwe_exact_host: the same function on host arrays, no device.
+ *
+ * Host estimators (no device), the operation order fixed; a quiet NaN results where a denominator is 0.
+ *   Site (fmh_genotype_site_stats): n_alt = 2 * hom_alt + het, n_ref = 2N - n_alt.
+ *     call_rate = (double)N / (double)n_samples      alt_frequency p = (double)n_alt / (double)(2N)      maf = min(p, 1.0 - p)
+ *     f_is = 1.0 - (double)(het * (2N - 1)) / (double)(n_alt * n_ref)
+ *     expected_het = (double)(n_alt * n_ref) / (double)(2N - 1): the unbiased HWE-expected het COUNT, an integer ratio with one division.
+ *   Weights (fmh_genotype_site_weights): e = (double)(n_alt * n_ref) / (double)(N * (2N - 1)), 0.0 where N == 0; w = rint(e * 2^31) as u32
+ *     (e <= N / (2N - 1) <= 1, so w <= 2^31).
+ *   Sample (fmh_genotype_sample_stats): called = hom_ref + het + hom_alt.
+ *     call_rate = (double)called / (double)kept_rows      het_rate = (double)het / (double)called
+ *     F = 1.0 - (double)het / ((double)weighted_called / 2^31): PLINK's --het method-of-moments F with the expectation taken over the
+ *     sample's own called sites.
+ *   Each output pointer of the two _out structs may be NULL.  A site with N >= 2^31 is refused (FMH_ERR_UNSUPPORTED: the products would
+ *   leave a u64); a NULL input FMH_ERR_INVALID (h_weighted_called_or_null may be NULL when h_f is); zero sites / samples is FMH_OK.
+ * Not built: sharding over devices (the tables are plain sums over rows: a caller adds row slabs), run_vcf wiring, u8 rows, the mid-p and
+ *   X-chromosome variants of the test, a `sites` pre-filter argument for fmh_ld_prune.
+ */
+typedef struct { uint32_t *d_hom_ref, *d_het, *d_hom_alt; } fmh_genotype_site_out;   /* each [row_count], device, written; any may be NULL */
+typedef struct { unsigned long long *d_hom_ref, *d_het, *d_hom_alt, *d_weighted_called; } fmh_genotype_sample_out;  /* each [n], device, ADDED into; any may be NULL */
+int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */,
+                        size_t n_samples, size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count], as fmh_ld_prune writes it */,
+                        const uint32_t* h_row_weight_or_null /* [row_count] */, const fmh_genotype_site_out* site_or_null,
+                        const fmh_genotype_sample_out* sample_or_null, uint64_t* h_kept_rows /* may be NULL */, void* stream);
+int fmh_hwe_exact(const uint32_t* d_hom_ref, const uint32_t* d_het, const uint32_t* d_hom_alt, size_t n_sites, double* d_p, int device,
+                  void* stream);
+int fmh_hwe_exact_host(const uint32_t* h_hom_ref, const uint32_t* h_het, const uint32_t* h_hom_alt, size_t n_sites, double* h_p);  /* no device */
+typedef struct { double *h_call_rate, *h_alt_frequency, *h_maf, *h_f_is, *h_expected_het; } fmh_genotype_site_stats_out;  /* each [n_sites] or NULL */
+int fmh_genotype_site_stats(const uint32_t* h_hom_ref, const uint32_t* h_het, const uint32_t* h_hom_alt, size_t n_sites, uint64_t n_samples,
+                            const fmh_genotype_site_stats_out* out);   /* host only, no device */
+int fmh_genotype_site_weights(const uint32_t* h_hom_ref, const uint32_t* h_het, const uint32_t* h_hom_alt, size_t n_sites,
+                              uint32_t* h_weight);   /* host only, no device */
+typedef struct { double *h_call_rate, *h_het_rate, *h_f; } fmh_genotype_sample_stats_out;  /* each [n] or NULL */
+int fmh_genotype_sample_stats(const uint64_t* h_hom_ref, const uint64_t* h_het, const uint64_t* h_hom_alt,
+                              const uint64_t* h_weighted_called_or_null, size_t n, uint64_t kept_rows,
+                              const fmh_genotype_sample_stats_out* out);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
