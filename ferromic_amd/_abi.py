@@ -29,6 +29,7 @@ MAX_PAIRS = 28
 HUDSON_PACK_F64 = 10
 HUDSON_PACK_U64 = 10
 COMM_ID_BYTES = 128
+STREAM_PER_THREAD = 2  # FMH_STREAM_PER_THREAD: the calling thread's own stream, wherever a `stream` is taken (None = the NULL stream)
 
 WC_STATES = (
     "calculable",

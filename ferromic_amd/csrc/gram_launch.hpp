@@ -18,8 +18,13 @@ struct GramFormat {
   int layout;
   size_t spb;     // sites per byte of a plane row
   size_t ksites;  // sites per K block = per Gram stage
+  // the options gram_plan sizes a launch by, as they stood when the call began: a call plans once per row slab and operand region, and
+  // another thread may call fmh_set_option between two of its plans
+  long long occ_cap, kchunk, slabs, slab_bytes;  // FMH_PD_OCC, FMH_PD_KCHUNK, FMH_PD_SLABS, FMH_PD_SLAB_BYTES
+  long long sb;                                  // FMH_PD_SB: samples per workgroup of the u8 planes kernel (pairwise only)
 };
-// fp4_exact: every operand value of the call is exact in e2m1 (pairwise: counts up to ploidy <= 4; kinship: -1, 0, 1)
+// fp4_exact: every operand value of the call is exact in e2m1 (pairwise: counts up to ploidy <= 4; kinship: -1, 0, 1).  One snapshot of
+// the FMH_PD_* options per call: every later decision of the call (gram_row_slab aside, which reads its one option once) comes from it.
 inline GramFormat gram_format(bool fp4_exact) {
   GramFormat f;
   f.fp4 = fp4_exact && options().pd_int8.load() == 0;  // FMH_PD_INT8: measurements / tests, the int8 route
@@ -28,6 +33,11 @@ inline GramFormat gram_format(bool fp4_exact) {
   f.layout = f.phased ? 1 : 0;
   f.spb = f.fp4 ? 2 : 1;
   f.ksites = fmh::kPdStageK * f.spb;
+  f.occ_cap = options().pd_occ.load();
+  f.kchunk = options().pd_kchunk.load();
+  f.slabs = options().pd_slabs.load();
+  f.slab_bytes = options().pd_slab_bytes.load();
+  f.sb = options().pd_sb.load();
   return f;
 }
 

@@ -44,9 +44,9 @@ extern "C" int fmh_kinship_counts(const fmh_matrix* m, const uint32_t* h_samples
   // (n <= 2^28 first: (2n + 1)^2 * 8 + n^2 * 8 then stays below 2^62 and cannot wrap)
   if (n > ((size_t)1 << 28)) return fail(FMH_ERR_UNSUPPORTED, "kinship of %zu samples: more than 2^28 samples are not supported", n);
   const size_t scratch_bytes = general ? (2 * n + 1) * (2 * n + 1) * 8 + n * n * 8 : 2 * n * n * 8;
-  if (scratch_bytes > (size_t)options().kin_budget_bytes.load())
-    return fail(FMH_ERR_UNSUPPORTED, "kinship of %zu samples needs %zu bytes of scratch, above FMH_KIN_BUDGET_BYTES = %lld", n, scratch_bytes,
-                options().kin_budget_bytes.load());
+  const long long budget = options().kin_budget_bytes.load();
+  if (scratch_bytes > (size_t)budget)
+    return fail(FMH_ERR_UNSUPPORTED, "kinship of %zu samples needs %zu bytes of scratch, above FMH_KIN_BUDGET_BYTES = %lld", n, scratch_bytes, budget);
   FMH_TRY(use_device(m->device));
   // the kept rows: every row of the range, or those the mask keeps (as a list the planes kernel gathers through)
   std::vector<unsigned long long> kept_list;

@@ -44,8 +44,9 @@ hipError_t gram_plan(Workspace* w, int device, const GramFormat& f, size_t n_pad
     if (oe != hipSuccess || occ < 1) occ = 1;
     gram_occ[device][fp4] = occ;
   }
-  // FMH_PD_OCC is read on every call (the hardware's answer above is what is kept), so fmh_set_option takes effect in a running process
-  const int env_occ = (int)options().pd_occ.load();
+  // FMH_PD_OCC is read on every call (the hardware's answer above is what is kept), so fmh_set_option takes effect in a running process;
+  // like the other FMH_PD_* options it comes from the call's snapshot (gram_format), not from a fresh read per plan
+  const int env_occ = (int)f.occ_cap;
   const int occ_now = env_occ > 0 && gram_occ[device][fp4] > env_occ ? env_occ : gram_occ[device][fp4];
   static thread_local bool phased_ready[64][2];
   if (phased && !phased_ready[device][fp4]) {
@@ -56,7 +57,7 @@ hipError_t gram_plan(Workspace* w, int device, const GramFormat& f, size_t n_pad
   // persistent: every workgroup resident (the phased kernel's two K tiles of LDS leave one workgroup per CU)
   p.grid = phased ? (unsigned)std::max(8, w->cus / 8 * 8) : (unsigned)std::max(8, w->cus * occ_now / 8 * 8);
   const size_t slots = p.grid / 8;
-  const size_t env_chunk = (size_t)options().pd_kchunk.load();
+  const size_t env_chunk = (size_t)f.kchunk;
   size_t j = env_chunk ? std::max<size_t>(1, (k_bytes + 8 * env_chunk - 1) / (8 * env_chunk)) : std::max<size_t>(1, (slots * 8 + p.tiles - 1) / p.tiles);
   const size_t cap_sites = (fp4 ? ((size_t)1 << 24) : (((size_t)1 << 31) - 1)) / max_product;
   const size_t k_cap = std::max<size_t>(cap_sites / f.spb / kPdStageK, 1) * kPdStageK;
@@ -69,9 +70,9 @@ hipError_t gram_plan(Workspace* w, int device, const GramFormat& f, size_t n_pad
   p.k_chunk = k_chunk;
   // the phased kernel writes every item's partial tile as a plain slab and a second kernel sums the slabs (no atomics) when the slabs fit the budget
   p.use_slabs = false;
-  if (phased && options().pd_slabs.load() != 0) {
+  if (phased && f.slabs != 0) {
     const size_t slab_bytes = p.tiles * 8 * j * (size_t)kPdBig * kPdBig * sizeof(int);
-    if (slab_bytes <= (size_t)options().pd_slab_bytes.load()) {
+    if (slab_bytes <= (size_t)f.slab_bytes) {
       if (w->pd_slab_bytes < slab_bytes) {
         // (hipFree waits for the device: a Gram enqueued earlier that still writes the old block has finished)
         if (w->pd_slabs) (void)hipFree(w->pd_slabs);
@@ -216,7 +217,7 @@ extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, u
       // samples per planes workgroup: the tile's raw bytes (one K block of sites x sb x ploidy) stay within 32 KiB of LDS, so
       // four workgroups share a CU and one's loads overlap another's packing (measured, 1 M x 2 500 FP4: 64 KiB tiles 1.94 ms,
       // 32 KiB 1.76 ms, 16 KiB 1.97 ms)
-      const uint32_t env_sb = (uint32_t)options().pd_sb.load();  // measurements
+      const uint32_t env_sb = (uint32_t)gf.sb;  // measurements
       uint32_t sb = env_sb ? env_sb : kPdBlock;
       while ((size_t)sb * m->ploidy * ksites > 32 * 1024 && sb > 4) sb /= 2;
       const size_t planes_smem = ksites * ((size_t)sb * m->ploidy + ((size_t)sb * m->ploidy + 7) / 8 + 1);

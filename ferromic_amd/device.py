@@ -230,7 +230,7 @@ class SummaryResult:
 
 
 def population_summaries(m: DeviceMatrix, g: Groups, formula: int = FORMULA_SUMMARY, row_begin: int = 0,
-                         row_count: Optional[int] = None, want_sites: bool = True) -> SummaryResult:
+                         row_count: Optional[int] = None, want_sites: bool = True, stream=None) -> SummaryResult:
     rows = m.variants - row_begin if row_count is None else row_count
     P = g.n_groups
     d_alt = DeviceBuffer(m.device, 4 * P * rows) if want_sites else None
@@ -238,7 +238,7 @@ def population_summaries(m: DeviceMatrix, g: Groups, formula: int = FORMULA_SUMM
     totals = (_abi.PopTotals * P)()
     _abi.check(_abi.load().fmh_population_summaries(m._h, g._h, row_begin, rows, formula,
                                                     d_alt.ptr if d_alt else None, d_called.ptr if d_called else None,
-                                                    totals, None))
+                                                    totals, stream))
     alt = d_alt.to_numpy(np.uint32, P * rows).reshape(P, rows) if want_sites else None
     called = d_called.to_numpy(np.uint32, P * rows).reshape(P, rows) if want_sites else None
     return SummaryResult([_pop_totals(totals[p]) for p in range(P)], alt, called)
@@ -257,7 +257,7 @@ def hudson_totals_dict(t: _abi.HudsonTotals) -> Dict[str, float]:
 
 
 def hudson_sweep(m: DeviceMatrix, g: Groups, formula: int, row_begin: int = 0, row_count: Optional[int] = None,
-                 want_sites: bool = True) -> HudsonResult:
+                 want_sites: bool = True, stream=None) -> HudsonResult:
     rows = m.variants - row_begin if row_count is None else row_count
     bufs = {}
     sites = None
@@ -269,7 +269,7 @@ def hudson_sweep(m: DeviceMatrix, g: Groups, formula: int, row_begin: int = 0, r
         sites = _abi.HudsonSites(*(bufs[n].ptr for n in ("fst", "dxy", "pi1", "pi2", "num", "den", "alt", "called")))
     totals = _abi.HudsonTotals()
     _abi.check(_abi.load().fmh_hudson_sweep(m._h, g._h, row_begin, rows, formula,
-                                            C.byref(sites) if sites is not None else None, C.byref(totals), None))
+                                            C.byref(sites) if sites is not None else None, C.byref(totals), stream))
     out_sites = None
     if want_sites:
         out_sites = {n: bufs[n].to_numpy(np.float64, rows) for n in ("fst", "dxy", "pi1", "pi2", "num", "den")}
@@ -374,15 +374,16 @@ def wc_sweep_many(m: DeviceMatrix, masks: np.ndarray, row_begin: int = 0, row_co
                     d_n.to_numpy(np.uint32, G * rows).reshape(G, rows))
 
 
-def pairwise_differences(m: DeviceMatrix, n_samples: int):
-    """fmh_pairwise_differences -> (diff, both) as [n, n] uint64 arrays (upper triangle filled)."""
+def pairwise_differences(m: DeviceMatrix, n_samples: int, stream=None):
+    """fmh_pairwise_differences -> (diff, both) as [n, n] uint64 arrays (upper triangle filled).  The accumulators are zeroed on the
+    stream the call runs on: fmh_device_zero does not synchronise, and a stream of the caller's is not ordered behind the NULL stream."""
     n = int(n_samples)
     d_diff, d_both = DeviceBuffer(m.device, 8 * n * n), DeviceBuffer(m.device, 8 * n * n)
     lib = _abi.load()
     if n:
-        _abi.check(lib.fmh_device_zero(m.device, d_diff.ptr, 8 * n * n, None))
-        _abi.check(lib.fmh_device_zero(m.device, d_both.ptr, 8 * n * n, None))
-    _abi.check(lib.fmh_pairwise_differences(m._h, n, d_diff.ptr, d_both.ptr, None))
+        _abi.check(lib.fmh_device_zero(m.device, d_diff.ptr, 8 * n * n, stream))
+        _abi.check(lib.fmh_device_zero(m.device, d_both.ptr, 8 * n * n, stream))
+    _abi.check(lib.fmh_pairwise_differences(m._h, n, d_diff.ptr, d_both.ptr, stream))
     return d_diff.to_numpy(np.uint64, n * n).reshape(n, n), d_both.to_numpy(np.uint64, n * n).reshape(n, n)
 
 
@@ -463,7 +464,7 @@ class LdBandResult:
 
 
 def ld_band(m: DeviceMatrix, g: Optional[Groups], band: int, threshold: float = 0.0, row_begin: int = 0, row_count: Optional[int] = None,
-            partner_end: Optional[int] = None, want=("r2", "n_ab", "n_joint", "over", "site_n", "site_alt")) -> LdBandResult:
+            partner_end: Optional[int] = None, want=("r2", "n_ab", "n_joint", "over", "site_n", "site_alt"), stream=None) -> LdBandResult:
     """fmh_ld_band: r^2 and its counts between rows [row_begin, row_begin + row_count) and their next `band` rows below partner_end
     (default: the end of the rows asked for); `want` names the outputs to ask for."""
     rows = m.variants - row_begin if row_count is None else row_count
@@ -473,7 +474,7 @@ def ld_band(m: DeviceMatrix, g: Optional[Groups], band: int, threshold: float = 
     bufs = {k: DeviceBuffer(m.device, max(sizes[k], 4)) for k in want}
     out = _abi.LdBandOut(*(bufs[k].ptr if k in bufs else None for k in ("r2", "n_ab", "n_joint", "over")))
     _abi.check(_abi.load().fmh_ld_band(m._h, g._h if g is not None else None, row_begin, rows, pend, band, float(threshold), C.byref(out),
-                                       bufs["site_n"].ptr if "site_n" in bufs else None, bufs["site_alt"].ptr if "site_alt" in bufs else None, None))
+                                       bufs["site_n"].ptr if "site_n" in bufs else None, bufs["site_alt"].ptr if "site_alt" in bufs else None, stream))
 
     def fetch(k, dtype, shape):
         return bufs[k].to_numpy(dtype, int(np.prod(shape))).reshape(shape) if k in bufs else None
@@ -483,12 +484,12 @@ def ld_band(m: DeviceMatrix, g: Optional[Groups], band: int, threshold: float = 
 
 
 def ld_prune(m: DeviceMatrix, g: Optional[Groups], window: int, threshold: float, row_begin: int = 0, row_count: Optional[int] = None,
-             chunk_rows: int = 0) -> np.ndarray:
+             chunk_rows: int = 0, stream=None) -> np.ndarray:
     """fmh_ld_prune (fmh_ld_prune_chunked when chunk_rows is given): the forward greedy keep flags of the rows, as bool."""
     rows = m.variants - row_begin if row_count is None else row_count
     keep = np.zeros(rows, dtype=np.uint8)
     _abi.check(_abi.load().fmh_ld_prune_chunked(m._h, g._h if g is not None else None, row_begin, rows, int(window), float(threshold), _ptr(keep),
-                                                int(chunk_rows), None))
+                                                int(chunk_rows), stream))
     return keep.astype(bool)
 
 
@@ -526,24 +527,24 @@ def _skipped_arrays(skipped, count: int):
     return flat[:, 0].copy(), flat[:, 1].copy()
 
 
-def sfs(m: DeviceMatrix, g: Groups, windows=None) -> SfsResult:
+def sfs(m: DeviceMatrix, g: Groups, windows=None, stream=None) -> SfsResult:
     """fmh_sfs: the 1-D spectra of the one group of `g` over row windows [(begin, end), ...] (default: one window, every row)."""
     w = np.array([[0, m.variants]] if windows is None else windows, dtype=np.uint64).reshape(-1, 2)
     n_windows, width = w.shape[0], g.sizes[0] + 1
     skipped = (_abi.SfsSkipped * max(n_windows, 1))()
     d_sfs = DeviceBuffer(m.device, max(8 * n_windows * width, 8))
-    _abi.check(_abi.load().fmh_sfs(m._h, g._h, _ptr(w), n_windows, d_sfs.ptr, skipped, None))
+    _abi.check(_abi.load().fmh_sfs(m._h, g._h, _ptr(w), n_windows, d_sfs.ptr, skipped, stream))
     multi, incomplete = _skipped_arrays(skipped, n_windows)
     return SfsResult(d_sfs.to_numpy(np.uint64, n_windows * width).reshape(n_windows, width), multi, incomplete)
 
 
-def sfs_joint(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None) -> SfsJointResult:
+def sfs_joint(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None, stream=None) -> SfsJointResult:
     """fmh_sfs_joint: the joint spectrum [n0 + 1][n1 + 1] of the two groups of `g` over rows [row_begin, row_begin + row_count)."""
     rows = m.variants - row_begin if row_count is None else row_count
     shape = (g.sizes[0] + 1, g.sizes[1] + 1) if g.n_groups == 2 else (1, 1)
     skipped = (_abi.SfsSkipped * 1)()
     d_sfs = DeviceBuffer(m.device, 8 * shape[0] * shape[1])
-    _abi.check(_abi.load().fmh_sfs_joint(m._h, g._h, row_begin, rows, d_sfs.ptr, skipped, None))
+    _abi.check(_abi.load().fmh_sfs_joint(m._h, g._h, row_begin, rows, d_sfs.ptr, skipped, stream))
     return SfsJointResult(d_sfs.to_numpy(np.uint64, shape[0] * shape[1]).reshape(shape), int(skipped[0].multiallelic), int(skipped[0].incomplete))
 
 

@@ -15,6 +15,10 @@
  *     through fmh_last_error().
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Calls that fill host
  *     totals synchronise that stream before returning.
+ *   - host threads: every function may be called from several threads at once, on one device or several; matrix and groups handles
+ *     may be shared by calls that only read them (every statistic), while creating, packing, generating into and destroying a handle
+ *     is the business of one thread at a time.  Output buffers belong to one call.  DESIGN.md, "Host threads", lists what the
+ *     library serialises internally.
  *   - per-site f64 tracks encode the reference's Option<f64>::None as NaN.
  *   - rows are variant sites in matrix order; a sweep over [row_begin, row_begin+row_count) writes
  *     per-site outputs at index (row - row_begin).
@@ -99,7 +103,11 @@ int fmh_copy_to_device(int device, void* d_dst, const void* h_src, size_t bytes,
 int fmh_device_zero(int device, void* d_ptr, size_t bytes, void* stream);
 int fmh_stream_synchronize(int device, void* stream);
 /* Frees the scratch the library keeps between calls on `device` (the sample-major planes of
- * fmh_pairwise_differences, up to 8 GiB); it is re-created on demand. */
+ * fmh_pairwise_differences and fmh_kinship_counts, up to 8 GiB; the idle blocks of the pool; the pinned upload staging); it is
+ * re-created on demand.  It may be called while other threads' fmh_* calls are in flight on the device and changes none of their
+ * results: it waits for a running fmh_pairwise_differences / fmh_kinship_counts (they hold the lock of that scratch for their whole
+ * length) and for a running upload, and it frees only pool blocks nobody holds.  (hipFree waits for the device: a slow call, not one
+ * for a hot path.) */
 int fmh_device_release_scratch(int device);
 
 /* ---- genotype matrix (replaces DenseGenotypeMatrix::new, stats.rs:261-296) ------------------- */
