@@ -9,6 +9,7 @@ from ferromic_amd import _abi as _abi
 _abi.load()
 
 from ._core import (  # noqa: E402,F401
+    AssociationScan,
     ChromosomePcaResult,
     DiversitySite,
     FStatEstimate,
@@ -28,6 +29,7 @@ from ._core import (  # noqa: E402,F401
     WcFstResult,
     WcFstSite,
     adjusted_sequence_length,
+    association_scan,
     chromosome_pca,
     chromosome_pca_to_file,
     ehh_scan,

@@ -239,6 +239,9 @@ SYMBOLS = {
     "fmh_genotype_site_stats": (_i, [_vp, _vp, _vp, _sz, _u64, _P(GenotypeSiteStatsOut)]),
     "fmh_genotype_site_weights": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "fmh_genotype_sample_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _u64, _P(GenotypeSampleStatsOut)]),
+    "fmh_assoc_sums": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "fmh_assoc_prepare": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _P(_sz), _vp]),
+    "fmh_assoc_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _u64, _sz, _sz, _vp, _vp, _vp, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

@@ -102,6 +102,8 @@ const OptionRow kOptionRows[] = {
     {"FMH_FSTAT_LDS_MASK_BYTES", &Options::fstat_lds_mask_bytes, 0, nullptr},
     {"FMH_KIN_BUDGET_BYTES", &Options::kin_budget_bytes, (long long)16 << 30, nullptr},
     {"FMH_QC_ITEM_ROWS", &Options::qc_item_rows, 0, nullptr},
+    {"FMH_ASSOC_ITEM_ROWS", &Options::assoc_item_rows, 0, nullptr},
+    {"FMH_ASSOC_BUDGET_BYTES", &Options::assoc_budget_bytes, (long long)1 << 30, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -1,0 +1,335 @@
+// assoc.hip — single-variant association scan: fmh_assoc_sums (per site the exact i64 sums of the genotype dosage, and of the called flag,
+// against K fixed-point value columns, an int8 contraction on the matrix cores straight from the bit planes), fmh_assoc_prepare (host: the
+// centred, orthonormalised covariate basis and the residualised phenotypes as i32 fixed point) and fmh_assoc_stats (host: beta, se, t and p
+// per site and phenotype from the sums and the QC tracks).  Kernels in assoc_kernels.hpp; definition in include/ferromic_hip.h, scheme in
+// DESIGN.md section 3.18.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "abi_internal.hpp"
+#include "assoc_kernels.hpp"
+#include "hap_launch.hpp"
+
+using namespace fmh;
+using namespace fmhi;
+
+namespace {
+
+constexpr size_t kAssocDefaultItemRows = 4096;
+constexpr size_t kAssocMaxItemRows = (size_t)1 << 30;
+constexpr size_t kAssocMaxSamples = (size_t)1 << 22;  // a digit accumulator holds 2 * n * 128 <= 2^30
+constexpr int32_t kAssocMaxValue = (int32_t)1 << 30;  // four signed base-256 digits
+
+}  // namespace
+
+extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null, size_t n_samples, size_t row_begin, size_t row_count,
+                              const int32_t* h_values, size_t n_columns, long long* d_dosage_sum, long long* d_called_sum_or_null, void* stream) {
+  // ---- every refusal, before any launch ----
+  if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
+  if (!h_values) return fail(FMH_ERR_INVALID, "NULL values");
+  if (!d_dosage_sum) return fail(FMH_ERR_INVALID, "d_dosage_sum is NULL");
+  if (n_samples == 0) return fail(FMH_ERR_INVALID, "n_samples is 0");
+  if (n_samples > kAssocMaxSamples) return fail(FMH_ERR_INVALID, "n_samples %zu exceeds 2^22: a digit accumulator would leave 32 bits", n_samples);
+  if (n_columns < 1 || n_columns > kAssocMaxColumns) return fail(FMH_ERR_INVALID, "%zu value columns: 1 to %u are taken", n_columns, kAssocMaxColumns);
+  for (size_t i = 0; i < n_samples * n_columns; ++i)
+    if (h_values[i] > kAssocMaxValue || h_values[i] < -kAssocMaxValue)
+      return fail(FMH_ERR_INVALID, "value %d (sample entry %zu, column %zu) is beyond +-2^30", h_values[i], i / n_columns, i % n_columns);
+  if (h_samples_or_null) {
+    for (size_t i = 0; i < n_samples; ++i) {
+      if (h_samples_or_null[i] >= m->samples) return fail(FMH_ERR_INVALID, "sample %u (entry %zu) is outside the matrix's %zu samples", h_samples_or_null[i], i, m->samples);
+      if (i && h_samples_or_null[i] <= h_samples_or_null[i - 1]) return fail(FMH_ERR_INVALID, "the sample list is not strictly ascending at entry %zu", i);
+    }
+  } else if (n_samples > m->samples) {
+    return fail(FMH_ERR_INVALID, "n_samples %zu exceeds the matrix's %zu samples", n_samples, m->samples);
+  }
+  if (row_begin > m->variants || row_count > m->variants - row_begin)
+    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
+  if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "the association scan takes diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
+  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the association scan reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  if (row_count == 0) return FMH_OK;
+
+  const size_t n = n_samples, K = n_columns;
+  const uint32_t last = h_samples_or_null ? h_samples_or_null[n - 1] : (uint32_t)(n - 1);
+  const uint32_t covered = last + 1;
+  const uint32_t nvec = last / 64 + 1;  // 64 samples per 16 bytes of a row; within the row: sample `last` exists
+  const uint32_t groups = (nvec + 3) / 4, vgroups = (uint32_t)((K + 15) / 16);
+  const size_t n_vectors = (size_t)groups * vgroups * kAssocChunkVecs;
+
+  const long long opt_rows = options().assoc_item_rows.load(std::memory_order_relaxed);
+  const size_t item_rows = opt_rows <= 0 ? kAssocDefaultItemRows : std::min<size_t>((size_t)opt_rows, kAssocMaxItemRows);
+  const size_t n_items = (row_count + item_rows - 1) / item_rows;
+  if (n_items > ((size_t)1 << 31)) return fail(FMH_ERR_UNSUPPORTED, "more than 2^31 work items: raise FMH_ASSOC_ITEM_ROWS");
+
+  // a matrix that is biallelic with nothing missing calls every genotype: C is the column totals, no second contraction
+  const bool complete = !m->pc && !m->p1 && !m->p2;
+  const bool contract_called = d_called_sum_or_null && !complete;
+  std::vector<long long> totals;
+  if (d_called_sum_or_null && complete) {
+    totals.assign(K, 0);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < K; ++k) totals[k] += h_values[i * K + k];
+  }
+  std::vector<int32_t> rank;
+  if (h_samples_or_null) {
+    rank.assign(covered, -1);
+    for (size_t i = 0; i < n; ++i) rank[h_samples_or_null[i]] = (int32_t)i;
+  }
+
+  FMH_TRY(use_device(m->device));
+  Workspace* ws = nullptr;
+  FMH_TRY(workspace(m->device, &ws));
+  hipStream_t st = (hipStream_t)stream;
+  DeviceScratch scratch;
+  scratch.device = m->device;
+  scratch.stream = st;
+  int32_t *d_values = nullptr, *d_rank = nullptr;
+  long long* d_totals = nullptr;
+  uint4* d_digits = nullptr;
+  FMH_TRY(scratch.get(&d_values, n * K));
+  FMH_TRY(scratch.get(&d_digits, n_vectors));
+  HIP_TRY(hipMemcpyAsync(d_values, h_values, n * K * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (!rank.empty()) {
+    FMH_TRY(scratch.get(&d_rank, rank.size()));
+    HIP_TRY(hipMemcpyAsync(d_rank, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  if (!totals.empty()) {
+    FMH_TRY(scratch.get(&d_totals, K));
+    HIP_TRY(hipMemcpyAsync(d_totals, totals.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
+  }
+
+  AssocArgs a{};
+  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
+  a.row_gap = m->pc ? m->row_gap : nullptr;
+  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
+  a.plane_pitch = m->plane_pitch;
+  a.nvec = nvec;
+  a.groups = groups;
+  a.columns = (uint32_t)K;
+  a.vgroups = vgroups;
+  a.digits = d_digits;
+  a.row_begin = row_begin;
+  a.row_count = row_count;
+  a.item_rows = (uint32_t)item_rows;
+  a.n_items = (uint32_t)n_items;
+  a.dosage_sum = d_dosage_sum;
+  a.called_sum = contract_called ? d_called_sum_or_null : nullptr;
+
+  KernelTimer timer;
+  FMH_TRY(timer.start(st));
+  hipLaunchKernelGGL(assoc_digits_kernel, dim3((unsigned)((n_vectors + 255) / 256)), dim3(256), 0, st, d_values, d_rank, (uint32_t)n, covered, (uint32_t)K,
+                     vgroups, n_vectors, d_digits);
+  HIP_TRY(hipGetLastError());
+  {
+    void (*kernel)(const AssocArgs) = contract_called ? assoc_sums_kernel<true> : assoc_sums_kernel<false>;
+    size_t grid = 0;
+    FMH_TRY(hap_grid(reinterpret_cast<const void*>(kernel), kAssocThreads, 0, n_items, ws->cus, &grid, kAssocChunkVecs * sizeof(uint4)));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kAssocThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (d_totals) {
+    const size_t count = row_count * K;
+    hipLaunchKernelGGL(assoc_fill_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, d_totals, (uint32_t)K, count, d_called_sum_or_null);
+    HIP_TRY(hipGetLastError());
+  }
+  FMH_TRY(timer.stop(st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return timer.read();
+}
+
+// ---- host only (no device).  The operation order is the header's; the unit is built with -ffp-contract=off ----------------------------------
+namespace {
+
+double seq_dot(const double* a, const double* b, size_t n, size_t stride_a, size_t stride_b) {
+  double s = 0.0;
+  for (size_t i = 0; i < n; ++i) s += a[i * stride_a] * b[i * stride_b];
+  return s;
+}
+
+// column-major work copy: centred in place
+void centre(double* x, size_t n) {
+  double s = 0.0;
+  for (size_t i = 0; i < n; ++i) s += x[i];
+  const double mean = s / (double)n;
+  for (size_t i = 0; i < n; ++i) x[i] -= mean;
+}
+
+// x minus its projections on the `c` orthonormal columns of q, one after the other, the whole pass twice
+void project_off(double* x, const std::vector<double>& q, size_t c, size_t n) {
+  for (int pass = 0; pass < 2; ++pass)
+    for (size_t j = 0; j < c; ++j) {
+      const double* qj = q.data() + j * n;
+      const double d = seq_dot(qj, x, n, 1, 1);
+      for (size_t i = 0; i < n; ++i) x[i] -= d * qj[i];
+    }
+}
+
+// the largest e with max |v| * 2^e <= 2^30; 0 for a column of zeros
+int fixed_point_exponent(const double* x, size_t n) {
+  double mx = 0.0;
+  for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(x[i]));
+  if (mx == 0.0) return 0;
+  int ex = 0;
+  const double f = std::frexp(mx, &ex);  // mx = f * 2^ex, f in [0.5, 1)
+  return f == 0.5 ? 31 - ex : 30 - ex;
+}
+
+// the continued fraction of the incomplete beta function (modified Lentz), to a relative change below 1e-15
+double beta_cf(double a, double b, double x) {
+  const double tiny = 1e-300;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (std::fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= 10000; ++m) {
+    const double dm = (double)m, m2 = 2.0 * dm;
+    double aa = dm * (b - dm) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h = h * (d * c);
+    aa = -(a + dm) * (qab + dm) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h = h * del;
+    if (std::fabs(del - 1.0) < 1e-15) break;
+  }
+  return h;
+}
+
+// two-sided tail of Student's t: I_x(df / 2, 1 / 2) at x = df / (df + t^2)
+double student_t_two_sided(double t, double df) {
+  const double t2 = t * t;
+  if (t2 == 0.0) return 1.0;
+  const double x = df / (df + t2), xc = t2 / (df + t2);  // xc = 1 - x without the cancellation
+  if (x == 0.0) return 0.0;
+  const double a = df / 2.0, b = 0.5;
+  const double front = std::exp(std::lgamma(a + b) - std::lgamma(a) - std::lgamma(b) + a * std::log(x) + b * std::log(xc));
+  if (x < (a + 1.0) / (a + b + 2.0)) return front * beta_cf(a, b, x) / a;
+  return 1.0 - front * beta_cf(b, a, xc) / b;
+}
+
+}  // namespace
+
+extern "C" int fmh_assoc_prepare(const double* h_phenotypes, const double* h_covariates_or_null, size_t n, size_t n_phenotypes, size_t n_covariates,
+                                 int32_t* h_values, int32_t* h_exponent, long long* h_total, double* h_yy, size_t* h_n_basis,
+                                 uint8_t* h_dropped_or_null) {
+  if (!h_phenotypes || !h_values || !h_exponent || !h_total || !h_yy || !h_n_basis) return fail(FMH_ERR_INVALID, "NULL argument");
+  if (n_covariates != 0 && !h_covariates_or_null) return fail(FMH_ERR_INVALID, "%zu covariates but the pointer is NULL", n_covariates);
+  if (n_phenotypes < 1) return fail(FMH_ERR_INVALID, "at least one phenotype is required");
+  if (n == 0 || n > kAssocMaxSamples) return fail(FMH_ERR_INVALID, "n = %zu: 1 to 2^22 samples are taken", n);
+  const size_t P = n_phenotypes, cin = n_covariates;
+  for (size_t i = 0; i < n * P; ++i)
+    if (!std::isfinite(h_phenotypes[i])) return fail(FMH_ERR_INVALID, "phenotype %zu of sample entry %zu is not finite", i % P, i / P);
+  for (size_t i = 0; i < n * cin; ++i)
+    if (!std::isfinite(h_covariates_or_null[i])) return fail(FMH_ERR_INVALID, "covariate %zu of sample entry %zu is not finite", i % cin, i / cin);
+
+  // covariates: centre, orthogonalise against the kept columns (modified Gram-Schmidt, twice), drop or normalise
+  std::vector<double> q;  // kept columns, column-major
+  std::vector<double> x(n);
+  size_t c = 0;
+  for (size_t j = 0; j < cin; ++j) {
+    for (size_t i = 0; i < n; ++i) x[i] = h_covariates_or_null[i * cin + j];
+    centre(x.data(), n);
+    const double r0 = std::sqrt(seq_dot(x.data(), x.data(), n, 1, 1));
+    project_off(x.data(), q, c, n);
+    const double r = std::sqrt(seq_dot(x.data(), x.data(), n, 1, 1));
+    const bool dropped = r0 == 0.0 || r <= r0 * 0x1p-26;
+    if (h_dropped_or_null) h_dropped_or_null[j] = dropped ? 1 : 0;
+    if (dropped) continue;
+    for (size_t i = 0; i < n; ++i) x[i] /= r;
+    q.insert(q.end(), x.begin(), x.end());
+    ++c;
+  }
+  if (n < c + 3) return fail(FMH_ERR_INVALID, "n - c - 2 = %lld residual degrees of freedom: at least 1 is required", (long long)n - (long long)c - 2);
+  if (c + P > kAssocMaxColumns) return fail(FMH_ERR_INVALID, "%zu kept covariates + %zu phenotypes exceed %u value columns", c, P, kAssocMaxColumns);
+  const size_t K = c + P;
+  *h_n_basis = c;
+
+  auto quantise = [&](const double* col, size_t k) {
+    const int e = fixed_point_exponent(col, n);
+    long long total = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const int32_t v = (int32_t)std::rint(std::ldexp(col[i], e));
+      h_values[i * K + k] = v;
+      total += v;
+    }
+    h_exponent[k] = e;
+    h_total[k] = total;
+  };
+  for (size_t j = 0; j < c; ++j) quantise(q.data() + j * n, j);
+  for (size_t p = 0; p < P; ++p) {
+    for (size_t i = 0; i < n; ++i) x[i] = h_phenotypes[i * P + p];
+    centre(x.data(), n);
+    project_off(x.data(), q, c, n);
+    quantise(x.data(), c + p);
+    double yy = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+      const double v = std::ldexp((double)h_values[i * K + c + p], -h_exponent[c + p]);
+      yy += v * v;
+    }
+    h_yy[p] = yy;
+  }
+  return FMH_OK;
+}
+
+extern "C" int fmh_assoc_stats(const long long* h_dosage_sum, const long long* h_called_sum, const uint32_t* h_hom_ref, const uint32_t* h_het,
+                               const uint32_t* h_hom_alt, size_t n_rows, const long long* h_total, const int32_t* h_exponent, const double* h_yy,
+                               uint64_t n_samples, size_t n_basis, size_t n_phenotypes, double* h_beta, double* h_se, double* h_t, double* h_p) {
+  if (n_phenotypes < 1) return fail(FMH_ERR_INVALID, "at least one phenotype is required");
+  if (n_basis + n_phenotypes > kAssocMaxColumns) return fail(FMH_ERR_INVALID, "%zu + %zu value columns exceed %u", n_basis, n_phenotypes, kAssocMaxColumns);
+  if (n_samples > kAssocMaxSamples || n_samples < n_basis + 3)
+    return fail(FMH_ERR_INVALID, "n = %llu with %zu basis columns: n <= 2^22 and n - c - 2 >= 1 are required", (unsigned long long)n_samples, n_basis);
+  if (n_rows == 0) return FMH_OK;
+  if (!h_dosage_sum || !h_called_sum || !h_hom_ref || !h_het || !h_hom_alt || !h_total || !h_exponent || !h_yy) return fail(FMH_ERR_INVALID, "NULL argument");
+  const size_t c = n_basis, P = n_phenotypes, K = c + P;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const uint64_t df = n_samples - c - 2;
+  auto put = [&](double* out, size_t i, double v) { if (out) out[i] = v; };
+  for (size_t r = 0; r < n_rows; ++r) {
+    const long long *S = h_dosage_sum + r * K, *C = h_called_sum + r * K;
+    const uint64_t het = h_het[r], alt = h_hom_alt[r], N = (uint64_t)h_hom_ref[r] + het + alt, n_alt = het + 2 * alt;
+    double D = nan, mu = 0.0;
+    if (N != 0) {
+      mu = (double)n_alt / (double)N;
+      D = (double)(het + 4 * alt) - (double)(n_alt * n_alt) / (double)N;
+      for (size_t k = 0; k < c; ++k) {
+        const double a = std::ldexp((double)S[k] + mu * (double)(h_total[k] - C[k]), -h_exponent[k]);
+        D = D - a * a;
+      }
+    }
+    for (size_t p = 0; p < P; ++p) {
+      const size_t o = r * P + p, k = c + p;
+      if (!(D > 0.0)) {  // N == 0 too
+        put(h_beta, o, nan); put(h_se, o, nan); put(h_t, o, nan); put(h_p, o, nan);
+        continue;
+      }
+      const double a = std::ldexp((double)S[k] + mu * (double)(h_total[k] - C[k]), -h_exponent[k]);
+      const double beta = a / D;
+      double rss = h_yy[p] - a * a / D;
+      if (rss < 0.0) rss = 0.0;
+      const double se = std::sqrt(rss / (double)df / D);
+      put(h_beta, o, beta);
+      put(h_se, o, se);
+      if (se == 0.0) {
+        put(h_t, o, nan); put(h_p, o, nan);
+        continue;
+      }
+      const double t = beta / se;
+      put(h_t, o, t);
+      put(h_p, o, student_t_two_sided(t, (double)df));
+    }
+  }
+  return FMH_OK;
+}

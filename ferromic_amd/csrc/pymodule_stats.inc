@@ -912,6 +912,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_fstat.inc"
 #include "pymodule_kinship.inc"
 #include "pymodule_qc.inc"
+#include "pymodule_assoc.inc"
 
 }  // namespace
 
@@ -1060,6 +1061,7 @@ PYBIND11_MODULE(_core, m) {
   bind_fstat(m);
   bind_kinship(m);
   bind_qc(m);
+  bind_assoc(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

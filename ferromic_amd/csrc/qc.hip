@@ -23,30 +23,6 @@ constexpr size_t kQcDefaultItemRows = 4096;
 constexpr size_t kQcMaxItemRows = (size_t)1 << 30;
 constexpr uint64_t kQcMaxStatGenotypes = (uint64_t)1 << 31;  // the estimators' integer products stay below 2^63
 
-// HIP events around a call's kernels when fmh_timing_enable is on, added to the library's kernel time after the synchronise
-struct KernelTimer {
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool on = timing_enabled();
-  ~KernelTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-  int start(hipStream_t st) {
-    if (!on) return FMH_OK;
-    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], st));
-    return FMH_OK;
-  }
-  int stop(hipStream_t st) {
-    if (on) HIP_TRY(hipEventRecord(ev[1], st));
-    return FMH_OK;
-  }
-  int read() {
-    if (!on) return FMH_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-    return FMH_OK;
-  }
-};
-
 }  // namespace
 
 extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_samples_or_null, size_t n_samples, size_t row_begin, size_t row_count,

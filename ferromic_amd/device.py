@@ -806,6 +806,102 @@ def genotype_sample_stats(hom_ref, het, hom_alt, kept_rows: int, weighted_called
     return out
 
 
+# ---- association scan: exact fixed-point dosage sums, regression per site --------------------------------------------------------------
+ASSOC_DEFAULT_ITEM_ROWS = 4096   # FMH_ASSOC_ITEM_ROWS unset
+ASSOC_MAX_COLUMNS = 64
+ASSOC_MAX_SAMPLES = 1 << 22
+ASSOC_STATS = ("beta", "se", "t", "p")
+
+
+@dataclass
+class AssocSums:
+    dosage: np.ndarray              # [row_count][K] int64
+    called: Optional[np.ndarray]    # [row_count][K] int64, or None when the called sums were not asked for
+
+
+@dataclass
+class AssocPrepared:
+    values: np.ndarray      # [n][K] int32: the c basis columns, then the P phenotypes
+    exponent: np.ndarray    # [K] int32
+    total: np.ndarray       # [K] int64
+    yy: np.ndarray          # [P] float64
+    n_basis: int            # c
+    dropped: np.ndarray     # [c_in] bool
+
+
+def assoc_sums(m: DeviceMatrix, values, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None,
+               called: bool = True, stream=None, fill: Optional[int] = None) -> AssocSums:
+    """fmh_assoc_sums over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all): S = sum of dosage x values and, with `called`, C = sum of called x values, [rows][K] int64.  `values` is
+    [n][K] int32.  `fill` pre-fills the outputs with that byte (tests: the call must write every entry)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    if values.ndim != 2:
+        raise ValueError("values is [n][K]")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if values.shape[0] != n:
+        raise ValueError("values has one row per selected sample")
+    k = values.shape[1]
+    nbytes = max(8 * rows * k, 8)
+
+    def buffer():
+        return DeviceBuffer(m.device, nbytes) if fill is None else DeviceBuffer.from_numpy(m.device, np.full(nbytes, fill, dtype=np.uint8))
+
+    d_s = buffer()
+    d_c = buffer() if called else None
+    _abi.check(_abi.load().fmh_assoc_sums(m._h, _ptr(samples), n, row_begin, rows, _ptr(values), k, d_s.ptr, None if d_c is None else d_c.ptr, stream))
+    return AssocSums(d_s.to_numpy(np.int64, rows * k).reshape(rows, k), None if d_c is None else d_c.to_numpy(np.int64, rows * k).reshape(rows, k))
+
+
+def assoc_prepare(phenotypes, covariates=None) -> AssocPrepared:
+    """fmh_assoc_prepare (host only): the centred, orthonormalised covariate basis and the residualised phenotypes as i32 fixed point."""
+    y = np.ascontiguousarray(phenotypes, dtype=np.float64)
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    if y.ndim != 2:
+        raise ValueError("phenotypes is [n] or [n][P]")
+    n, p = y.shape
+    x = None
+    c_in = 0
+    if covariates is not None:
+        x = np.ascontiguousarray(covariates, dtype=np.float64)
+        if x.ndim != 2 or x.shape[0] != n:
+            raise ValueError("covariates is [n][c_in]")
+        c_in = x.shape[1]
+    values = np.zeros(max(n * (c_in + p), 1), dtype=np.int32)
+    exponent = np.zeros(c_in + p, dtype=np.int32)
+    total = np.zeros(c_in + p, dtype=np.int64)
+    yy = np.zeros(p, dtype=np.float64)
+    dropped = np.zeros(max(c_in, 1), dtype=np.uint8)
+    c = C.c_size_t(0)
+    _abi.check(_abi.load().fmh_assoc_prepare(_ptr(y), None if c_in == 0 else _ptr(x), n, p, c_in, _ptr(values), _ptr(exponent), _ptr(total), _ptr(yy),
+                                             C.byref(c), _ptr(dropped)))
+    k = int(c.value) + p
+    return AssocPrepared(values[: n * k].reshape(n, k).copy(), exponent[:k].copy(), total[:k].copy(), yy, int(c.value), dropped[:c_in].astype(bool))
+
+
+def assoc_stats(dosage_sum, called_sum, hom_ref, het, hom_alt, total, exponent, yy, n_samples: int, n_basis: int,
+                outputs=ASSOC_STATS) -> Dict[str, np.ndarray]:
+    """fmh_assoc_stats (host only): beta, se, t and p [rows][P] from the sums, the QC tracks and fmh_assoc_prepare's T, e and yy."""
+    s = np.ascontiguousarray(dosage_sum, dtype=np.int64)
+    cs = np.ascontiguousarray(called_sum, dtype=np.int64)
+    tracks = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    yy = np.ascontiguousarray(yy, dtype=np.float64).reshape(-1)
+    total = np.ascontiguousarray(total, dtype=np.int64).reshape(-1)
+    exponent = np.ascontiguousarray(exponent, dtype=np.int32).reshape(-1)
+    rows, p, k = tracks[0].size, yy.size, int(n_basis) + yy.size
+    if s.size != rows * k or cs.size != rows * k or total.size != k or exponent.size != k or any(a.size != rows for a in tracks):
+        raise ValueError("the sums are [rows][c + P], the tracks [rows], total and exponent [c + P]")
+    out = {name: np.zeros((rows, p), dtype=np.float64) for name in outputs}
+    _abi.check(_abi.load().fmh_assoc_stats(_ptr(s), _ptr(cs), *[_ptr(a) for a in tracks], rows, _ptr(total), _ptr(exponent), _ptr(yy), int(n_samples),
+                                           int(n_basis), p, *[_ptr(out[name]) if name in out else None for name in ASSOC_STATS]))
+    return out
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -81,7 +81,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
- *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS
+ *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -714,6 +714,79 @@ typedef struct { double *h_call_rate, *h_het_rate, *h_f; } fmh_genotype_sample_s
 int fmh_genotype_sample_stats(const uint64_t* h_hom_ref, const uint64_t* h_het, const uint64_t* h_hom_alt,
                               const uint64_t* h_weighted_called_or_null, size_t n, uint64_t kept_rows,
                               const fmh_genotype_sample_stats_out* out);   /* host only, no device */
+
+/* ---- association scan: exact fixed-point dosage sums, linear regression per site (an addition: the reference has none) -----------------
+ * The consumer of the cohort chain QC -> fmh_ld_prune -> fmh_kinship_counts -> PCA: for every site the regression of each phenotype on the
+ * genotype dosage, with an intercept and covariates (typically the principal components) in the model; beta, its standard error, t and p.
+ * Matrix, samples and genotype are fmh_genotype_counts': ploidy 2, a packed image, sample s owns columns 2s and 2s+1; c_s(r) = 1 when the
+ * genotype of s at row r is called (both entries called and both alleles <= 1), g_s(r) in {0, 1, 2} the dosage.  Bits under uncalled
+ * entries are undefined: every class is masked with the called plane.  The selected samples are h_samples_or_null (strictly ascending,
+ * distinct matrix sample numbers) or the first n_samples; n = n_samples; i is a position in that list.
+ *
+ * Device sums (fmh_assoc_sums).  Given V[n][K] (i32, host, row-major by sample), for every row r of [row_begin, row_begin + row_count) and k < K:
+ *     S[r][k] = sum_i c_i(r) * g_i(r) * V[i][k]   (dosage sum)        C[r][k] = sum_i c_i(r) * V[i][k]   (called sum; optional output)
+ *   Both are exact `long long` device buffers [row_count][K], WRITTEN (not added).  Limits: 1 <= K <= 64, |V| <= 2^30, n <= 2^22, so
+ *   |S| <= 2 * 2^22 * 2^30 = 2^53: every sum converts to f64 without rounding.  V travels as four signed base-256 digits (d in [-128, 127])
+ *   and the contraction over samples runs on the int8 matrix cores straight from the bit planes; an i32 digit accumulator holds at most
+ *   2 * n * 128 <= 2^30.  A matrix that is biallelic with nothing missing needs no second contraction: the call fills C with the column
+ *   totals T[k] = sum_i V[i][k].  Enqueues on `stream` and synchronises it.
+ *   Refusals, all before any launch, in this order.  FMH_ERR_INVALID: NULL matrix, values or d_dosage_sum; n_samples == 0 or > 2^22; K
+ *   outside 1..64; a value beyond +-2^30; a sample index out of range, or a list that is not strictly ascending (n_samples beyond the
+ *   matrix's samples without a list); a row range past the matrix.  FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix without a
+ *   packed image (u8 rows only: call fmh_matrix_pack first).  row_count == 0 is FMH_OK.
+ *   Option: FMH_ASSOC_ITEM_ROWS = the most rows of a work item (default 4 096).  It changes no result, nor do FMH_GRID_PER_CU and FMH_GRID_BLOCKS.
+ *
+ * Host preparation (fmh_assoc_prepare, no device).  h_phenotypes f64 [n][P], P >= 1; h_covariates_or_null f64 [n][c_in], both in the order
+ * of the selected samples.  The operation order is fixed, so that a plain Python loop over floats reproduces the integers (the library is
+ * built with -ffp-contract=off).  A "sequential" sum starts from 0.0 and adds in sample order.
+ *   1. Intercept: always in the model and NEVER a value column.  Every covariate and phenotype column is centred: mean = (sequential sum) / n,
+ *      then x_i = x_i - mean.  (A constant column 1/sqrt(n) would round every entry the same way, and that systematic error is amplified by
+ *      the cancellation in D below.)
+ *   2. Covariates, in column order: r0 = sqrt(sequential sum of x_i * x_i) of the centred column.  Then, twice over: for each kept column q in
+ *      the order kept, d = sequential sum of q_i * x_i, then x_i = x_i - d * q_i (modified Gram-Schmidt).  r = sqrt(sequential sum of
+ *      x_i * x_i).  r0 == 0 or r <= r0 * 2^-26: the column is dropped as constant or collinear (h_dropped_or_null[j] = 1, else 0).
+ *      Otherwise x_i = x_i / r and the column is kept; c = the number kept.
+ *   3. Phenotypes: centred, then the c kept columns projected off the same way, twice over.
+ *   4. Fixed point, per kept column and phenotype: e_k = the largest integer with max_i |v_ik| * 2^e_k <= 2^30 (from frexp: max = f * 2^x with
+ *      f in [0.5, 1) gives e = 31 - x when f == 0.5, else 30 - x); e_k = 0 for a column of zeros.
+ *   5. Outputs: V[i][k] = (int32) rint(v_ik * 2^e_k) [n][K] with K = c + P, columns 0..c the basis and c..c+P the phenotypes (h_values must
+ *      hold n * (c_in + P) entries; n * K are written, row pitch K); e[K]; T[K] exact i64; yy[p] = sequential sum of (V[i][c+p] * 2^-e)^2;
+ *      *h_n_basis = c.  h_exponent and h_total hold c_in + P entries.
+ *   Refusals (FMH_ERR_INVALID): a NULL pointer (h_dropped_or_null excepted; h_covariates_or_null when c_in == 0); P == 0; n == 0 or
+ *   n > 2^22; a non-finite input; n - c - 2 < 1; c + P > 64.
+ *
+ * Host statistics (fmh_assoc_stats, no device).  Per row: S and C [K], the three u32 QC tracks hom_ref, het, hom_alt of the same rows and
+ * samples (fmh_genotype_counts), T, e, yy, n, c, P.  Missing genotypes are mean-imputed (as regenie and fastGWA do):
+ *     N = hom_ref + het + hom_alt;  n_alt = het + 2 * hom_alt;  mu = (double)n_alt / (double)N
+ *     a_k  = ldexp((double)S_k + mu * (double)(T_k - C_k), -e_k)              k < K   (T_k - C_k in i64)
+ *     gg   = (double)(het + 4 * hom_alt) - (double)(n_alt * n_alt) / (double)N         (u64 product)
+ *     D    = gg - a_0 * a_0 - a_1 * a_1 - ... - a_{c-1} * a_{c-1}                      (subtracted in that order)
+ *     beta = a_{c+p} / D;   rss = yy_p - (a_{c+p} * a_{c+p}) / D, 0.0 if negative;   df = n - c - 2
+ *     se   = sqrt((rss / (double)df) / D);   t = beta / se;   p = the two-sided Student-t tail of |t| with df degrees of freedom
+ *   N == 0 or not D > 0: a quiet NaN in all four outputs of the row.  se == 0: t and p are NaN.
+ *   p = I_x(df/2, 1/2), the regularised incomplete beta function at x = df / (df + t^2), with xc = t^2 / (df + t^2) for 1 - x:
+ *     t^2 == 0: 1.0.  x == 0: 0.0.  a = df / 2.0, b = 0.5,
+ *     front = exp(lgamma(a + b) - lgamma(a) - lgamma(b) + a * log(x) + b * log(xc));
+ *     x < (a + 1) / (a + b + 2):  p = front * cf(a, b, x) / a;  otherwise  p = 1.0 - front * cf(b, a, xc) / b,
+ *     cf the continued fraction by the modified Lentz method (floor 1e-300), iterated until a step changes it by less than 1e-15 relative.
+ *   Outputs beta, se, t, p: f64 [rows][P]; each may be NULL.  Refusals (FMH_ERR_INVALID): P == 0; c + P > 64; n > 2^22 or n - c - 2 < 1; a
+ *   NULL input with n_rows > 0.  n_rows == 0 is FMH_OK.
+ * Not built: logistic regression, per-phenotype missing values (a NaN is refused), mixed models, dominant / recessive coding, sharding over
+ *   devices (a caller splits rows), run_vcf wiring, u8 rows, more than 64 value columns per call.
+ */
+int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                   size_t row_begin, size_t row_count, const int32_t* h_values /* [n_samples][n_columns] */, size_t n_columns,
+                   long long* d_dosage_sum /* [row_count][n_columns], device, written */,
+                   long long* d_called_sum_or_null /* [row_count][n_columns], device, written */, void* stream);
+int fmh_assoc_prepare(const double* h_phenotypes /* [n][n_phenotypes] */, const double* h_covariates_or_null /* [n][n_covariates] */, size_t n,
+                      size_t n_phenotypes, size_t n_covariates, int32_t* h_values /* n * (n_covariates + n_phenotypes) entries; [n][K] written */,
+                      int32_t* h_exponent, long long* h_total /* n_covariates + n_phenotypes entries each; K written */,
+                      double* h_yy /* [n_phenotypes] */, size_t* h_n_basis, uint8_t* h_dropped_or_null /* [n_covariates] */);   /* host only, no device */
+int fmh_assoc_stats(const long long* h_dosage_sum, const long long* h_called_sum /* [n_rows][n_basis + n_phenotypes] each */,
+                    const uint32_t* h_hom_ref, const uint32_t* h_het, const uint32_t* h_hom_alt /* [n_rows] each */, size_t n_rows,
+                    const long long* h_total, const int32_t* h_exponent /* [n_basis + n_phenotypes] each */, const double* h_yy /* [n_phenotypes] */,
+                    uint64_t n_samples, size_t n_basis, size_t n_phenotypes,
+                    double* h_beta, double* h_se, double* h_t, double* h_p /* [n_rows][n_phenotypes] each, or NULL */);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
