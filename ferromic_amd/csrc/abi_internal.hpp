@@ -107,6 +107,8 @@ struct DeviceScratch {
   hipStream_t stream = nullptr;
   bool settled = false;  // set once the call has synchronised the stream its kernels ran on
   std::vector<void*> ptrs;
+  DeviceScratch() = default;
+  DeviceScratch(int device_, hipStream_t stream_) : device(device_), stream(stream_) {}
   // An early (error) return may leave kernels that write these blocks enqueued: wait for the stream before the blocks go
   // back to the pool, where another thread's pool_malloc could be handed them at once.
   ~DeviceScratch() {

@@ -12,7 +12,7 @@
 
 #include "abi_internal.hpp"
 #include "assoc_kernels.hpp"
-#include "hap_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -20,7 +20,6 @@ using namespace fmhi;
 namespace {
 
 constexpr size_t kAssocDefaultItemRows = 4096;
-constexpr size_t kAssocMaxItemRows = (size_t)1 << 30;
 constexpr size_t kAssocMaxSamples = (size_t)1 << 22;  // a digit accumulator holds 2 * n * 128 <= 2^30
 constexpr int32_t kAssocMaxValue = (int32_t)1 << 30;  // four signed base-256 digits
 
@@ -38,18 +37,10 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
   for (size_t i = 0; i < n_samples * n_columns; ++i)
     if (h_values[i] > kAssocMaxValue || h_values[i] < -kAssocMaxValue)
       return fail(FMH_ERR_INVALID, "value %d (sample entry %zu, column %zu) is beyond +-2^30", h_values[i], i / n_columns, i % n_columns);
-  if (h_samples_or_null) {
-    for (size_t i = 0; i < n_samples; ++i) {
-      if (h_samples_or_null[i] >= m->samples) return fail(FMH_ERR_INVALID, "sample %u (entry %zu) is outside the matrix's %zu samples", h_samples_or_null[i], i, m->samples);
-      if (i && h_samples_or_null[i] <= h_samples_or_null[i - 1]) return fail(FMH_ERR_INVALID, "the sample list is not strictly ascending at entry %zu", i);
-    }
-  } else if (n_samples > m->samples) {
-    return fail(FMH_ERR_INVALID, "n_samples %zu exceeds the matrix's %zu samples", n_samples, m->samples);
-  }
-  if (row_begin > m->variants || row_count > m->variants - row_begin)
-    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
+  FMH_TRY(check_samples(h_samples_or_null, n_samples, m->samples));
+  FMH_TRY(check_rows(row_begin, row_count, m->variants));
   if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "the association scan takes diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the association scan reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  FMH_TRY(check_packed(m, "the association scan reads"));
   if (row_count == 0) return FMH_OK;
 
   const size_t n = n_samples, K = n_columns;
@@ -59,10 +50,9 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
   const uint32_t groups = (nvec + 3) / 4, vgroups = (uint32_t)((K + 15) / 16);
   const size_t n_vectors = (size_t)groups * vgroups * kAssocChunkVecs;
 
-  const long long opt_rows = options().assoc_item_rows.load(std::memory_order_relaxed);
-  const size_t item_rows = opt_rows <= 0 ? kAssocDefaultItemRows : std::min<size_t>((size_t)opt_rows, kAssocMaxItemRows);
+  const size_t item_rows = item_rows_of(options().assoc_item_rows, kAssocDefaultItemRows);
   const size_t n_items = (row_count + item_rows - 1) / item_rows;
-  if (n_items > ((size_t)1 << 31)) return fail(FMH_ERR_UNSUPPORTED, "more than 2^31 work items: raise FMH_ASSOC_ITEM_ROWS");
+  FMH_TRY(check_item_count(n_items, "FMH_ASSOC_ITEM_ROWS"));
 
   // a matrix that is biallelic with nothing missing calls every genotype: C is the column totals, no second contraction
   const bool complete = !m->pc && !m->p1 && !m->p2;
@@ -79,33 +69,19 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
     for (size_t i = 0; i < n; ++i) rank[h_samples_or_null[i]] = (int32_t)i;
   }
 
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
+  hipStream_t st = call.st;
   int32_t *d_values = nullptr, *d_rank = nullptr;
   long long* d_totals = nullptr;
   uint4* d_digits = nullptr;
-  FMH_TRY(scratch.get(&d_values, n * K));
-  FMH_TRY(scratch.get(&d_digits, n_vectors));
-  HIP_TRY(hipMemcpyAsync(d_values, h_values, n * K * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (!rank.empty()) {
-    FMH_TRY(scratch.get(&d_rank, rank.size()));
-    HIP_TRY(hipMemcpyAsync(d_rank, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  if (!totals.empty()) {
-    FMH_TRY(scratch.get(&d_totals, K));
-    HIP_TRY(hipMemcpyAsync(d_totals, totals.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
-  }
+  FMH_TRY(call.upload(h_values, n * K, &d_values));
+  FMH_TRY(call.scratch.get(&d_digits, n_vectors));
+  if (!rank.empty()) FMH_TRY(call.upload(rank.data(), rank.size(), &d_rank));
+  if (!totals.empty()) FMH_TRY(call.upload(totals.data(), K, &d_totals));
 
   AssocArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   a.nvec = nvec;
   a.groups = groups;
   a.columns = (uint32_t)K;
@@ -118,15 +94,14 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
   a.dosage_sum = d_dosage_sum;
   a.called_sum = contract_called ? d_called_sum_or_null : nullptr;
 
-  KernelTimer timer;
-  FMH_TRY(timer.start(st));
+  FMH_TRY(call.start());
   hipLaunchKernelGGL(assoc_digits_kernel, dim3((unsigned)((n_vectors + 255) / 256)), dim3(256), 0, st, d_values, d_rank, (uint32_t)n, covered, (uint32_t)K,
                      vgroups, n_vectors, d_digits);
   HIP_TRY(hipGetLastError());
   {
     void (*kernel)(const AssocArgs) = contract_called ? assoc_sums_kernel<true> : assoc_sums_kernel<false>;
     size_t grid = 0;
-    FMH_TRY(hap_grid(reinterpret_cast<const void*>(kernel), kAssocThreads, 0, n_items, ws->cus, &grid, kAssocChunkVecs * sizeof(uint4)));
+    FMH_TRY(persistent_grid(reinterpret_cast<const void*>(kernel), kAssocThreads, 0, n_items, call.ws->cus, &grid, kAssocChunkVecs * sizeof(uint4)));
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kAssocThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
   }
@@ -135,10 +110,7 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
     hipLaunchKernelGGL(assoc_fill_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, d_totals, (uint32_t)K, count, d_called_sum_or_null);
     HIP_TRY(hipGetLastError());
   }
-  FMH_TRY(timer.stop(st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  return timer.read();
+  return call.finish();
 }
 
 // ---- host only (no device).  The operation order is the header's; the unit is built with -ffp-contract=off ----------------------------------

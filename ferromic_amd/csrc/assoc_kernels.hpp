@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plane_rows.hpp"
+
 namespace fmh {
 
 constexpr uint32_t kAssocThreads = 256;
@@ -41,10 +43,7 @@ constexpr uint32_t kAssocEven = 0x55555555u;
 
 typedef int assoc_v4i __attribute__((ext_vector_type(4)));
 
-struct AssocArgs {
-  const uint8_t *p0, *p1, *p2, *pc;  // planes (p1 / p2 / pc may be null)
-  const uint8_t *row_gap, *row_hi;   // one byte per row or null (null = read the plane of every row)
-  size_t plane_pitch;
+struct AssocArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   uint32_t nvec;                     // 16-byte vectors of a row through the last selected sample (<= plane_pitch / 16)
   uint32_t groups;                   // ceil(nvec / 4)
   uint32_t columns;                  // K

@@ -10,6 +10,7 @@
 #include "abi_internal.hpp"
 #include "ehh_kernels.hpp"
 #include "hap_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -31,8 +32,7 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_
   if (g->n_groups != 1) return fail(FMH_ERR_INVALID, "the haplotype scan takes exactly 1 group, got %d", g->n_groups);
   if (g->device != m->device || g->columns != m->columns) return fail(FMH_ERR_INVALID, "the groups were not made for this matrix");
   if (g->sizes[0] == 0) return fail(FMH_ERR_INVALID, "group 0 has no member");
-  if (row_begin > row_end || row_end > m->variants)
-    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_end, m->variants);
+  FMH_TRY(check_rows(row_begin, row_end - row_begin, m->variants));  // (row_end below row_begin wraps to a count no matrix holds)
   for (size_t i = 0; i < n_focal; ++i)
     if (focal[i] < row_begin || focal[i] >= row_end)
       return fail(FMH_ERR_INVALID, "focal row %llu (entry %zu) is outside the rows [%zu, %zu)", (unsigned long long)focal[i], i, row_begin, row_end);
@@ -49,8 +49,7 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_
                 (unsigned long long)g->sizes[0], kEhhMaxMembers);
   if (want_pairs && n_focal > ((size_t)1 << 32) / 4 / (size_t)p->max_extent)
     return fail(FMH_ERR_UNSUPPORTED, "a curve table of %zu focal rows x 2 sides x 2 cores x %u steps exceeds 2^32 entries", n_focal, p->max_extent);
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the haplotype scan reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
-  return FMH_OK;
+  return check_packed(m, "the haplotype scan reads");
 }
 
 }  // namespace
@@ -61,10 +60,8 @@ extern "C" int fmh_ehh_scan(const fmh_matrix* m, const fmh_groups* g, size_t row
                             const uint32_t* h_positions_or_null, const fmh_ehh_params* params, fmh_ehh_side* d_out, uint32_t* d_pairs_or_null,
                             void* stream) {
   FMH_TRY(check_args(m, g, row_begin, row_end, h_focal, n_focal, h_positions_or_null, params, d_out, d_pairs_or_null != nullptr));
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
 
   // the members' columns, ascending: member rank -> column
   const uint32_t n = (uint32_t)g->sizes[0];
@@ -81,28 +78,17 @@ extern "C" int fmh_ehh_scan(const fmh_matrix* m, const fmh_groups* g, size_t row
     return fail(FMH_ERR_UNSUPPORTED, "a group of %u members needs %zu bytes of LDS, this device gives a workgroup %d", n, lds_bytes, lds_max);
 
   const size_t n_items = n_focal * 2;
-  const unsigned threads = hap_pick_threads(n, n_items, ws->cus);
+  const unsigned threads = hap_pick_threads(n, n_items, call.ws->cus);
 
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
   uint32_t* d_cols = nullptr;
   unsigned long long* d_focal = nullptr;
   uint32_t* d_pos = nullptr;
-  FMH_TRY(scratch.get(&d_cols, cols.size()));
-  FMH_TRY(scratch.get(&d_focal, n_focal));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_focal, h_focal, n_focal * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  if (h_positions_or_null) {  // the rows of the range only
-    FMH_TRY(scratch.get(&d_pos, row_end - row_begin));
-    HIP_TRY(hipMemcpyAsync(d_pos, h_positions_or_null + row_begin, (row_end - row_begin) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
+  FMH_TRY(call.upload(cols.data(), cols.size(), &d_cols));
+  FMH_TRY(call.upload(h_focal, n_focal, &d_focal));
+  if (h_positions_or_null) FMH_TRY(call.upload(h_positions_or_null + row_begin, row_end - row_begin, &d_pos));  // the rows of the range only
 
   EhhArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   a.cols = d_cols;
   a.n = n;
   a.touch_first = (cols.front() >> 5) * 4;
@@ -122,25 +108,14 @@ extern "C" int fmh_ehh_scan(const fmh_matrix* m, const fmh_groups* g, size_t row
                                         : (planes == 3 ? ehh_kernel<3, false> : planes == 2 ? ehh_kernel<2, false> : ehh_kernel<1, false>);
   if (lds_bytes > ((size_t)64 << 10))
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  // launch shape (hap_launch.hpp), with the kernel's registers in it: at 81-88 VGPRs five waves fit a SIMD, fewer workgroups than LDS allows
+  // launch shape (hap_launch.hpp, stat_call.hpp), with the kernel's registers in it: at 81-88 VGPRs five waves fit a SIMD, fewer workgroups than LDS allows
   size_t grid = 0;
-  FMH_TRY(hap_grid(reinterpret_cast<const void*>(kernel), threads, lds_bytes, n_items, ws->cus, &grid));
+  FMH_TRY(persistent_grid(reinterpret_cast<const void*>(kernel), threads, lds_bytes, n_items, call.ws->cus, &grid));
 
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds_bytes, st, a);
+  FMH_TRY(call.start());
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds_bytes, call.st, a);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  if (timing) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-  }
-  return FMH_OK;
+  return call.finish();
 }
 
 extern "C" int fmh_ehh_stats(const fmh_ehh_side* h_sides, size_t n_focal, int include_edges, fmh_ehh_stats_out* h_out) {

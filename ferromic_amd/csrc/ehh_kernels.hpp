@@ -33,10 +33,7 @@ constexpr uint32_t kEhhNoClass = 0xFFFFu;
 constexpr uint32_t kEhhMaxMembers = kHapMaxMembers;  // the same 4.75 bytes per member: the scan adds no LDS
 static_assert(kEhhMaxMembers < kEhhNoClass, "the label of a member of neither core is no class");
 
-struct EhhArgs {
-  const uint8_t *p0, *p1, *p2, *pc;  // planes (p1 / p2 / pc may be null)
-  const uint8_t *row_gap, *row_hi;   // one byte per row or null (null = read the plane of every row)
-  size_t plane_pitch;
+struct EhhArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   const uint32_t* cols;              // [n]: the column of member rank r, ascending
   uint32_t n;
   uint32_t touch_first, touch_last;  // byte offsets of the first and last plane dword of a row that holds a member

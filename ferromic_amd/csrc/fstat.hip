@@ -10,7 +10,7 @@
 
 #include "abi_internal.hpp"
 #include "fstat_kernels.hpp"
-#include "hap_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -18,13 +18,10 @@ using namespace fmhi;
 namespace {
 
 constexpr size_t kFstatDefaultItemRows = 4096;
-constexpr size_t kFstatMaxItemRows = (size_t)1 << 30;
 // with 8 192 bytes of entries a workgroup's LDS stays under 20 KiB at any G (16 + 256 + 64 x 33 x 4 bytes of row state): eight workgroups per CU
 constexpr size_t kFstatDefaultMaskBytes = 8192;
 constexpr size_t kFstatMaxMaskBytes = (size_t)48 << 10;  // state + entries stay under the 64 KiB a launch gets without asking
 constexpr uint64_t kFstatMaxSize = (uint64_t)1 << 17;    // fmh_fstat_f4: a term's cofactor n n stays at most 2^34
-
-struct Block { size_t begin, end; };
 
 bool group_count_ok(int n_groups) { return n_groups >= 2 && n_groups <= FMH_FSTAT_MAX_GROUPS; }
 
@@ -39,7 +36,6 @@ extern "C" size_t fmh_fstat_moment_count(int n_groups) {
 
 extern "C" int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_mask, int n_groups, const uint64_t* h_blocks, size_t n_blocks,
                                  uint64_t* d_moments, fmh_sfs_skipped* h_skipped, void* stream) {
-  static_assert(sizeof(Block) == 2 * sizeof(uint64_t), "a block is two u64");
   // ---- every refusal that needs no device, in the header's order ----
   if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
   if (!h_column_mask) return fail(FMH_ERR_INVALID, "h_column_mask is NULL");
@@ -54,10 +50,8 @@ extern "C" int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_ma
     if (sizes[g] == 0) return fail(FMH_ERR_INVALID, "group %u has no member", g);
     max_size = std::max(max_size, sizes[g]);
   }
-  const Block* blocks = reinterpret_cast<const Block*>(h_blocks);
-  for (size_t b = 0; b < n_blocks; ++b)
-    if (blocks[b].begin > blocks[b].end || blocks[b].end > m->variants)
-      return fail(FMH_ERR_INVALID, "rows [%zu, %zu) of block %zu exceed the matrix's %zu variants", blocks[b].begin, blocks[b].end, b, m->variants);
+  const RowSpan* blocks = reinterpret_cast<const RowSpan*>(h_blocks);
+  FMH_TRY(check_row_spans(blocks, n_blocks, "block", m->variants));
   if (n_blocks == 0) return fail(FMH_ERR_INVALID, "n_blocks is 0");
   for (size_t b = 0; b < n_blocks; ++b) {
     const unsigned __int128 worst = (unsigned __int128)(blocks[b].end - blocks[b].begin) * max_size * max_size;
@@ -65,26 +59,24 @@ extern "C" int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_ma
       return fail(FMH_ERR_UNSUPPORTED, "block %zu: %zu rows x %llu^2 members reach 2^63, a u64 moment could wrap: use smaller blocks", b,
                   blocks[b].end - blocks[b].begin, (unsigned long long)max_size);
   }
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the f-statistics read the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  FMH_TRY(check_packed(m, "the f-statistics read"));
 
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
+  hipStream_t st = call.st;
   const size_t M = fmh_fstat_moment_count(n_groups);
   HIP_TRY(hipMemsetAsync(d_moments, 0, n_blocks * M * sizeof(uint64_t), st));
   if (h_skipped) memset(h_skipped, 0, n_blocks * sizeof(fmh_sfs_skipped));
 
   // work items: at most item_rows rows each, never across a block; a block is cut into EQUAL items (a 5 000-row block into 2 x 2 500, not
   // 4 096 + 904: with the uneven cut 2 000 such blocks measured 3.2 ms against 2.1 ms with items of 1 024 or of 16 384 rows)
-  const long long opt_rows = options().fstat_item_rows.load(std::memory_order_relaxed);
-  const size_t item_rows = opt_rows <= 0 ? kFstatDefaultItemRows : std::min<size_t>((size_t)opt_rows, kFstatMaxItemRows);
+  const size_t item_rows = item_rows_of(options().fstat_item_rows, kFstatDefaultItemRows);
   std::vector<FstatItem> items;
   for (size_t b = 0; b < n_blocks; ++b) {
     const size_t rows = blocks[b].end - blocks[b].begin;
     if (rows == 0) continue;
     const size_t pieces = (rows + item_rows - 1) / item_rows;
-    if (items.size() + pieces > ((size_t)1 << 31)) return fail(FMH_ERR_UNSUPPORTED, "more than 2^31 work items: raise FMH_FSTAT_ITEM_ROWS");
+    FMH_TRY(check_item_count(items.size() + pieces, "FMH_FSTAT_ITEM_ROWS"));
     const size_t each = (rows + pieces - 1) / pieces;  // <= item_rows
     for (size_t r = blocks[b].begin; r < blocks[b].end; r += each)
       items.push_back(FstatItem{(unsigned long long)r, (uint32_t)std::min(each, blocks[b].end - r), (uint32_t)b});
@@ -126,10 +118,7 @@ extern "C" int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_ma
   const uint32_t n_entries = (uint32_t)ent_group.size(), n_vectors = vec_end - vec_begin;
 
   FstatArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   a.vec_begin = vec_begin;
   a.vec_end = vec_end;
   a.n_groups = G;
@@ -149,50 +138,30 @@ extern "C" int fmh_fstat_moments(const fmh_matrix* m, const uint8_t* h_column_ma
   void (*kernel)(const FstatArgs) = lanes4 ? (lds_masks ? fstat_kernel<4, true> : fstat_kernel<4, false>)
                                            : (lds_masks ? fstat_kernel<16, true> : fstat_kernel<16, false>);
   size_t grid = 0;
-  FMH_TRY(hap_grid(reinterpret_cast<const void*>(kernel), kFstatThreads, lds_bytes, items.size(), ws->cus, &grid));
+  FMH_TRY(persistent_grid(reinterpret_cast<const void*>(kernel), kFstatThreads, lds_bytes, items.size(), call.ws->cus, &grid));
 
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
   FstatItem* d_items = nullptr;
   uint32_t *d_off = nullptr, *d_group = nullptr;
   uint4* d_mask = nullptr;
-  FMH_TRY(scratch.get(&d_items, items.size()));
-  FMH_TRY(scratch.get(&d_off, ent_off.size()));
-  FMH_TRY(scratch.get(&d_group, ent_group.size()));
-  FMH_TRY(scratch.get(&d_mask, (size_t)n_entries));
-  HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(FstatItem), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_off, ent_off.data(), ent_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_group, ent_group.data(), ent_group.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_mask, ent_mask.data(), ent_mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  FMH_TRY(call.upload(items.data(), items.size(), &d_items));
+  FMH_TRY(call.upload(ent_off.data(), ent_off.size(), &d_off));
+  FMH_TRY(call.upload(ent_group.data(), ent_group.size(), &d_group));
+  FMH_TRY(call.upload(ent_mask.data(), (size_t)n_entries, &d_mask));  // four dwords per entry
   unsigned long long* d_skipped = nullptr;
-  if (h_skipped) {
-    FMH_TRY(scratch.get(&d_skipped, n_blocks * 2));
-    HIP_TRY(hipMemsetAsync(d_skipped, 0, n_blocks * 2 * sizeof(unsigned long long), st));
-  }
+  if (h_skipped) FMH_TRY(call.zeroed(n_blocks * 2, &d_skipped));
   a.items = d_items;
   a.ent_off = d_off;
   a.ent_group = d_group;
   a.ent_mask = d_mask;
   a.skipped = d_skipped;
 
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
+  FMH_TRY(call.start());
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kFstatThreads), lds_bytes, st, a);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+  FMH_TRY(call.stop());
   static_assert(sizeof(fmh_sfs_skipped) == 2 * sizeof(unsigned long long), "fmh_sfs_skipped is two u64");
   if (h_skipped) HIP_TRY(hipMemcpyAsync(h_skipped, d_skipped, n_blocks * sizeof(fmh_sfs_skipped), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  if (timing) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-  }
-  return FMH_OK;
+  return call.finish();
 }
 
 // ---- host only ---------------------------------------------------------------------------------------------------------------------------

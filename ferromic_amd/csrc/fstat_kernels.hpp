@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plane_rows.hpp"
 #include "sfs_kernels.hpp"  // sfs_load16, sfs_or128, sfs_andn128, sfs_any128; and128, popc128
 
 namespace fmh {
@@ -34,10 +35,7 @@ struct FstatItem {
   uint32_t block;
 };
 
-struct FstatArgs {
-  const uint8_t *p0, *p1, *p2, *pc;  // planes (p1 / p2 / pc may be null)
-  const uint8_t *row_gap, *row_hi;   // one byte per row or null (null = read the plane of every row)
-  size_t plane_pitch;
+struct FstatArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   uint32_t vec_begin, vec_end;       // the 16-byte vectors of a row that can hold a member of any group
   uint32_t n_groups;
   uint32_t n_entries;

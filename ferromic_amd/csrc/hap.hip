@@ -9,6 +9,7 @@
 #include "abi_internal.hpp"
 #include "hap_kernels.hpp"
 #include "hap_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -17,10 +18,8 @@ static_assert(sizeof(fmh_hap_window) == 24 && sizeof(HapWindow) == sizeof(fmh_ha
 
 namespace {
 
-struct Window { size_t begin, end; };
-
 // every refusal, in the header's order; none needs a device
-int check_args(const fmh_matrix* m, const fmh_groups* g, const Window* windows, size_t n_windows, const void* d_out, bool want_first) {
+int check_args(const fmh_matrix* m, const fmh_groups* g, const RowSpan* windows, size_t n_windows, const void* d_out, bool want_first) {
   if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
   if (!g) return fail(FMH_ERR_INVALID, "NULL groups");
   if (!windows) return fail(FMH_ERR_INVALID, "h_windows is NULL");
@@ -28,17 +27,14 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, const Window* windows, 
   if (g->n_groups != 1) return fail(FMH_ERR_INVALID, "the haplotype windows take exactly 1 group, got %d", g->n_groups);
   if (g->device != m->device || g->columns != m->columns) return fail(FMH_ERR_INVALID, "the groups were not made for this matrix");
   if (g->sizes[0] == 0) return fail(FMH_ERR_INVALID, "group 0 has no member");
-  for (size_t w = 0; w < n_windows; ++w)
-    if (windows[w].begin > windows[w].end || windows[w].end > m->variants)
-      return fail(FMH_ERR_INVALID, "rows [%zu, %zu) of window %zu exceed the matrix's %zu variants", windows[w].begin, windows[w].end, w, m->variants);
+  FMH_TRY(check_row_spans(windows, n_windows, "window", m->variants));
   if (n_windows == 0) return fail(FMH_ERR_INVALID, "n_windows is 0");
   if (g->sizes[0] > kHapMaxMembers)
     return fail(FMH_ERR_UNSUPPORTED, "a group of %llu members exceeds the %u the haplotype kernel holds on chip (fmh_haplotype_max_members)",
                 (unsigned long long)g->sizes[0], kHapMaxMembers);
   if (want_first && n_windows > ((size_t)1 << 32) / (size_t)g->sizes[0])
     return fail(FMH_ERR_UNSUPPORTED, "a partition table of %zu windows x %llu members exceeds 2^32 entries", n_windows, (unsigned long long)g->sizes[0]);
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the haplotype windows read the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
-  return FMH_OK;
+  return check_packed(m, "the haplotype windows read");
 }
 
 }  // namespace
@@ -47,13 +43,9 @@ extern "C" uint32_t fmh_haplotype_max_members(void) { return kHapMaxMembers; }
 
 extern "C" int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g, const uint64_t* h_windows, size_t n_windows, fmh_hap_window* d_out,
                                      uint32_t* d_first_or_null, void* stream) {
-  static_assert(sizeof(Window) == 2 * sizeof(uint64_t), "a window is two u64");
-  const Window* windows = reinterpret_cast<const Window*>(h_windows);
-  FMH_TRY(check_args(m, g, windows, n_windows, d_out, d_first_or_null != nullptr));
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
+  FMH_TRY(check_args(m, g, reinterpret_cast<const RowSpan*>(h_windows), n_windows, d_out, d_first_or_null != nullptr));
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
 
   // the members' columns, ascending: member rank -> column
   const uint32_t n = (uint32_t)g->sizes[0];
@@ -69,26 +61,18 @@ extern "C" int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g, c
   if (lds_bytes > (size_t)std::max(lds_max, 0))
     return fail(FMH_ERR_UNSUPPORTED, "a group of %u members needs %zu bytes of LDS, this device gives a workgroup %d", n, lds_bytes, lds_max);
 
-  // launch shape (hap_launch.hpp; the kernel's 44-46 VGPRs never bound the workgroups a CU holds, so LDS and thread slots decide)
-  const unsigned threads = hap_pick_threads(n, n_windows, ws->cus);
+  // launch shape (hap_launch.hpp, stat_call.hpp; the kernel's 44-46 VGPRs never bound the workgroups a CU holds, so LDS and thread slots decide)
+  const unsigned threads = hap_pick_threads(n, n_windows, call.ws->cus);
   size_t grid = 0;
-  FMH_TRY(hap_grid(nullptr, threads, lds_bytes, n_windows, ws->cus, &grid));
+  FMH_TRY(persistent_grid(nullptr, threads, lds_bytes, n_windows, call.ws->cus, &grid));
 
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
   uint32_t* d_cols = nullptr;
   unsigned long long* d_windows = nullptr;
-  FMH_TRY(scratch.get(&d_cols, cols.size()));
-  FMH_TRY(scratch.get(&d_windows, n_windows * 2));
-  HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_windows, h_windows, n_windows * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  FMH_TRY(call.upload(cols.data(), cols.size(), &d_cols));
+  FMH_TRY(call.upload(h_windows, n_windows * 2, &d_windows));
 
   HapArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   a.cols = d_cols;
   a.n = n;
   a.touch_first = (cols.front() >> 5) * 4;
@@ -104,21 +88,10 @@ extern "C" int fmh_haplotype_windows(const fmh_matrix* m, const fmh_groups* g, c
   if (lds_bytes > ((size_t)64 << 10))
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds_bytes, st, a);
+  FMH_TRY(call.start());
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds_bytes, call.st, a);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  if (timing) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-  }
-  return FMH_OK;
+  return call.finish();
 }
 
 extern "C" int fmh_haplotype_stats(const fmh_hap_window* h_windows, size_t n_windows, uint64_t n, fmh_hap_stats_out* h_out) {

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plane_rows.hpp"
+
 namespace fmh {
 
 // the record of include/ferromic_hip.h's fmh_hap_window
@@ -32,10 +34,7 @@ struct HapWindow {
   uint32_t top[3];
 };
 
-struct HapArgs {
-  const uint8_t *p0, *p1, *p2, *pc;  // planes (p1 / p2 / pc may be null)
-  const uint8_t *row_gap, *row_hi;   // one byte per row or null (null = read the plane of every row)
-  size_t plane_pitch;
+struct HapArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   const uint32_t* cols;              // [n]: the column of member rank r, ascending
   uint32_t n;
   uint32_t touch_first, touch_last;  // byte offsets of the first and last plane dword of a row that holds a member
@@ -46,14 +45,13 @@ struct HapArgs {
 };
 
 constexpr uint32_t kHapLdsHead = 128;       // dwords before the labels: 16 wave sums of the scan, 16 x 6 of the end-of-window reduction
-constexpr uint32_t kHapLdsPerCu = 160u << 10;
 // the largest group: head + n labels + 3 x ceil(n / 16) words (two bitmaps of 2 n bits, one prefix per bitmap word) within 160 KiB
 constexpr uint32_t kHapMaxMembers = 34304;
 
 __host__ __device__ constexpr uint32_t hap_pad4(uint32_t x) { return (x + 3u) & ~3u; }
 __host__ __device__ constexpr uint32_t hap_bitmap_words(uint32_t n) { return hap_pad4((n + 15u) / 16u); }
 __host__ __device__ constexpr size_t hap_lds_bytes(uint32_t n) { return ((size_t)kHapLdsHead + hap_pad4(n) + 3u * (size_t)hap_bitmap_words(n)) * 4u; }
-static_assert(hap_lds_bytes(kHapMaxMembers) <= kHapLdsPerCu, "the largest group fits one CU's LDS");
+static_assert(hap_lds_bytes(kHapMaxMembers) <= kLdsPerCu, "the largest group fits one CU's LDS");
 static_assert(kHapMaxMembers < 0xFFFFu, "labels, class sizes and member ranks are 16-bit halves of an LDS word");
 
 __device__ __forceinline__ void hap_top3_insert(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t v) {

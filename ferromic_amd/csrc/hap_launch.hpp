@@ -1,15 +1,10 @@
-// hap_launch.hpp — what the statistics on the persistent grid share on the host side: the launch shape of the two haplotype kernels (hap.hip:
-// one item = one window; ehh.hip: one item = one focal row and side) - threads per workgroup -, the size of the persistent grid (hap_grid:
-// also fstat.hip, qc.hip, assoc.hip) and the event timer of a call's kernels (KernelTimer: qc.hip, assoc.hip).  One rule in one place, so the
-// units cannot drift apart.
+// hap_launch.hpp — the threads per workgroup of the two haplotype kernels (hap.hip: one item = one window; ehh.hip: one item = one focal row
+// and side).  One rule in one place, so the two units cannot drift apart; what every statistic shares is in stat_call.hpp.
 #pragma once
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "abi_internal.hpp"
-#include "hap_kernels.hpp"
 
 namespace fmhi {
 
@@ -25,50 +20,5 @@ inline unsigned hap_pick_threads(uint32_t n, size_t n_items, int cus) {
   if (n_items < (size_t)std::max(cus, 1)) return n <= 1024 ? 256 : n <= 4096 ? 512 : 1024;
   return n <= 8192 ? 256 : n <= 16384 ? 512 : 1024;
 }
-
-// Workgroups of the persistent grid: the workgroups a CU holds by LDS and by its 2 048 thread slots (at most eight) - and, when
-// `kernel_or_null` is given, by the kernel's registers as the runtime reports them: a workgroup beyond what is resident starts only when
-// another has walked all its items, and then walks its own alone.  FMH_GRID_PER_CU / FMH_GRID_BLOCKS override; never more than the items.
-// `lds_bytes` is the DYNAMIC LDS of the launch; a kernel that declares its LDS statically passes it as `static_lds_bytes` (the occupancy query
-// reads it from the kernel itself and must not be told it twice).
-inline int hap_grid(const void* kernel_or_null, unsigned threads, size_t lds_bytes, size_t n_items, int cus, size_t* grid_out, size_t static_lds_bytes = 0) {
-  size_t per_cu = std::max<size_t>(1, std::min<size_t>({(size_t)8, fmh::kHapLdsPerCu / (lds_bytes + static_lds_bytes), (size_t)2048 / threads}));
-  if (kernel_or_null) {
-    int resident = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel_or_null, (int)threads, lds_bytes));
-    if (resident > 0) per_cu = std::min(per_cu, (size_t)resident);
-  }
-  const long long opt_per_cu = options().grid_per_cu.load(std::memory_order_relaxed);
-  if (opt_per_cu > 0) per_cu = (size_t)std::min<long long>(opt_per_cu, 32);
-  size_t grid = (size_t)std::max(cus, 1) * per_cu;
-  const long long opt_blocks = options().grid_blocks.load(std::memory_order_relaxed);
-  if (opt_blocks > 0) grid = (size_t)std::min<long long>(opt_blocks, 1 << 20);
-  *grid_out = std::min(grid, n_items);
-  return FMH_OK;
-}
-
-// HIP events around a call's kernels when fmh_timing_enable is on, added to the library's kernel time after the synchronise (qc.hip, assoc.hip)
-struct KernelTimer {
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool on = timing_enabled();
-  ~KernelTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-  int start(hipStream_t st) {
-    if (!on) return FMH_OK;
-    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], st));
-    return FMH_OK;
-  }
-  int stop(hipStream_t st) {
-    if (on) HIP_TRY(hipEventRecord(ev[1], st));
-    return FMH_OK;
-  }
-  int read() {
-    if (!on) return FMH_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-    return FMH_OK;
-  }
-};
 
 }  // namespace fmhi

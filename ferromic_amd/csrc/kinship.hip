@@ -13,6 +13,7 @@
 #include "pairwise_kernels.hpp"
 #include "gram_launch.hpp"
 #include "kin_kernels.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -24,17 +25,9 @@ extern "C" int fmh_kinship_counts(const fmh_matrix* m, const uint32_t* h_samples
   if (!out->d_both || !out->d_het_het || !out->d_ibs0 || !out->d_het_hom) return fail(FMH_ERR_INVALID, "a table of out is NULL");
   if (n_samples == 0) return fail(FMH_ERR_INVALID, "n_samples is 0");
   if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "kinship takes diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
-  if (h_samples_or_null) {
-    for (size_t i = 0; i < n_samples; ++i) {
-      if (h_samples_or_null[i] >= m->samples) return fail(FMH_ERR_INVALID, "sample %u (entry %zu) is outside the matrix's %zu samples", h_samples_or_null[i], i, m->samples);
-      if (i && h_samples_or_null[i] <= h_samples_or_null[i - 1]) return fail(FMH_ERR_INVALID, "the sample list is not strictly ascending at entry %zu", i);
-    }
-  } else if (n_samples > m->samples) {
-    return fail(FMH_ERR_INVALID, "n_samples %zu exceeds the matrix's %zu samples", n_samples, m->samples);
-  }
-  if (row_begin > m->variants || row_count > m->variants - row_begin)
-    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "kinship reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  FMH_TRY(check_samples(h_samples_or_null, n_samples, m->samples));
+  FMH_TRY(check_rows(row_begin, row_count, m->variants));
+  FMH_TRY(check_packed(m, "kinship reads"));
   const size_t n = n_samples;
   // a strictly ascending list that ends at n - 1 is 0 .. n-1: the identity takes the dword staging of the planes kernel, no list is uploaded
   const uint32_t* h_list = h_samples_or_null && h_samples_or_null[n - 1] != n - 1 ? h_samples_or_null : nullptr;
@@ -68,9 +61,7 @@ extern "C" int fmh_kinship_counts(const fmh_matrix* m, const uint32_t* h_samples
   std::lock_guard<std::mutex> busy(w->in_use);
   uint8_t* planes = nullptr;
   FMH_TRY(gram_planes(w, (n_pad_a + n_pad_w) * slab / gf.spb, &planes));
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  DeviceScratch scratch(m->device, st);
   unsigned long long *d_ga = nullptr, *d_ta = nullptr, *d_gw = nullptr, *d_rows = nullptr;
   uint32_t* d_samples = nullptr;
   FMH_TRY(scratch.get(&d_ga, na * na));

@@ -8,6 +8,7 @@
 
 #include "abi_internal.hpp"
 #include "ld_kernels.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -26,8 +27,7 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_
     if (g->n_groups != 1) return fail(FMH_ERR_INVALID, "linkage disequilibrium takes exactly one group, got %d", g->n_groups);
     if (g->device != m->device || g->columns != m->columns) return fail(FMH_ERR_INVALID, "the group was not made for this matrix");
   }
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "linkage disequilibrium reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
-  return FMH_OK;
+  return check_packed(m, "linkage disequilibrium reads");
 }
 
 // the band kernel over rows [row_begin, row_begin + row_count), enqueued on `st`, no synchronisation
@@ -57,10 +57,6 @@ int enqueue_band(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, siz
   a.d_tiles = (uint32_t)d_tiles;
   // a launch holds at most 2^30 tiles: whole row tiles per launch
   const size_t tiles_max = std::max<size_t>(((size_t)1 << 30) / d_tiles, 1);
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
   for (size_t done = 0; done < row_count;) {
     const size_t rows = std::min(row_count - done, tiles_max * kLdRows);
     a.row_begin = row_begin + done;
@@ -76,13 +72,6 @@ int enqueue_band(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, siz
     else hipLaunchKernelGGL(ld_band_kernel<false>, grid, dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     done += rows;
-  }
-  if (timing) {
-    HIP_TRY(hipEventRecord(ev[1], st));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
   }
   return FMH_OK;
 }
@@ -113,44 +102,43 @@ extern "C" int fmh_ld_band(const fmh_matrix* m, const fmh_groups* g, size_t row_
                            double threshold, const fmh_ld_band_out* d_out, uint32_t* d_site_n, uint32_t* d_site_alt, void* stream) {
   if (!d_out) return fail(FMH_ERR_INVALID, "d_out is NULL");
   FMH_TRY(check_args(m, g, row_begin, row_count, partner_end, band, threshold));
-  FMH_TRY(use_device(m->device));
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
   if (row_count == 0) return FMH_OK;
-  hipStream_t st = (hipStream_t)stream;
-  FMH_TRY(enqueue_band(m, g, row_begin, row_count, partner_end, band, threshold, *d_out, d_site_n, d_site_alt, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return FMH_OK;
+  FMH_TRY(call.start());
+  FMH_TRY(enqueue_band(m, g, row_begin, row_count, partner_end, band, threshold, *d_out, d_site_n, d_site_alt, call.st));
+  return call.finish();
 }
 
 extern "C" int fmh_ld_prune_chunked(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_t row_count, size_t window, double threshold,
                                     uint8_t* h_keep, size_t chunk_rows, void* stream) {
   if (row_count != 0 && !h_keep) return fail(FMH_ERR_INVALID, "h_keep is NULL");
-  const size_t end = m && row_count <= m->variants && row_begin <= m->variants - row_count ? row_begin + row_count : (size_t)-1;
-  if (m && end == (size_t)-1) return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
-  FMH_TRY(check_args(m, g, row_begin, row_count, end, window, threshold));
-  FMH_TRY(use_device(m->device));
+  if (m) FMH_TRY(check_rows(row_begin, row_count, m->variants));
+  const size_t end = row_begin + row_count;
+  FMH_TRY(check_args(m, g, row_begin, row_count, end, window, threshold));  // (a NULL matrix is its first refusal)
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
   if (row_count == 0) return FMH_OK;
   const size_t words = (window + 31) / 32;
   if (chunk_rows == 0) chunk_rows = std::max<size_t>(kLdPruneScratchBytes / (words * sizeof(uint32_t)), kLdRows);
   chunk_rows = std::min(chunk_rows, row_count);
-  hipStream_t st = (hipStream_t)stream;
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  hipStream_t st = call.st;
   uint32_t* d_over = nullptr;
-  FMH_TRY(scratch.get(&d_over, chunk_rows * words));
+  FMH_TRY(call.scratch.get(&d_over, chunk_rows * words));
   std::vector<uint32_t> h_over(chunk_rows * words);
   std::fill(h_keep, h_keep + row_count, (uint8_t)1);
   fmh_ld_band_out out{};
   out.over = d_over;
   for (size_t done = 0; done < row_count; done += chunk_rows) {
     const size_t rows = std::min(chunk_rows, row_count - done);
-    // pairs reach into the next chunks through partner_end = the end of the whole range
+    // pairs reach into the next chunks through partner_end = the end of the whole range; each chunk is one timed span
+    FMH_TRY(call.start());
     FMH_TRY(enqueue_band(m, g, row_begin + done, rows, end, window, threshold, out, nullptr, nullptr, st));
+    FMH_TRY(call.stop());
     HIP_TRY(hipMemcpyAsync(h_over.data(), d_over, rows * words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    FMH_TRY(call.finish());
     greedy_rows(h_over.data(), words, window, done, rows, row_count, h_keep);
   }
-  scratch.settled = true;
   return FMH_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "abi_internal.hpp"
 #include "pairwise_kernels.hpp"
 #include "gram_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -126,7 +127,7 @@ extern "C" int fmh_timing_read_gram(double* h_stage_ms) {
 extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, unsigned long long* d_diff,
                                         unsigned long long* d_both, void* stream) {
   if (!m || !d_diff || !d_both) return fail(FMH_ERR_INVALID, "NULL argument");
-  if (n_samples > m->samples) return fail(FMH_ERR_INVALID, "n_samples %zu exceeds the matrix's %zu samples", n_samples, m->samples);
+  FMH_TRY(check_samples(nullptr, n_samples, m->samples));
   if (m->ploidy > 127) return fail(FMH_ERR_UNSUPPORTED, "pairwise differences support ploidy <= 127 (int8 operands), got %zu", m->ploidy);
   FMH_TRY(use_device(m->device));
   if (n_samples < 2 || m->variants == 0) return FMH_OK;
@@ -156,9 +157,7 @@ extern "C" int fmh_pairwise_differences(const fmh_matrix* m, size_t n_samples, u
   uint8_t* planes = nullptr;
   FMH_TRY(gram_planes(w, (size_t)n_planes * n_pad * slab / spb, &planes));
   hipError_t e = hipSuccess;
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  DeviceScratch scratch(m->device, st);
   unsigned long long *d_gram = nullptr, *d_totals = nullptr;
   if (single) {
     const size_t gram_bytes = n_samples * n_samples * sizeof(unsigned long long), totals_bytes = n_samples * sizeof(unsigned long long);

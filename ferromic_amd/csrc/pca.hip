@@ -16,6 +16,7 @@
 
 #include "abi_internal.hpp"
 #include "pca_kernels.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -247,16 +248,13 @@ extern "C" int fmh_pca_eigen_host(double* h_matrix, size_t n, double* h_eigenval
 
 extern "C" int fmh_pca_scan_sites(const fmh_matrix* m, size_t row_begin, size_t row_count, uint32_t* d_alt_count, uint8_t* d_flags, void* stream) {
   if (!m || !d_alt_count || !d_flags) return fail(FMH_ERR_INVALID, "NULL argument");
-  if (row_begin > m->variants || row_count > m->variants - row_begin)
-    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
+  FMH_TRY(check_rows(row_begin, row_count, m->variants));
   FMH_TRY(use_device(m->device));
   if (row_count == 0) return FMH_OK;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((row_count + 3) / 4));
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
+  KernelTimer<> timer;
+  FMH_TRY(timer.start(st));
   if (use_packed(m)) {
     hipLaunchKernelGGL(pca_scan_packed_kernel, grid, dim3(256), 0, st, m->p0, m->p1, m->p2, m->pc, m->pc ? m->row_gap : nullptr,
                        (m->p1 || m->p2) ? m->row_hi : nullptr, m->plane_pitch, m->columns, row_begin, row_count, d_alt_count, d_flags);
@@ -266,10 +264,9 @@ extern "C" int fmh_pca_scan_sites(const fmh_matrix* m, size_t row_begin, size_t 
                        d_alt_count, d_flags);
   }
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+  FMH_TRY(timer.stop(st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (timing) { float ms = 0.0f; HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); g_pca_stage_ms[3] = ms; }
-  return FMH_OK;
+  return timer.elapsed(0, &g_pca_stage_ms[3]);
 }
 
 namespace {
@@ -315,9 +312,7 @@ int gram_impl(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, c
   size_t words_per_split = round_up((kwords + splits - 1) / splits, kPcaStageWords);
   splits = (kwords + words_per_split - 1) / words_per_split;
 
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  DeviceScratch scratch(m->device, st);
   unsigned long long *d_bits = nullptr, *d_kept = nullptr;
   double2* d_vals = nullptr;
   double* d_slabs = nullptr;
@@ -332,39 +327,30 @@ int gram_impl(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_kept, c
   HIP_TRY(hipMemcpyAsync(d_vals, vals.data(), vals_bytes, hipMemcpyHostToDevice, st));
 
   // measurement: events between the three kernels (fmh_timing_enable, read back with fmh_timing_read_pca)
-  const bool timing = timing_enabled();
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+  KernelTimer<4> timer;
   const dim3 tgrid((unsigned)kwords, (unsigned)((n_pad / 64 + 3) / 4));
-  if (timing) HIP_TRY(hipEventRecord(ev[0], st));
+  FMH_TRY(timer.start(st));
   if (packed)
     hipLaunchKernelGGL(pca_transpose_packed_kernel, tgrid, dim3(256), 0, st, m->p0, m->plane_pitch, d_kept, n_kept, (uint32_t)n_pad, d_bits);
   else
     hipLaunchKernelGGL(pca_transpose_bytes_kernel, tgrid, dim3(256), 0, st, m->data, m->pitch, m->columns, d_kept, n_kept, (uint32_t)n_pad, d_bits);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+  FMH_TRY(timer.mark(1, st));
   const double denom = (double)(n - 1);
   hipLaunchKernelGGL(pca_gram_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, st, d_bits, d_vals, (uint32_t)n_pad, (uint32_t)kwords,
                      (uint32_t)nt, (uint32_t)words_per_split, (uint32_t)n, denom, d_gram, d_slabs);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[2], st));
+  FMH_TRY(timer.mark(2, st));
   if (splits > 1) {
     const size_t threads = tiles * (size_t)kPcaTile * kPcaTile;
     hipLaunchKernelGGL(pca_slab_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, d_slabs, (uint32_t)tiles, (uint32_t)splits,
                        (uint32_t)nt, (uint32_t)n, denom, d_gram);
     HIP_TRY(hipGetLastError());
   }
-  if (timing) HIP_TRY(hipEventRecord(ev[3], st));
+  FMH_TRY(timer.stop(st));
   HIP_TRY(hipStreamSynchronize(st));
   scratch.settled = true;
-  if (timing) {
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      g_pca_stage_ms[i] = ms;
-    }
-  }
+  for (int i = 0; i < 3; ++i) FMH_TRY(timer.elapsed(i, &g_pca_stage_ms[i]));
   return FMH_OK;
 }
 }  // namespace
@@ -431,12 +417,8 @@ extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t
   std::vector<double> top(n_components * n), lambda(n_components);
   if (api) {
     std::lock_guard<std::mutex> one_at_a_time(g_solver_device_mutex[device & 63]);
-    const bool timing = timing_enabled();
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-    if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); }
-    DeviceScratch scratch;
-    scratch.device = device;
+    KernelTimer<> timer;
+    DeviceScratch scratch(device, nullptr);
     double *d_w = nullptr, *d_e = nullptr;
     rocblas_int* d_info = nullptr;
     FMH_TRY(scratch.get(&d_w, n));
@@ -445,13 +427,13 @@ extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t
     if (api->set_stream(handle, nullptr) != 0) return fail(FMH_ERR_HIP, "rocblas_set_stream failed");
     // the matrix is symmetric, so its row-major image is its column-major image; the eigenvectors come back as COLUMNS of a
     // column-major matrix = rows of the row-major view, eigenvalues ascending
-    if (timing) HIP_TRY(hipEventRecord(ev[0], nullptr));
+    FMH_TRY(timer.start(nullptr));
     const rocblas_status rs = api->dsyevd(handle, kEvectOriginal, kFillLower, (rocblas_int)n, d_gram, (rocblas_int)n, d_w, d_e, d_info);
     if (rs != 0) return fail(FMH_ERR_HIP, "rocsolver_dsyevd returned status %d", rs);
-    if (timing) HIP_TRY(hipEventRecord(ev[1], nullptr));
+    FMH_TRY(timer.stop(nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     scratch.settled = true;
-    if (timing) { float ms = 0.0f; HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); g_pca_stage_ms[4] = ms; }
+    FMH_TRY(timer.elapsed(0, &g_pca_stage_ms[4]));
     g_pca_stage_ms[5] = 2.0;
     rocblas_int info = 0;
     HIP_TRY(hipMemcpy(&info, d_info, sizeof info, hipMemcpyDeviceToHost));

@@ -165,7 +165,7 @@ AssociationScan association_scan(const py::object& variants, const py::object& p
                                  const py::object& region) {
   auto store = store_from_python(variants);
   if (store->S != 0 && store->P != 2) value_error("the association scan takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
-  const vector<uint32_t> list = kinship_samples(samples, store->first_sample_count());
+  const vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
   const AssocModel model = assoc_model(phenotypes, covariates, list.size());
   shared_ptr<const Store> sub = store;
   bool empty = store->S == 0;
@@ -195,7 +195,7 @@ AssociationScan population_association_scan(const Population& pop, const py::obj
     if (sides[s] == 3) list.push_back((uint32_t)s);
   const AssocModel model = assoc_model(phenotypes, covariates, list.size());
   if (count == 0) return association_over_rows(nullptr, 0, 0, list, model, {});
-  const LdRows rows = ld_rows_from_population(pop);
+  const ResidentRows rows = resident_rows_of(pop);
   const vector<int64_t>& all = pop.store->positions;
   vector<int64_t> positions(all.begin(), all.begin() + (std::ptrdiff_t)std::min(rows.rc, all.size()));
   return association_over_rows(rows.dm, rows.r0, rows.rc, list, model, std::move(positions));

@@ -102,7 +102,7 @@ EhhRequest ehh_parse_request(const py::object& focal, double min_ehh, const py::
 }
 
 // `resident` is asked (and the matrix uploaded) only when there is a focal row to scan
-HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& positions, size_t count, const std::function<LdRows()>& resident) {
+HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& positions, size_t count, const std::function<ResidentRows()>& resident) {
   HaplotypeScan out;
   out.n = n;
   out.has_pairs = req.curve;
@@ -132,7 +132,7 @@ HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& pos
   out.stats.resize(F);
   if (req.curve) out.pairs.assign(F * 4 * out.max_extent, 0);
   if (F) {
-    const LdRows rows = resident();
+    const ResidentRows rows = resident();
     const DevMatrix& dm = *rows.dm;
     vector<uint64_t> device_focal = out.focal;
     for (uint64_t& f : device_focal) f += rows.r0;
@@ -180,7 +180,7 @@ HaplotypeScan ehh_of_variants(const py::object& variants, const py::object& hapl
     sub = store_subset(store, idx);
   }
   return ehh_over_rows(n, req, sub->positions, (size_t)sub->S, [&] {
-    LdRows rows;
+    ResidentRows rows;
     rows.mask = mask;
     auto [dm, r0, rc] = sub->device_rows();
     rows.dm = dm; rows.r0 = r0; rows.rc = rc;
@@ -194,7 +194,7 @@ HaplotypeScan ehh_of_population(const Population& pop, const EhhRequest& req) {
   if (count == 0) return ehh_over_rows(pop.haplotypes.size(), req, {}, 0, nullptr);
   const vector<uint8_t> mask = sfs_population_mask(pop);
   const size_t n = hap_sample_size(pop.haplotypes, &mask);
-  return ehh_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), [&] { return ld_rows_from_population(pop); });
+  return ehh_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), [&] { return resident_rows_of(pop); });
 }
 
 void bind_ehh(py::module_& m, py::class_<Population, shared_ptr<Population>>& population) {

@@ -197,7 +197,7 @@ FStatistics f_statistics(const py::object& populations, const py::object& blocks
   else { runs.ranges = {(uint64_t)0, (uint64_t)rows}; runs.window_of = {0}; }
   const size_t n_runs = runs.window_of.size();
   if (n_runs == 0) return out;
-  const LdRows resident = ld_rows_from_population(first);
+  const ResidentRows resident = resident_rows_of(first);
   for (uint64_t& r : runs.ranges) r += resident.r0;
   const DevMatrix& dm = *resident.dm;
   vector<uint8_t> flat;

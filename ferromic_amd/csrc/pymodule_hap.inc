@@ -108,7 +108,7 @@ size_t hap_sample_size(const vector<Hap>& haps, const vector<uint8_t>* mask) {
 
 // `resident` is asked (and the matrix uploaded) only when some window holds a row: an empty window is one class of everyone
 HaplotypeWindows hap_over_rows(size_t n, const HapRequest& req, const vector<int64_t>& positions, size_t count, bool partition,
-                               const std::function<LdRows()>& resident) {
+                               const std::function<ResidentRows()>& resident) {
   HaplotypeWindows out;
   out.n = n;
   out.ranges = hap_row_ranges(req, positions, count);
@@ -127,7 +127,7 @@ HaplotypeWindows hap_over_rows(size_t n, const HapRequest& req, const vector<int
   bool any_row = false;
   for (size_t w = 0; w < n_windows; ++w) any_row = any_row || out.ranges[2 * w + 1] > out.ranges[2 * w];
   if (any_row) {
-    const LdRows rows = resident();
+    const ResidentRows rows = resident();
     vector<uint64_t> device_ranges = out.ranges;
     for (uint64_t& r : device_ranges) r += rows.r0;
     const DevMatrix& dm = *rows.dm;
@@ -166,7 +166,7 @@ HaplotypeWindows garud_h(const py::object& variants, const py::object& haplotype
     sub = store_subset(store, idx);
   }
   return hap_over_rows(n, req, sub->positions, (size_t)sub->S, partition, [&] {
-    LdRows rows;
+    ResidentRows rows;
     rows.mask = mask;
     auto [dm, r0, rc] = sub->device_rows();
     rows.dm = dm; rows.r0 = r0; rows.rc = rc;
@@ -181,7 +181,7 @@ HaplotypeWindows population_garud_h(const Population& pop, const py::object& win
   if (count == 0) return hap_over_rows(pop.haplotypes.size(), req, {}, 0, partition, nullptr);
   const vector<uint8_t> mask = sfs_population_mask(pop);
   const size_t n = hap_sample_size(pop.haplotypes, &mask);
-  return hap_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), partition, [&] { return ld_rows_from_population(pop); });
+  return hap_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), partition, [&] { return resident_rows_of(pop); });
 }
 
 void bind_hap(py::module_& m) {

@@ -1,5 +1,5 @@
 // pymodule_kinship.inc — ferromic.kinship, Population.kinship and the Kinship result (included inside pymodule_stats.inc's namespace, after
-// pymodule_ld.inc whose LdRows it reuses).  An addition to the reference's surface: it has no relatedness code; the definition is
+// the argument handling the statistics share).  An addition to the reference's surface: it has no relatedness code; the definition is
 // include/ferromic_hip.h's (fmh_kinship_counts, fmh_kinship_stats, fmh_kinship_unrelated).  The four tables are exact integers from the
 // device; kinship and IBS distance are computed from them on the host by the library; the GIL is released around the C calls.
 
@@ -31,27 +31,13 @@ struct Kinship {
   string repr() const { return "Kinship(samples=" + std::to_string(n()) + ", sites=" + std::to_string(sites.size()) + ")"; }
 };
 
-// the `sites` argument: None, or a boolean array with one entry per row in play
-vector<uint8_t> kinship_keep(const py::object& sites, size_t rows, bool* given) {
-  *given = !sites.is_none();
-  vector<uint8_t> keep;
-  if (!*given) return keep;
-  auto arr = py::array_t<bool, py::array::c_style | py::array::forcecast>::ensure(sites);
-  if (!arr || arr.ndim() != 1) value_error("sites must be a one-dimensional boolean array");
-  if ((size_t)arr.shape(0) != rows) value_error("sites has " + std::to_string(arr.shape(0)) + " entries for " + std::to_string(rows) + " rows");
-  keep.resize(rows);
-  const bool* p = arr.data();
-  for (size_t i = 0; i < rows; ++i) keep[i] = p[i] ? 1 : 0;
-  return keep;
-}
-
 Kinship kinship_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, vector<uint32_t> samples, const py::object& sites) {
   Kinship out;
   out.samples = std::move(samples);
   const size_t n = out.n();
   if (n == 0) value_error("at least one sample is required for kinship");
   bool masked = false;
-  const vector<uint8_t> keep = kinship_keep(sites, rc, &masked);
+  const vector<uint8_t> keep = site_mask_arg(sites, rc, &masked);
   for (size_t i = 0; i < rc; ++i)
     if (!masked || keep[i]) out.sites.push_back((int64_t)i);
   const size_t total = n * n;
@@ -79,27 +65,10 @@ Kinship kinship_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc,
   return out;
 }
 
-// the `samples` argument: None = every sample, else strictly ascending sample numbers below `limit`
-vector<uint32_t> kinship_samples(const py::object& samples, int64_t limit) {
-  vector<uint32_t> out;
-  if (samples.is_none()) {
-    for (int64_t s = 0; s < limit; ++s) out.push_back((uint32_t)s);
-    return out;
-  }
-  for (const py::handle& item : py::iter(samples)) {
-    if (!is_intlike(item)) raise(PyExc_TypeError, "samples must be integers");
-    const int64_t s = to_i64(item);
-    if (s < 0 || s >= limit) value_error("sample " + std::to_string(s) + " is outside the variants' " + std::to_string(limit) + " samples");
-    if (!out.empty() && (int64_t)out.back() >= s) value_error("samples must be strictly ascending");
-    out.push_back((uint32_t)s);
-  }
-  return out;
-}
-
 Kinship kinship(const py::object& variants, const py::object& samples, const py::object& sites, const py::object& region) {
   auto store = store_from_python(variants);
   if (store->S != 0 && store->P != 2) value_error("kinship takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
-  vector<uint32_t> list = kinship_samples(samples, store->first_sample_count());
+  vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
   shared_ptr<const Store> sub = store;
   bool empty = store->S == 0;
   if (!empty && !region.is_none()) {
@@ -126,7 +95,7 @@ Kinship population_kinship(const Population& pop, const py::object& sites) {
   for (size_t s = 0; s < sides.size(); ++s)
     if (sides[s] == 3) list.push_back((uint32_t)s);
   if (count == 0) return kinship_over_rows(nullptr, 0, 0, std::move(list), sites);
-  const LdRows rows = ld_rows_from_population(pop);
+  const ResidentRows rows = resident_rows_of(pop);
   return kinship_over_rows(rows.dm, rows.r0, rows.rc, std::move(list), sites);
 }
 

@@ -44,14 +44,9 @@ py::array_t<bool> ld_prune_rows(const DevMatrix& dm, const vector<uint8_t>& mask
   return out;
 }
 
-// the rows of `region` (every variant when None) of a variant list, resident: (matrix, first row, rows, column mask); rows == 0 = nothing to do
-struct LdRows {
-  shared_ptr<DevMatrix> dm;
-  size_t r0 = 0, rc = 0;
-  vector<uint8_t> mask;
-};
-LdRows ld_rows_from_variants(const py::object& variants, const vector<Hap>& haps, const py::object& region) {
-  LdRows out;
+// the rows of `region` (every variant when None) of a variant list; rows == 0 = nothing to do
+ResidentRows ld_rows_from_variants(const py::object& variants, const vector<Hap>& haps, const py::object& region) {
+  ResidentRows out;
   auto store = store_from_python(variants);
   if (store->S == 0) return out;
   shared_ptr<const Store> sub = store;
@@ -71,7 +66,7 @@ LdRows ld_rows_from_variants(const py::object& variants, const vector<Hap>& haps
 py::array_t<double> ld_r2(const py::object& variants, const py::object& haplotypes, int64_t max_sites_apart, const py::object& region) {
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   ld_validate(haps.size(), max_sites_apart, "max_sites_apart", nullptr);
-  const LdRows rows = ld_rows_from_variants(variants, haps, region);
+  const ResidentRows rows = ld_rows_from_variants(variants, haps, region);
   if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
   return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
 }
@@ -79,38 +74,21 @@ py::array_t<double> ld_r2(const py::object& variants, const py::object& haplotyp
 py::array_t<bool> ld_prune(const py::object& variants, const py::object& haplotypes, int64_t window_sites, double r2_threshold, const py::object& region) {
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   ld_validate(haps.size(), window_sites, "window_sites", &r2_threshold);
-  const LdRows rows = ld_rows_from_variants(variants, haps, region);
+  const ResidentRows rows = ld_rows_from_variants(variants, haps, region);
   if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
   return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
 }
 
-// a Population's own haplotypes over its resident matrix: the dense one of from_numpy, else the variant store's
-LdRows ld_rows_from_population(const Population& pop) {
-  LdRows out;
-  if (pop.dense) {
-    if (pop.dense->variants == 0) return out;
-    out.mask = pop.dense->mask_for(pop.haplotypes);
-    out.dm = pop.dense->device_matrix();
-    out.rc = out.dm->variants;
-    return out;
-  }
-  if (pop.store->S == 0) return out;
-  out.mask = pop.store->mask_for(pop.haplotypes, pop.store->first_sample_count());
-  auto [dm, r0, rc] = pop.store->device_rows();
-  out.dm = dm; out.r0 = r0; out.rc = rc;
-  return out;
-}
-
 py::array_t<double> population_ld_r2(const Population& pop, int64_t max_sites_apart) {
   ld_validate(pop.haplotypes.size(), max_sites_apart, "max_sites_apart", nullptr);
-  const LdRows rows = ld_rows_from_population(pop);
+  const ResidentRows rows = resident_rows_of(pop);
   if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
   return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
 }
 
 py::array_t<bool> population_ld_prune(const Population& pop, int64_t window_sites, double r2_threshold) {
   ld_validate(pop.haplotypes.size(), window_sites, "window_sites", &r2_threshold);
-  const LdRows rows = ld_rows_from_population(pop);
+  const ResidentRows rows = resident_rows_of(pop);
   if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
   return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
 }

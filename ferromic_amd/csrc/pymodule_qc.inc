@@ -100,7 +100,7 @@ GenotypeQC genotype_qc_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, siz
   out.has_hwe = hwe;
   out.has_f = inbreeding;
   bool masked = false;
-  const vector<uint8_t> keep = kinship_keep(sites, rc, &masked);
+  const vector<uint8_t> keep = site_mask_arg(sites, rc, &masked);
   const uint8_t* keep_ptr = masked ? keep.data() : nullptr;
   out.s_hom_ref.assign(n, 0); out.s_het.assign(n, 0); out.s_hom_alt.assign(n, 0);
   if (inbreeding) out.s_weighted.assign(n, 0);
@@ -143,7 +143,7 @@ GenotypeQC genotype_qc(const py::object& variants, const py::object& samples, co
                        bool inbreeding) {
   auto store = store_from_python(variants);
   if (store->S != 0 && store->P != 2) value_error("genotype QC takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
-  vector<uint32_t> list = kinship_samples(samples, store->first_sample_count());
+  vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
   shared_ptr<const Store> sub = store;
   bool empty = store->S == 0;
   if (!empty && !region.is_none()) {
@@ -170,7 +170,7 @@ GenotypeQC population_genotype_qc(const Population& pop, const py::object& sites
   for (size_t s = 0; s < sides.size(); ++s)
     if (sides[s] == 3) list.push_back((uint32_t)s);
   if (count == 0) return genotype_qc_over_rows(nullptr, 0, 0, std::move(list), sites, hwe, inbreeding);
-  const LdRows rows = ld_rows_from_population(pop);
+  const ResidentRows rows = resident_rows_of(pop);
   return genotype_qc_over_rows(rows.dm, rows.r0, rows.rc, std::move(list), sites, hwe, inbreeding);
 }
 

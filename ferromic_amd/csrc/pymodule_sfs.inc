@@ -1,6 +1,6 @@
 // pymodule_sfs.inc — ferromic.site_frequency_spectrum / joint_site_frequency_spectrum, Population.site_frequency_spectrum and the classes
-// SiteFrequencySpectrum / JointSiteFrequencySpectrum (included inside pymodule_stats.inc's namespace, after pymodule_ld.inc whose row
-// handling it shares).  An addition to the reference's surface: it has no site frequency spectrum; the definition is
+// SiteFrequencySpectrum / JointSiteFrequencySpectrum (included inside pymodule_stats.inc's namespace, after the row
+// handling the statistics share).  An addition to the reference's surface: it has no site frequency spectrum; the definition is
 // include/ferromic_hip.h's (fmh_sfs, fmh_sfs_joint, fmh_sfs_stats).  Counts come from the device, the GIL is released around the calls;
 // the statistics are fmh_sfs_stats on the host, so they work on any spectrum (from_counts) without a device.
 
@@ -141,7 +141,7 @@ SfsRuns sfs_runs(const vector<int64_t>& positions, size_t count, size_t r0, cons
 // the spectra of a group of n haplotypes over the windows (None: every row); positions = those of the `count` rows that `resident` says
 // where to find - it is asked (and the matrix uploaded) only when some window holds a row
 SiteFrequencySpectrum sfs_over_rows(size_t n, const vector<int64_t>& positions, size_t count, const optional<vector<Region>>& windows,
-                                    const std::function<LdRows()>& resident) {
+                                    const std::function<ResidentRows()>& resident) {
   SiteFrequencySpectrum out;
   out.n = n;
   out.windowed = windows.has_value();
@@ -156,7 +156,7 @@ SiteFrequencySpectrum sfs_over_rows(size_t n, const vector<int64_t>& positions, 
   else { runs.ranges = {(uint64_t)0, (uint64_t)count}; runs.window_of = {0}; }
   const size_t n_runs = runs.window_of.size();
   if (n_runs == 0) return out;
-  const LdRows rows = resident();
+  const ResidentRows rows = resident();
   for (uint64_t& r : runs.ranges) r += rows.r0;
   const DevMatrix& dm = *rows.dm;
   const shared_ptr<Groups> gp = groups_for(dm, {rows.mask});
@@ -204,7 +204,7 @@ SiteFrequencySpectrum site_frequency_spectrum(const py::object& variants, const 
     sub = store_subset(store, idx);
   }
   return sfs_over_rows(n, sub->positions, (size_t)sub->S, wins, [&] {
-    LdRows rows;
+    ResidentRows rows;
     rows.mask = mask;
     auto [dm, r0, rc] = sub->device_rows();
     rows.dm = dm; rows.r0 = r0; rows.rc = rc;
@@ -223,7 +223,7 @@ SiteFrequencySpectrum population_sfs(const Population& pop, const py::object& wi
   if (count == 0) return sfs_over_rows(pop.haplotypes.size(), {}, 0, wins, nullptr);
   const vector<uint8_t> mask = sfs_population_mask(pop);
   const size_t n = sfs_sample_size(pop.haplotypes, &mask);
-  return sfs_over_rows(n, pop.store->positions, std::min(count, pop.store->positions.size()), wins, [&] { return ld_rows_from_population(pop); });
+  return sfs_over_rows(n, pop.store->positions, std::min(count, pop.store->positions.size()), wins, [&] { return resident_rows_of(pop); });
 }
 
 JointSiteFrequencySpectrum joint_site_frequency_spectrum(const py::object& a, const py::object& b) {
@@ -234,7 +234,7 @@ JointSiteFrequencySpectrum joint_site_frequency_spectrum(const py::object& a, co
   if (!same_dense && !same_store)
     value_error("the joint site frequency spectrum needs two populations over ONE resident matrix: make both with with_haplotypes from one Population");
   const size_t count = p1->dense ? (size_t)p1->dense->variants : (size_t)p1->store->S;
-  LdRows r1, r2;
+  ResidentRows r1, r2;
   if (count != 0) {
     r1.mask = sfs_population_mask(*p1);
     r2.mask = sfs_population_mask(*p2);
@@ -244,7 +244,7 @@ JointSiteFrequencySpectrum joint_site_frequency_spectrum(const py::object& a, co
   out.n1 = count ? sfs_sample_size(p2->haplotypes, &r2.mask) : (sfs_sample_size(p2->haplotypes, nullptr), p2->haplotypes.size());
   out.counts.assign((out.n0 + 1) * (out.n1 + 1), 0);
   if (count == 0) return out;
-  r1 = ld_rows_from_population(*p1);
+  r1 = resident_rows_of(*p1);
   r2.mask = sfs_population_mask(*p2);
   const DevMatrix& dm = *r1.dm;
   const shared_ptr<Groups> gp = groups_for(dm, {r1.mask, r2.mask});

@@ -12,7 +12,7 @@
 
 #include "abi_internal.hpp"
 #include "qc_kernels.hpp"
-#include "hap_launch.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -20,7 +20,6 @@ using namespace fmhi;
 namespace {
 
 constexpr size_t kQcDefaultItemRows = 4096;
-constexpr size_t kQcMaxItemRows = (size_t)1 << 30;
 constexpr uint64_t kQcMaxStatGenotypes = (uint64_t)1 << 31;  // the estimators' integer products stay below 2^63
 
 }  // namespace
@@ -32,16 +31,8 @@ extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_sample
   if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
   if (n_samples == 0) return fail(FMH_ERR_INVALID, "n_samples is 0");
   if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "genotype QC takes diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
-  if (h_samples_or_null) {
-    for (size_t i = 0; i < n_samples; ++i) {
-      if (h_samples_or_null[i] >= m->samples) return fail(FMH_ERR_INVALID, "sample %u (entry %zu) is outside the matrix's %zu samples", h_samples_or_null[i], i, m->samples);
-      if (i && h_samples_or_null[i] <= h_samples_or_null[i - 1]) return fail(FMH_ERR_INVALID, "the sample list is not strictly ascending at entry %zu", i);
-    }
-  } else if (n_samples > m->samples) {
-    return fail(FMH_ERR_INVALID, "n_samples %zu exceeds the matrix's %zu samples", n_samples, m->samples);
-  }
-  if (row_begin > m->variants || row_count > m->variants - row_begin)
-    return fail(FMH_ERR_INVALID, "rows [%zu, %zu) exceed the matrix's %zu variants", row_begin, row_begin + row_count, m->variants);
+  FMH_TRY(check_samples(h_samples_or_null, n_samples, m->samples));
+  FMH_TRY(check_rows(row_begin, row_count, m->variants));
   const fmh_genotype_site_out site = site_or_null ? *site_or_null : fmh_genotype_site_out{nullptr, nullptr, nullptr};
   const fmh_genotype_sample_out sample = sample_or_null ? *sample_or_null : fmh_genotype_sample_out{nullptr, nullptr, nullptr, nullptr};
   const bool want_tracks = site.d_hom_ref || site.d_het || site.d_hom_alt;
@@ -49,7 +40,7 @@ extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_sample
   if (!want_tracks && !want_tables && !sample.d_weighted_called) return fail(FMH_ERR_INVALID, "every output is NULL");
   if (h_row_weight_or_null && !sample.d_weighted_called) return fail(FMH_ERR_INVALID, "row weights are given but d_weighted_called is NULL");
   if (!h_row_weight_or_null && sample.d_weighted_called) return fail(FMH_ERR_INVALID, "d_weighted_called is given but the row weights are NULL");
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "genotype QC reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  FMH_TRY(check_packed(m, "genotype QC reads"));
 
   const size_t n = n_samples;
   size_t kept = row_count;
@@ -75,38 +66,22 @@ extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_sample
   }
   for (size_t w = 1; w < selected.size(); ++w) rank_before[w] = rank_before[w - 1] + (uint32_t)__builtin_popcount(selected[w - 1]);
 
-  const long long opt_rows = options().qc_item_rows.load(std::memory_order_relaxed);
-  const size_t item_rows = opt_rows <= 0 ? kQcDefaultItemRows : std::min<size_t>((size_t)opt_rows, kQcMaxItemRows);
+  const size_t item_rows = item_rows_of(options().qc_item_rows, kQcDefaultItemRows);
   const size_t row_blocks = (row_count + item_rows - 1) / item_rows;
-  if (row_blocks * n_chunks > ((size_t)1 << 31)) return fail(FMH_ERR_UNSUPPORTED, "more than 2^31 work items: raise FMH_QC_ITEM_ROWS");
+  FMH_TRY(check_item_count(row_blocks * n_chunks, "FMH_QC_ITEM_ROWS"));
 
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
+  hipStream_t st = call.st;
   uint32_t *d_selected = nullptr, *d_rank = nullptr, *d_weight = nullptr;
   uint8_t* d_keep = nullptr;
-  FMH_TRY(scratch.get(&d_selected, selected.size()));
-  FMH_TRY(scratch.get(&d_rank, rank_before.size()));
-  HIP_TRY(hipMemcpyAsync(d_selected, selected.data(), selected.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_rank, rank_before.data(), rank_before.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (h_keep_or_null && (tables || weighted)) {
-    FMH_TRY(scratch.get(&d_keep, row_count));
-    HIP_TRY(hipMemcpyAsync(d_keep, h_keep_or_null, row_count, hipMemcpyHostToDevice, st));
-  }
-  if (weighted) {
-    FMH_TRY(scratch.get(&d_weight, row_count));
-    HIP_TRY(hipMemcpyAsync(d_weight, h_row_weight_or_null, row_count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
+  FMH_TRY(call.upload(selected.data(), selected.size(), &d_selected));
+  FMH_TRY(call.upload(rank_before.data(), rank_before.size(), &d_rank));
+  if (h_keep_or_null && (tables || weighted)) FMH_TRY(call.upload(h_keep_or_null, row_count, &d_keep));
+  if (weighted) FMH_TRY(call.upload(h_row_weight_or_null, row_count, &d_weight));
 
   QcArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   a.words = words;
   a.word_lanes = word_lanes;
   a.n_chunks = n_chunks;
@@ -123,8 +98,7 @@ extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_sample
   a.hom_ref = sample.d_hom_ref; a.het = sample.d_het; a.hom_alt = sample.d_hom_alt;
   a.weighted_called = sample.d_weighted_called;
 
-  KernelTimer timer;
-  FMH_TRY(timer.start(st));
+  FMH_TRY(call.start());
   if (want_tracks || tables) {
     // a row cut into column chunks has one writer per chunk: the tracks are zeroed and added to; otherwise they are stored
     if (want_tracks && n_chunks > 1)
@@ -133,21 +107,18 @@ extern "C" int fmh_genotype_counts(const fmh_matrix* m, const uint32_t* h_sample
     void (*kernel)(const QcArgs) = want_tracks ? (tables ? qc_count_kernel<true, true> : qc_count_kernel<true, false>) : qc_count_kernel<false, true>;
     const size_t lds_bytes = (size_t)qc_count_lds_dwords(word_lanes, tables) * sizeof(uint32_t);
     size_t grid = 0;
-    FMH_TRY(hap_grid(reinterpret_cast<const void*>(kernel), kQcThreads, lds_bytes, a.n_items, ws->cus, &grid));
+    FMH_TRY(persistent_grid(reinterpret_cast<const void*>(kernel), kQcThreads, lds_bytes, a.n_items, call.ws->cus, &grid));
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kQcThreads), lds_bytes, st, a);
     HIP_TRY(hipGetLastError());
   }
   if (weighted) {
     const size_t lds_bytes = (size_t)16 * word_lanes * sizeof(unsigned long long);
     size_t grid = 0;
-    FMH_TRY(hap_grid(reinterpret_cast<const void*>(qc_weighted_kernel), kQcThreads, lds_bytes, a.n_items, ws->cus, &grid));
+    FMH_TRY(persistent_grid(reinterpret_cast<const void*>(qc_weighted_kernel), kQcThreads, lds_bytes, a.n_items, call.ws->cus, &grid));
     hipLaunchKernelGGL(qc_weighted_kernel, dim3((unsigned)grid), dim3(kQcThreads), lds_bytes, st, a);
     HIP_TRY(hipGetLastError());
   }
-  FMH_TRY(timer.stop(st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  return timer.read();
+  return call.finish();
 }
 
 extern "C" int fmh_hwe_exact(const uint32_t* d_hom_ref, const uint32_t* d_het, const uint32_t* d_hom_alt, size_t n_sites, double* d_p, int device,
@@ -155,15 +126,12 @@ extern "C" int fmh_hwe_exact(const uint32_t* d_hom_ref, const uint32_t* d_het, c
   if (n_sites == 0) return FMH_OK;
   if (!d_hom_ref || !d_het || !d_hom_alt || !d_p) return fail(FMH_ERR_INVALID, "NULL argument");
   if ((n_sites + 255) / 256 > 0x7FFFFFFFu) return fail(FMH_ERR_UNSUPPORTED, "more than 2^39 sites in one call");
-  FMH_TRY(use_device(device));
-  hipStream_t st = (hipStream_t)stream;
-  KernelTimer timer;
-  FMH_TRY(timer.start(st));
-  hipLaunchKernelGGL(hwe_kernel, dim3((unsigned)((n_sites + 255) / 256)), dim3(256), 0, st, d_hom_ref, d_het, d_hom_alt, n_sites, d_p);
+  StatCall call;
+  FMH_TRY(call.begin(device, stream));
+  FMH_TRY(call.start());
+  hipLaunchKernelGGL(hwe_kernel, dim3((unsigned)((n_sites + 255) / 256)), dim3(256), 0, call.st, d_hom_ref, d_het, d_hom_alt, n_sites, d_p);
   HIP_TRY(hipGetLastError());
-  FMH_TRY(timer.stop(st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return timer.read();
+  return call.finish();
 }
 
 // ---- host only (no device).  The operation order is the header's; the unit is built with -ffp-contract=off ----------------------------------

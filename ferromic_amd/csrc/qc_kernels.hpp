@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plane_rows.hpp"
+
 namespace fmh {
 
 constexpr uint32_t kQcThreads = 256;
@@ -30,10 +32,7 @@ constexpr uint32_t kQcFlushBlocks = 31;    // 31 x 8 = 248 <= 255 rows of a lane
 constexpr uint32_t kQcMinWordLanes = 8;    // the transposed butterfly hands eight rows to eight lanes
 constexpr uint32_t kQcEven = 0x55555555u;
 
-struct QcArgs {
-  const uint8_t *p0, *p1, *p2, *pc;  // planes (p1 / p2 / pc may be null)
-  const uint8_t *row_gap, *row_hi;   // one byte per row or null (null = read the plane of every row)
-  size_t plane_pitch;
+struct QcArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   uint32_t words;                    // 32-bit words of a row that exist (plane_pitch / 4)
   uint32_t word_lanes;               // LW
   uint32_t n_chunks;                 // column chunks of LW words

@@ -9,6 +9,7 @@
 
 #include "abi_internal.hpp"
 #include "sfs_kernels.hpp"
+#include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -16,19 +17,15 @@ using namespace fmhi;
 namespace {
 
 constexpr size_t kSfsMaxBins = (size_t)1 << 28;          // bins of one call's table
-constexpr size_t kSfsLdsPerCu = (size_t)160 << 10;       // MI355X
 constexpr size_t kSfsDefaultItemRows = 4096;             // measured ahead of 1 024 and 16 384 at 10 M rows
-constexpr size_t kSfsMaxItemRows = (size_t)1 << 30;      // an LDS bin is 32 bits
 // the largest tile ONE 512-thread workgroup per CU can hold beside the kernel's head: eight waves resident at any n
-constexpr size_t kSfsMaxLdsBins = kSfsLdsPerCu / 4 - kSfsLdsHead;
+constexpr size_t kSfsMaxLdsBins = kLdsPerCu / 4 - kSfsLdsHead;
 // the default cap: the largest tile that still lets EIGHT 256-thread workgroups share a CU (a joint spectrum measured 2x faster at that
 // occupancy than with one 512-thread workgroup and a 160 KiB tile); a 1-D spectrum of 5 000 haplotypes fits whole
-constexpr size_t kSfsDefaultLdsBins = kSfsLdsPerCu / 8 / 4 - kSfsLdsHead;
-
-struct Window { size_t begin, end; };
+constexpr size_t kSfsDefaultLdsBins = kLdsPerCu / 8 / 4 - kSfsLdsHead;
 
 // every refusal that needs no device, in the header's order; *bins = one window's slice
-int check_args(const fmh_matrix* m, const fmh_groups* g, int want_groups, const void* d_sfs, const Window* windows, size_t n_windows,
+int check_args(const fmh_matrix* m, const fmh_groups* g, int want_groups, const void* d_sfs, const RowSpan* windows, size_t n_windows,
                bool windows_given, size_t* bins) {
   if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
   if (!g) return fail(FMH_ERR_INVALID, "NULL groups");
@@ -40,15 +37,13 @@ int check_args(const fmh_matrix* m, const fmh_groups* g, int want_groups, const 
   if (g->device != m->device || g->columns != m->columns) return fail(FMH_ERR_INVALID, "the groups were not made for this matrix");
   for (int p = 0; p < want_groups; ++p)
     if (g->sizes[p] == 0) return fail(FMH_ERR_INVALID, "group %d has no member", p);
-  for (size_t w = 0; w < n_windows; ++w)
-    if (windows[w].begin > windows[w].end || windows[w].end > m->variants)
-      return fail(FMH_ERR_INVALID, "rows [%zu, %zu) of window %zu exceed the matrix's %zu variants", windows[w].begin, windows[w].end, w, m->variants);
+  FMH_TRY(check_row_spans(windows, n_windows, "window", m->variants));
   if (n_windows == 0) return fail(FMH_ERR_INVALID, "n_windows is 0");
   size_t slice = (size_t)g->sizes[0] + 1;
   if (want_groups == 2) slice *= (size_t)g->sizes[1] + 1;  // both factors are below 2^32
   if (slice > kSfsMaxBins || n_windows > kSfsMaxBins / slice)
     return fail(FMH_ERR_UNSUPPORTED, "a table of %zu windows x %zu bins exceeds 2^28 bins", n_windows, slice);
-  if (!m->p0) return fail(FMH_ERR_UNSUPPORTED, "the site frequency spectrum reads the bit-packed image: call fmh_matrix_pack first (the matrix holds u8 rows only)");
+  FMH_TRY(check_packed(m, "the site frequency spectrum reads"));
   *bins = slice;
   return FMH_OK;
 }
@@ -72,22 +67,20 @@ void plan_tile(size_t budget, uint32_t n0, uint32_t n1, bool joint, SfsAxis* ax0
   *ax1 = l1 == (size_t)n1 + 1 ? whole(n1) : ends(n1, l1);
 }
 
-int run(const fmh_matrix* m, const fmh_groups* g, bool joint, const Window* windows, size_t n_windows, size_t bins, uint64_t* d_sfs,
+int run(const fmh_matrix* m, const fmh_groups* g, bool joint, const RowSpan* windows, size_t n_windows, size_t bins, uint64_t* d_sfs,
         fmh_sfs_skipped* h_skipped, void* stream) {
-  FMH_TRY(use_device(m->device));
-  Workspace* ws = nullptr;
-  FMH_TRY(workspace(m->device, &ws));
-  hipStream_t st = (hipStream_t)stream;
+  StatCall call;
+  FMH_TRY(call.begin(m->device, stream));
+  hipStream_t st = call.st;
   HIP_TRY(hipMemsetAsync(d_sfs, 0, n_windows * bins * sizeof(uint64_t), st));
   if (h_skipped) memset(h_skipped, 0, n_windows * sizeof(fmh_sfs_skipped));
 
   // work items: at most item_rows rows each, never across a window
-  long long opt_rows = options().sfs_item_rows.load(std::memory_order_relaxed);
-  const size_t item_rows = opt_rows <= 0 ? kSfsDefaultItemRows : std::min<size_t>((size_t)opt_rows, kSfsMaxItemRows);
+  const size_t item_rows = item_rows_of(options().sfs_item_rows, kSfsDefaultItemRows);
   std::vector<SfsItem> items;
   for (size_t w = 0; w < n_windows; ++w)
     for (size_t r = windows[w].begin; r < windows[w].end; r += item_rows) {
-      if (items.size() >= ((size_t)1 << 31)) return fail(FMH_ERR_UNSUPPORTED, "more than 2^31 work items: raise FMH_SFS_ITEM_ROWS");
+      FMH_TRY(check_item_count(items.size() + 1, "FMH_SFS_ITEM_ROWS"));
       items.push_back(SfsItem{(unsigned long long)r, (uint32_t)std::min(item_rows, windows[w].end - r), (uint32_t)w});
     }
   if (items.empty()) {
@@ -96,10 +89,7 @@ int run(const fmh_matrix* m, const fmh_groups* g, bool joint, const Window* wind
   }
 
   SfsArgs a{};
-  a.p0 = m->p0; a.p1 = m->p1; a.p2 = m->p2; a.pc = m->pc;
-  a.row_gap = m->pc ? m->row_gap : nullptr;
-  a.row_hi = (m->p1 || m->p2) ? m->row_hi : nullptr;
-  a.plane_pitch = m->plane_pitch;
+  set_plane_rows(a, m);
   const uint8_t* mask_bits = reinterpret_cast<const uint8_t*>(g->mask_bits);  // one bit per column, a group's row is mask_pitch / 8 bytes
   a.mask0 = mask_bits;
   a.mask1 = joint ? mask_bits + g->mask_pitch / 8 : mask_bits;
@@ -115,28 +105,21 @@ int run(const fmh_matrix* m, const fmh_groups* g, bool joint, const Window* wind
   // beyond that one 512-thread workgroup per CU - eight waves per CU either way.
   int lds_max = 0;
   HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device));
-  const size_t lds_cap = std::min<size_t>(kSfsLdsPerCu, (size_t)std::max(lds_max, 1024));
+  const size_t lds_cap = std::min<size_t>(kLdsPerCu, (size_t)std::max(lds_max, 1024));
   long long opt_bins = options().sfs_lds_bins.load(std::memory_order_relaxed);
   size_t budget = opt_bins <= 0 ? kSfsDefaultLdsBins : (size_t)std::min<long long>(opt_bins, (long long)kSfsMaxLdsBins);
   budget = std::max<size_t>(std::min(budget, lds_cap / 4 - kSfsLdsHead), 4);
   plan_tile(budget, (uint32_t)g->sizes[0], joint ? (uint32_t)g->sizes[1] : 0, joint, &a.ax0, &a.ax1);
   const size_t lds_bytes = ((size_t)a.ax0.L * a.ax1.L + kSfsLdsHead) * sizeof(uint32_t);
-  const bool wide = lds_bytes > kSfsLdsPerCu / 2;
+  const bool wide = lds_bytes > kLdsPerCu / 2;
   const unsigned threads = wide ? 512 : 256;
-  const size_t per_cu = wide ? 1 : std::min<size_t>(8, kSfsLdsPerCu / lds_bytes);
-  const unsigned grid = (unsigned)std::min<size_t>(items.size(), (size_t)std::max(ws->cus, 1) * per_cu);
+  const size_t per_cu = wide ? 1 : std::min<size_t>(8, kLdsPerCu / lds_bytes);
+  const unsigned grid = (unsigned)std::min<size_t>(items.size(), (size_t)std::max(call.ws->cus, 1) * per_cu);
 
-  DeviceScratch scratch;
-  scratch.device = m->device;
-  scratch.stream = st;
   SfsItem* d_items = nullptr;
-  FMH_TRY(scratch.get(&d_items, items.size()));
-  HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(SfsItem), hipMemcpyHostToDevice, st));
+  FMH_TRY(call.upload(items.data(), items.size(), &d_items));
   unsigned long long* d_skipped = nullptr;
-  if (h_skipped) {
-    FMH_TRY(scratch.get(&d_skipped, n_windows * 2));
-    HIP_TRY(hipMemsetAsync(d_skipped, 0, n_windows * 2 * sizeof(unsigned long long), st));
-  }
+  if (h_skipped) FMH_TRY(call.zeroed(n_windows * 2, &d_skipped));
   a.items = d_items;
   a.n_items = (uint32_t)items.size();
   a.bins = bins;
@@ -149,31 +132,20 @@ int run(const fmh_matrix* m, const fmh_groups* g, bool joint, const Window* wind
   if (lds_bytes > ((size_t)64 << 10))
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
 
-  const bool timing = timing_enabled();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } event_guard{ev};
-  if (timing) { for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i])); HIP_TRY(hipEventRecord(ev[0], st)); }
+  FMH_TRY(call.start());
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds_bytes, st, a);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+  FMH_TRY(call.stop());
   static_assert(sizeof(fmh_sfs_skipped) == 2 * sizeof(unsigned long long), "fmh_sfs_skipped is two u64");
   if (h_skipped) HIP_TRY(hipMemcpyAsync(h_skipped, d_skipped, n_windows * sizeof(fmh_sfs_skipped), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  if (timing) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    timing_add(ms);
-  }
-  return FMH_OK;
+  return call.finish();
 }
 
 }  // namespace
 
 extern "C" int fmh_sfs(const fmh_matrix* m, const fmh_groups* g, const uint64_t* h_windows, size_t n_windows, uint64_t* d_sfs,
                        fmh_sfs_skipped* h_skipped_or_null, void* stream) {
-  static_assert(sizeof(Window) == 2 * sizeof(uint64_t), "a window is two u64");
-  const Window* windows = reinterpret_cast<const Window*>(h_windows);
+  const RowSpan* windows = reinterpret_cast<const RowSpan*>(h_windows);
   size_t bins = 0;
   FMH_TRY(check_args(m, g, 1, d_sfs, windows, n_windows, h_windows != nullptr, &bins));
   return run(m, g, false, windows, n_windows, bins, d_sfs, h_skipped_or_null, stream);
@@ -182,7 +154,7 @@ extern "C" int fmh_sfs(const fmh_matrix* m, const fmh_groups* g, const uint64_t*
 extern "C" int fmh_sfs_joint(const fmh_matrix* m, const fmh_groups* g, size_t row_begin, size_t row_count, uint64_t* d_sfs,
                              fmh_sfs_skipped* h_skipped_or_null, void* stream) {
   // (a range whose end wraps is outside every matrix)
-  const Window window{row_begin, row_count <= std::numeric_limits<size_t>::max() - row_begin ? row_begin + row_count : std::numeric_limits<size_t>::max()};
+  const RowSpan window{row_begin, row_count <= std::numeric_limits<size_t>::max() - row_begin ? row_begin + row_count : std::numeric_limits<size_t>::max()};
   size_t bins = 0;
   FMH_TRY(check_args(m, g, 2, d_sfs, &window, 1, true, &bins));
   return run(m, g, true, &window, 1, bins, d_sfs, h_skipped_or_null, stream);

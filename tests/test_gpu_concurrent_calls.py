@@ -694,8 +694,8 @@ def test_refusals_stay_with_their_thread(dev):
         dm.close()
 
 
-# Read once per call, or every use from one snapshot, by reading hap_launch.hpp (FMH_HAP_THREADS, FMH_GRID_BLOCKS, FMH_GRID_PER_CU), sfs.hip,
-# fstat.hip, qc.hip (the three item-row options) and gram_launch.hpp / pairwise.hip (gram_format, gram_row_slab, gram_plan: the FMH_PD_* ones).
+# Read once per call, or every use from one snapshot, by reading hap_launch.hpp (FMH_HAP_THREADS), stat_call.hpp (FMH_GRID_BLOCKS,
+# FMH_GRID_PER_CU and, through item_rows_of, the item-row options of sfs.hip, fstat.hip, qc.hip) and gram_launch.hpp / pairwise.hip (gram_format, gram_row_slab, gram_plan: the FMH_PD_* ones).
 OPTION_VALUES = {
     "FMH_HAP_THREADS": ["64", "256", "512", "1024", None],
     "FMH_GRID_BLOCKS": ["3", None],
