@@ -23,6 +23,7 @@ from ._core import (  # noqa: E402,F401
     HudsonFstSite,
     JointSiteFrequencySpectrum,
     Kinship,
+    LogisticScan,
     PairwiseDifference,
     Population,
     SiteFrequencySpectrum,
@@ -47,6 +48,7 @@ from ._core import (  # noqa: E402,F401
     kinship,
     ld_prune,
     ld_r2,
+    logistic_scan,
     nsl,
     nucleotide_diversity,
     pairwise_differences,

@@ -242,6 +242,11 @@ SYMBOLS = {
     "fmh_assoc_sums": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "fmh_assoc_prepare": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _P(_sz), _vp]),
     "fmh_assoc_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _u64, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "fmh_assoc_homalt_sums": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "fmh_logistic_null": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_sz), _vp]),
+    "fmh_logistic_score": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _i, _vp]),
+    "fmh_logistic_score_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "fmh_logistic_stats": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

@@ -11,11 +11,13 @@
 #include <vector>
 
 #include "abi_internal.hpp"
+#include "assoc_host.hpp"
 #include "assoc_kernels.hpp"
 #include "stat_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
+using namespace fmh_host;  // assoc_host.hpp: the arithmetic shared with the logistic null model
 
 namespace {
 
@@ -116,40 +118,6 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
 // ---- host only (no device).  The operation order is the header's; the unit is built with -ffp-contract=off ----------------------------------
 namespace {
 
-double seq_dot(const double* a, const double* b, size_t n, size_t stride_a, size_t stride_b) {
-  double s = 0.0;
-  for (size_t i = 0; i < n; ++i) s += a[i * stride_a] * b[i * stride_b];
-  return s;
-}
-
-// column-major work copy: centred in place
-void centre(double* x, size_t n) {
-  double s = 0.0;
-  for (size_t i = 0; i < n; ++i) s += x[i];
-  const double mean = s / (double)n;
-  for (size_t i = 0; i < n; ++i) x[i] -= mean;
-}
-
-// x minus its projections on the `c` orthonormal columns of q, one after the other, the whole pass twice
-void project_off(double* x, const std::vector<double>& q, size_t c, size_t n) {
-  for (int pass = 0; pass < 2; ++pass)
-    for (size_t j = 0; j < c; ++j) {
-      const double* qj = q.data() + j * n;
-      const double d = seq_dot(qj, x, n, 1, 1);
-      for (size_t i = 0; i < n; ++i) x[i] -= d * qj[i];
-    }
-}
-
-// the largest e with max |v| * 2^e <= 2^30; 0 for a column of zeros
-int fixed_point_exponent(const double* x, size_t n) {
-  double mx = 0.0;
-  for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(x[i]));
-  if (mx == 0.0) return 0;
-  int ex = 0;
-  const double f = std::frexp(mx, &ex);  // mx = f * 2^ex, f in [0.5, 1)
-  return f == 0.5 ? 31 - ex : 30 - ex;
-}
-
 // the continued fraction of the incomplete beta function (modified Lentz), to a relative change below 1e-15
 double beta_cf(double a, double b, double x) {
   const double tiny = 1e-300;
@@ -210,36 +178,13 @@ extern "C" int fmh_assoc_prepare(const double* h_phenotypes, const double* h_cov
   // covariates: centre, orthogonalise against the kept columns (modified Gram-Schmidt, twice), drop or normalise
   std::vector<double> q;  // kept columns, column-major
   std::vector<double> x(n);
-  size_t c = 0;
-  for (size_t j = 0; j < cin; ++j) {
-    for (size_t i = 0; i < n; ++i) x[i] = h_covariates_or_null[i * cin + j];
-    centre(x.data(), n);
-    const double r0 = std::sqrt(seq_dot(x.data(), x.data(), n, 1, 1));
-    project_off(x.data(), q, c, n);
-    const double r = std::sqrt(seq_dot(x.data(), x.data(), n, 1, 1));
-    const bool dropped = r0 == 0.0 || r <= r0 * 0x1p-26;
-    if (h_dropped_or_null) h_dropped_or_null[j] = dropped ? 1 : 0;
-    if (dropped) continue;
-    for (size_t i = 0; i < n; ++i) x[i] /= r;
-    q.insert(q.end(), x.begin(), x.end());
-    ++c;
-  }
+  const size_t c = covariate_basis(h_covariates_or_null, n, cin, q, h_dropped_or_null);
   if (n < c + 3) return fail(FMH_ERR_INVALID, "n - c - 2 = %lld residual degrees of freedom: at least 1 is required", (long long)n - (long long)c - 2);
   if (c + P > kAssocMaxColumns) return fail(FMH_ERR_INVALID, "%zu kept covariates + %zu phenotypes exceed %u value columns", c, P, kAssocMaxColumns);
   const size_t K = c + P;
   *h_n_basis = c;
 
-  auto quantise = [&](const double* col, size_t k) {
-    const int e = fixed_point_exponent(col, n);
-    long long total = 0;
-    for (size_t i = 0; i < n; ++i) {
-      const int32_t v = (int32_t)std::rint(std::ldexp(col[i], e));
-      h_values[i * K + k] = v;
-      total += v;
-    }
-    h_exponent[k] = e;
-    h_total[k] = total;
-  };
+  auto quantise = [&](const double* col, size_t k) { quantise_column(col, n, h_values + k, K, h_exponent + k, h_total + k); };
   for (size_t j = 0; j < c; ++j) quantise(q.data() + j * n, j);
   for (size_t p = 0; p < P; ++p) {
     for (size_t i = 0; i < n; ++i) x[i] = h_phenotypes[i * P + p];

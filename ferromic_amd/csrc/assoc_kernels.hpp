@@ -62,8 +62,8 @@ __host__ __device__ inline uint32_t assoc_digit(int32_t v, uint32_t j) {
 }
 
 // B in MFMA operand order.  One thread per 16-byte vector.  rank[s] = the position of matrix sample s in the list or -1 (null: s itself
-// while s < n); values [n][K].
-__global__ __launch_bounds__(256) void assoc_digits_kernel(const int32_t* __restrict__ values, const int32_t* __restrict__ rank, uint32_t n,
+// while s < n); values [n][K].  `static`: logistic.hip includes this header too (as pairwise_kernels.hpp's plain kernels are for kinship.hip).
+static __global__ __launch_bounds__(256) void assoc_digits_kernel(const int32_t* __restrict__ values, const int32_t* __restrict__ rank, uint32_t n,
                                                            uint32_t covered, uint32_t K, uint32_t vgroups, size_t n_vectors, uint4* __restrict__ digits) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n_vectors) return;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void assoc_digits_kernel(const int32_t* __rest
 }
 
 // C of a matrix that is biallelic with nothing missing: every row's called sum is the column total
-__global__ __launch_bounds__(256) void assoc_fill_kernel(const long long* __restrict__ totals, uint32_t K, size_t count, long long* __restrict__ out) {
+static __global__ __launch_bounds__(256) void assoc_fill_kernel(const long long* __restrict__ totals, uint32_t K, size_t count, long long* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = totals[i % K];
 }

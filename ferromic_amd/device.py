@@ -902,6 +902,131 @@ def assoc_stats(dosage_sum, called_sum, hom_ref, het, hom_alt, total, exponent, 
     return out
 
 
+# ---- logistic association scan: score test from exact class sums ------------------------------------------------------------------------
+LOGISTIC_MAX_SAMPLES = 1 << 21
+LOGISTIC_STATS = ("chi2", "z", "p", "beta", "se")
+LOGISTIC_REASONS = ("fitted", "one_class", "not_converged", "pivot", "zero_weight", "basis_lost")   # FMH_LOGISTIC_* 0 .. 5
+
+
+@dataclass
+class LogisticNull:
+    values: List[np.ndarray]   # per phenotype batch [n][Pb * (c + 3)] int32: what one fmh_assoc_sums call takes
+    exponent: np.ndarray       # [P][c + 3] int32
+    total: np.ndarray          # [P][c + 3] int64
+    fitted: np.ndarray         # [P] bool
+    reason: np.ndarray         # [P] int32 (FMH_LOGISTIC_*)
+    iterations: np.ndarray     # [P] int32
+    n_cases: np.ndarray        # [P] uint64
+    n_basis: int               # c
+    dropped: np.ndarray        # [c_in] bool
+    batch: int                 # floor(64 / (c + 3)) phenotypes per batch
+
+
+def assoc_homalt_sums(m: DeviceMatrix, values, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None,
+                      stream=None, fill: Optional[int] = None) -> np.ndarray:
+    """fmh_assoc_homalt_sums over rows [row_begin, row_begin + row_count): H = sum over the called hom-alt genotypes of the selected samples
+    of values, [rows][K] int64.  `values` is [n][K] int32.  `fill` pre-fills the output with that byte (tests: every entry is written)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    if values.ndim != 2:
+        raise ValueError("values is [n][K]")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if values.shape[0] != n:
+        raise ValueError("values has one row per selected sample")
+    k = values.shape[1]
+    nbytes = max(8 * rows * k, 8)
+    d_h = DeviceBuffer(m.device, nbytes) if fill is None else DeviceBuffer.from_numpy(m.device, np.full(nbytes, fill, dtype=np.uint8))
+    _abi.check(_abi.load().fmh_assoc_homalt_sums(m._h, _ptr(samples), n, row_begin, rows, _ptr(values), k, d_h.ptr, stream))
+    return d_h.to_numpy(np.int64, rows * k).reshape(rows, k)
+
+
+def logistic_null(phenotypes, covariates=None) -> LogisticNull:
+    """fmh_logistic_null (host only): the null model of every case / control phenotype and its c + 3 value columns as i32 fixed point."""
+    y = np.ascontiguousarray(phenotypes, dtype=np.float64)
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    if y.ndim != 2:
+        raise ValueError("phenotypes is [n] or [n][P]")
+    n, p = y.shape
+    x = None
+    c_in = 0
+    if covariates is not None:
+        x = np.ascontiguousarray(covariates, dtype=np.float64)
+        if x.ndim != 2 or x.shape[0] != n:
+            raise ValueError("covariates is [n][c_in]")
+        c_in = x.shape[1]
+    values = np.zeros(max(n * p * (c_in + 3), 1), dtype=np.int32)
+    exponent = np.zeros(max(p * (c_in + 3), 1), dtype=np.int32)
+    total = np.zeros(max(p * (c_in + 3), 1), dtype=np.int64)
+    fitted, reason, iterations = np.zeros(max(p, 1), np.uint8), np.zeros(max(p, 1), np.int32), np.zeros(max(p, 1), np.int32)
+    n_cases = np.zeros(max(p, 1), dtype=np.uint64)
+    dropped = np.zeros(max(c_in, 1), dtype=np.uint8)
+    c = C.c_size_t(0)
+    _abi.check(_abi.load().fmh_logistic_null(_ptr(y), None if c_in == 0 else _ptr(x), n, p, c_in, _ptr(values), _ptr(exponent), _ptr(total), _ptr(fitted),
+                                             _ptr(reason), _ptr(iterations), _ptr(n_cases), C.byref(c), _ptr(dropped)))
+    w = int(c.value) + 3
+    batch = ASSOC_MAX_COLUMNS // w
+    tables = []
+    for first in range(0, p, batch):
+        pb = min(batch, p - first)
+        tables.append(values[n * w * first: n * w * (first + pb)].reshape(n, pb * w).copy())
+    return LogisticNull(tables, exponent[: p * w].reshape(p, w).copy(), total[: p * w].reshape(p, w).copy(), fitted[:p].astype(bool), reason[:p].copy(),
+                        iterations[:p].copy(), n_cases[:p].copy(), int(c.value), dropped[:c_in].astype(bool), batch)
+
+
+def _logistic_score_inputs(dosage_sum, called_sum, homalt_sum, hom_ref, het, hom_alt, total, exponent, n_basis):
+    h = np.ascontiguousarray(homalt_sum, dtype=np.int64)
+    tracks = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    rows = tracks[0].size
+    pb = h.size // rows if rows else (h.shape[1] if h.ndim == 2 else 1)
+    k = pb * (int(n_basis) + 3)
+    s = np.ascontiguousarray(dosage_sum, dtype=np.int64)
+    cs = np.ascontiguousarray(called_sum, dtype=np.int64)
+    total = np.ascontiguousarray(total, dtype=np.int64).reshape(-1)
+    exponent = np.ascontiguousarray(exponent, dtype=np.int32).reshape(-1)
+    if s.size != rows * k or cs.size != rows * k or h.size != rows * pb or total.size != k or exponent.size != k or any(a.size != rows for a in tracks):
+        raise ValueError("the sums are [rows][Pb * (c + 3)], the hom-alt sums [rows][Pb], the tracks [rows], total and exponent [Pb * (c + 3)]")
+    return s, cs, h, tracks, total, exponent, rows, pb
+
+
+def logistic_score_host(dosage_sum, called_sum, homalt_sum, hom_ref, het, hom_alt, total, exponent, n_basis: int):
+    """fmh_logistic_score_host (host only): (score, variance), each [rows][Pb] float64, of one phenotype batch."""
+    s, cs, h, tracks, total, exponent, rows, pb = _logistic_score_inputs(dosage_sum, called_sum, homalt_sum, hom_ref, het, hom_alt, total, exponent, n_basis)
+    score, variance = np.zeros((rows, pb)), np.zeros((rows, pb))
+    _abi.check(_abi.load().fmh_logistic_score_host(_ptr(s), _ptr(cs), _ptr(h), *[_ptr(a) for a in tracks], rows, _ptr(total), _ptr(exponent), int(n_basis),
+                                                   pb, _ptr(score), _ptr(variance)))
+    return score, variance
+
+
+def logistic_score(device: int, dosage_sum, called_sum, homalt_sum, hom_ref, het, hom_alt, total, exponent, n_basis: int, stream=None,
+                   fill: Optional[int] = None):
+    """fmh_logistic_score on device `device`: the same function as the host twin's, from device copies of the host arrays given."""
+    s, cs, h, tracks, total, exponent, rows, pb = _logistic_score_inputs(dosage_sum, called_sum, homalt_sum, hom_ref, het, hom_alt, total, exponent, n_basis)
+    if rows == 0:
+        return np.zeros((0, pb)), np.zeros((0, pb))
+    bufs = [DeviceBuffer.from_numpy(device, a) for a in (s, cs, h, *tracks)]
+    nbytes = 8 * rows * pb
+    out = [DeviceBuffer(device, nbytes) if fill is None else DeviceBuffer.from_numpy(device, np.full(nbytes, fill, dtype=np.uint8)) for _ in range(2)]
+    _abi.check(_abi.load().fmh_logistic_score(*[b.ptr for b in bufs], rows, _ptr(total), _ptr(exponent), int(n_basis), pb, out[0].ptr, out[1].ptr, device,
+                                              stream))
+    return tuple(o.to_numpy(np.float64, rows * pb).reshape(rows, pb) for o in out)
+
+
+def logistic_stats(score, variance, outputs=LOGISTIC_STATS) -> Dict[str, np.ndarray]:
+    """fmh_logistic_stats (host only): chi2, z, p, beta and se, shaped as `score`."""
+    u = np.ascontiguousarray(score, dtype=np.float64)
+    v = np.ascontiguousarray(variance, dtype=np.float64)
+    if u.shape != v.shape:
+        raise ValueError("score and variance have one shape")
+    out = {name: np.zeros(u.shape, dtype=np.float64) for name in outputs}
+    _abi.check(_abi.load().fmh_logistic_stats(_ptr(u), _ptr(v), u.size, *[_ptr(out[name]) if name in out else None for name in LOGISTIC_STATS]))
+    return out
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -771,8 +771,8 @@ int fmh_genotype_sample_stats(const uint64_t* h_hom_ref, const uint64_t* h_het, 
  *     cf the continued fraction by the modified Lentz method (floor 1e-300), iterated until a step changes it by less than 1e-15 relative.
  *   Outputs beta, se, t, p: f64 [rows][P]; each may be NULL.  Refusals (FMH_ERR_INVALID): P == 0; c + P > 64; n > 2^22 or n - c - 2 < 1; a
  *   NULL input with n_rows > 0.  n_rows == 0 is FMH_OK.
- * Not built: logistic regression, per-phenotype missing values (a NaN is refused), mixed models, dominant / recessive coding, sharding over
- *   devices (a caller splits rows), run_vcf wiring, u8 rows, more than 64 value columns per call.
+ * Not built: per-phenotype missing values (a NaN is refused), mixed models, dominant / recessive coding, sharding over devices (a caller
+ *   splits rows), run_vcf wiring, u8 rows, more than 64 value columns per call.  Case / control phenotypes: the next section.
  */
 int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
                    size_t row_begin, size_t row_count, const int32_t* h_values /* [n_samples][n_columns] */, size_t n_columns,
@@ -787,6 +787,110 @@ int fmh_assoc_stats(const long long* h_dosage_sum, const long long* h_called_sum
                     const long long* h_total, const int32_t* h_exponent /* [n_basis + n_phenotypes] each */, const double* h_yy /* [n_phenotypes] */,
                     uint64_t n_samples, size_t n_basis, size_t n_phenotypes,
                     double* h_beta, double* h_se, double* h_t, double* h_p /* [n_rows][n_phenotypes] each, or NULL */);   /* host only, no device */
+
+/* ---- logistic association scan: score test from exact class sums (an addition: the reference has none) -----------------------------------
+ * The association scan for case / control phenotypes: per site the score test of the genotype dosage in a logistic model with an intercept
+ * and covariates, the null model (covariates only) fitted once per phenotype on the host.  Matrix, samples, c_i(r), g_i(r), row ranges and
+ * the row tables are fmh_assoc_sums'.  With g~_i = g_i where the genotype is called and mu (the row's mean dosage) where it is not, the
+ * statistic of a row needs  sum_i g~_i r_i,  sum_i g~_i b_ij  and  sum_i w_i g~_i^2  for per-sample columns r, b_j, w of the null model.  The
+ * first two are S + mu (T - C) of fmh_assoc_sums.  The third is not linear in the dosage: g^2 = g + 2 [g = 2], so it is S + 2 H + mu^2 (T - C)
+ * of the w column with H the sum over the hom-alt genotypes.  The device returns integers only; every f64 follows from them in a fixed order.
+ *
+ * Hom-alt sums (fmh_assoc_homalt_sums).  Given V[n][K] (i32, host, row-major by sample), for every row r of the range and k < K:
+ *     H[r][k] = sum_i c_i(r) * [g_i(r) == 2] * V[i][k]
+ *   an exact `long long` device buffer [row_count][K], WRITTEN (not added); every entry has one writer.  Limits: 1 <= K <= 64, |V| <= 2^30,
+ *   n <= 2^21, so that |S + 2 H| <= 2 * 2^21 * 2^30 + 2 * 2^21 * 2^30 = 2^53 converts to f64 without rounding.  The contraction is
+ *   fmh_assoc_sums' (four signed base-256 digits on the int8 matrix cores, straight from the bit planes) with the operand
+ *   lo & hi & "both entries called and no upper-plane bit".  Enqueues on `stream` and synchronises it.
+ *   Refusals, all before any launch, are fmh_assoc_sums' in its order.  FMH_ERR_INVALID: NULL matrix, values or d_homalt_sum; n_samples == 0
+ *   or > 2^21; K outside 1..64; a value beyond +-2^30; a sample index out of range, or a list that is not strictly ascending (n_samples
+ *   beyond the matrix's samples without a list); a row range past the matrix.  FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix
+ *   without a packed image.  row_count == 0 is FMH_OK.  Options: FMH_ASSOC_ITEM_ROWS, FMH_GRID_PER_CU and FMH_GRID_BLOCKS govern this call
+ *   as they do fmh_assoc_sums, and change no result.
+ *
+ * Null model (fmh_logistic_null, host, no device).  h_phenotypes f64 [n][P], every entry exactly 0.0 (control) or 1.0 (case);
+ * h_covariates_or_null f64 [n][c_in], both in the order of the selected samples.  The operation order is fixed, so that a plain Python loop
+ * over floats reproduces every integer (the library is built with -ffp-contract=off; exp, log and erfc are the C library's).  A
+ * "sequential" sum starts from 0.0 and adds in ascending index order.
+ *   1. Covariates: centred and orthonormalised exactly as fmh_assoc_prepare's steps 1 and 2, with the same drop rule and the same
+ *      h_dropped_or_null report; c = the number kept, q_j the kept columns.
+ *   2. Design, d = c + 1 columns: x_i0 = 1.0 / sqrt((double)n) for every i, x_ij = q_{j-1}(i) for j = 1 .. c.
+ *   3. Null fit of a phenotype y (Newton / IRLS, no step halving).  n_cases = the number of y_i == 1.0.  n_cases == 0 or == n: not fitted,
+ *      reason FMH_LOGISTIC_ONE_CLASS, 0 steps.  Start (the intercept-only fit): beta_0 = log((double)n_cases / (double)(n - n_cases)) / x_00,
+ *      beta_j = 0.0 otherwise.  Then steps s = 1, 2, .. 25:
+ *        a. per sample eta_i = sequential sum over j of x_ij * beta_j;  mu_i = 1.0 / (1.0 + exp(-eta_i));  w_i = mu_i * (1.0 - mu_i).  The first
+ *           w_i that is not > 0.0: not fitted, FMH_LOGISTIC_ZERO_WEIGHT (iterations = the steps completed before).
+ *        b. gradient g_j = sequential sum over i of x_ij * (y_i - mu_i); Hessian, for k <= j, A_jk = sequential sum over i of (x_ij * w_i) * x_ik.
+ *        c. Cholesky A = L L^T: for j = 0 .. c, for k = 0 .. j: s = A_jk, then s = s - L_jm * L_km for m = 0 .. k-1 in that order; k < j:
+ *           L_jk = s / L_kk; k == j: s not > 0.0: not fitted, FMH_LOGISTIC_PIVOT; else L_jj = sqrt(s).
+ *        d. forward, j = 0 .. c: s = g_j, s = s - L_jm * z_m for m = 0 .. j-1, z_j = s / L_jj.  Backward, j = c .. 0: s = z_j,
+ *           s = s - L_mj * delta_m for m = j+1 .. c ascending, delta_j = s / L_jj.
+ *        e. beta_j = beta_j + delta_j; iterations = s.  Every |delta_j| finite and the largest < 1e-8: converged - mu and w are recomputed
+ *           from the final beta as in a. (a w_i not > 0.0: FMH_LOGISTIC_ZERO_WEIGHT) and the fit ends.
+ *      25 steps without convergence: not fitted, FMH_LOGISTIC_NOT_CONVERGED.  (A phenotype that a covariate separates ends in one of the
+ *      last three reasons; which one is decided by this order alone.)
+ *   4. Whitened basis of a fitted phenotype.  For j = 0 .. c in order: z_i = sqrt(w_i) * x_ij; r0 = sqrt(sequential sum of z_i * z_i); then,
+ *      twice over, for each u already kept, in the order kept: t = sequential sum of u_i * z_i, z_i = z_i - t * u_i; r = sqrt(sequential sum
+ *      of z_i * z_i); r0 == 0 or r <= r0 * 2^-26: not fitted, FMH_LOGISTIC_BASIS_LOST; else u_j(i) = z_i / r.  (No centring here.)
+ *   5. Value columns of phenotype p, W = c + 3 of them: b_j(i) = sqrt(w_i) * u_j(i) for j = 0 .. c; then r_i = y_i - mu_i; then w_i.  Each is
+ *      turned into i32 fixed point with its exponent and exact i64 total by fmh_assoc_prepare's step 4.  A phenotype that is not fitted has
+ *      zeros in all W columns, exponents and totals.
+ *   6. Layout.  B = floor(64 / W) phenotypes form a batch; batch t holds phenotypes tB .. min(P, tB + B) - 1, Pb of them.  Its values are
+ *      one [n][Pb * W] i32 table (row-major by sample, phenotype after phenotype within a row) at h_values + n * W * B * t: exactly the
+ *      h_values / n_columns = Pb * W of one fmh_assoc_sums call.  h_exponent and h_total are [P][W]; those of batch t start at entry W * B * t.
+ *      h_values must hold n * P * (c_in + 3) entries, h_exponent and h_total P * (c_in + 3); n * P * W and P * W are written.
+ *      Per phenotype: h_fitted (1 / 0), h_reason (FMH_LOGISTIC_*), h_iterations, h_n_cases.  *h_n_basis = c.
+ *   Refusals (FMH_ERR_INVALID): a NULL pointer (h_dropped_or_null excepted; h_covariates_or_null when c_in == 0); P == 0; n == 0 or
+ *   n > 2^21; a non-finite covariate; a phenotype entry other than 0.0 or 1.0; c + 3 > 64; n < c + 3.
+ *
+ * Score and variance (fmh_logistic_score on the device, fmh_logistic_score_host its twin; ONE function compiled for both, bitwise equal).
+ * For one batch of Pb phenotypes, K = Pb * W: S, C [rows][K] from fmh_assoc_sums on the batch's values; H [rows][Pb] from
+ * fmh_assoc_homalt_sums on the batch's Pb w columns ([n][Pb]); the three u32 QC tracks of the same rows and samples; T[K], e[K]; c; Pb.
+ * Missing genotypes are mean-imputed, as in the linear scan.  Per row:
+ *     N = hom_ref + het + hom_alt;  n_alt = het + 2 * hom_alt;  mu = (double)n_alt / (double)N
+ *   and per phenotype p, with o = p * W  (T_k - C_k and S_k + 2 H_p in i64):
+ *     a_j = ldexp((double)S[o+j] + mu * (double)(T[o+j] - C[o+j]), -e[o+j])                                   j = 0 .. c
+ *     U   = the same expression at column o + c + 1
+ *     qq  = ldexp((double)(S[o+c+2] + 2 * H[p]) + (mu * mu) * (double)(T[o+c+2] - C[o+c+2]), -e[o+c+2])
+ *     Vr  = qq - a_0 * a_0 - a_1 * a_1 - ... - a_c * a_c                                                      (subtracted in that order)
+ *   score[r][p] = U, variance[r][p] = Vr: f64 [rows][Pb], WRITTEN.  N == 0, n_alt == 0 or n_alt == 2N (a site without variation carries no
+ *   test; an integer rule): a quiet NaN in both.  fmh_logistic_score runs one thread per (row, phenotype) with 64-bit indices, uploads T and
+ *   e, enqueues on `stream` and synchronises it.
+ *   Refusals: FMH_ERR_INVALID for Pb == 0 or Pb * (c + 3) > 64, then - unless n_rows == 0, which is FMH_OK - for a NULL pointer;
+ *   FMH_ERR_UNSUPPORTED for more than 2^39 (row, phenotype) pairs in one device call.
+ *
+ * Statistics (fmh_logistic_stats, host, no device).  Per entry of U and Vr:
+ *     chi2 = U * U / Vr      z = U / sqrt(Vr)      p = erfc(sqrt(chi2 / 2.0))      beta = U / Vr      se = 1.0 / sqrt(Vr)
+ *   p is the upper tail of chi-square with one degree of freedom.  beta and se are the ONE-STEP, score-based estimates of the log odds ratio
+ *   per allele (the first Newton step from the null), not a Wald fit: they agree with it for small effects only.  All five are a quiet NaN
+ *   where Vr is not > 0 or an input is NaN.  Each output pointer may be NULL; count == 0 is FMH_OK; a NULL input FMH_ERR_INVALID.
+ * Not built: Wald and Firth estimates, the saddle-point correction for unbalanced case / control, per-phenotype missing values, mixed
+ *   models, sharding over devices (a caller splits rows), run_vcf wiring, u8 rows.
+ */
+#define FMH_LOGISTIC_FITTED 0
+#define FMH_LOGISTIC_ONE_CLASS 1      /* no case or no control */
+#define FMH_LOGISTIC_NOT_CONVERGED 2  /* 25 Newton steps without max |delta| < 1e-8 */
+#define FMH_LOGISTIC_PIVOT 3          /* a Cholesky pivot that is not > 0 */
+#define FMH_LOGISTIC_ZERO_WEIGHT 4    /* some w_i = mu_i (1 - mu_i) is not > 0 */
+#define FMH_LOGISTIC_BASIS_LOST 5     /* a column of the whitened design is collinear */
+int fmh_assoc_homalt_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */,
+                          size_t n_samples, size_t row_begin, size_t row_count, const int32_t* h_values /* [n_samples][n_columns] */,
+                          size_t n_columns, long long* d_homalt_sum /* [row_count][n_columns], device, written */, void* stream);
+int fmh_logistic_null(const double* h_phenotypes /* [n][n_phenotypes], 0.0 or 1.0 */, const double* h_covariates_or_null /* [n][n_covariates] */,
+                      size_t n, size_t n_phenotypes, size_t n_covariates, int32_t* h_values /* n * n_phenotypes * (n_covariates + 3) entries */,
+                      int32_t* h_exponent, long long* h_total /* n_phenotypes * (n_covariates + 3) entries each */, uint8_t* h_fitted,
+                      int32_t* h_reason, int32_t* h_iterations, uint64_t* h_n_cases /* [n_phenotypes] each */, size_t* h_n_basis,
+                      uint8_t* h_dropped_or_null /* [n_covariates] */);   /* host only, no device */
+int fmh_logistic_score(const long long* d_dosage_sum, const long long* d_called_sum /* [n_rows][n_phenotypes * (n_basis + 3)] each */,
+                       const long long* d_homalt_sum /* [n_rows][n_phenotypes] */, const uint32_t* d_hom_ref, const uint32_t* d_het,
+                       const uint32_t* d_hom_alt /* [n_rows] each */, size_t n_rows, const long long* h_total,
+                       const int32_t* h_exponent /* [n_phenotypes * (n_basis + 3)] each, host */, size_t n_basis, size_t n_phenotypes,
+                       double* d_score, double* d_variance /* [n_rows][n_phenotypes] each, device, written */, int device, void* stream);
+int fmh_logistic_score_host(const long long* h_dosage_sum, const long long* h_called_sum, const long long* h_homalt_sum, const uint32_t* h_hom_ref,
+                            const uint32_t* h_het, const uint32_t* h_hom_alt, size_t n_rows, const long long* h_total, const int32_t* h_exponent,
+                            size_t n_basis, size_t n_phenotypes, double* h_score, double* h_variance);   /* host only, no device */
+int fmh_logistic_stats(const double* h_score, const double* h_variance, size_t count, double* h_chi2, double* h_z, double* h_p, double* h_beta,
+                       double* h_se /* [count] each, or NULL */);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
