@@ -762,6 +762,16 @@ extern "C" int fmh_matrix_download(const fmh_matrix* m, uint8_t* h_data, uint64_
     if (e == hipSuccess) e = hipMemcpy(h_missing, d_words, words * 8, hipMemcpyDeviceToHost);
     (void)hipFree(d_words);
     if (e != hipSuccess) return fail(FMH_ERR_HIP, "missing-mask download failed: %s", hipGetErrorString(e));
+    // byte rows keep whatever their writer put under a missing entry (the rows of fmh_matrix_wrap are the caller's, fmh_matrix_create on the u8
+    // layout copies the host's): the header promises 0 there whichever route built the matrix, as the unpack of a packed image gives
+    if (m->data) {
+      const size_t entries = m->variants * (size_t)m->columns;
+      for (size_t w = 0; w < words; ++w)
+        for (uint64_t bits = h_missing[w]; bits; bits &= bits - 1) {
+          const size_t idx = w * 64 + (size_t)__builtin_ctzll(bits);
+          if (idx < entries) h_data[idx] = 0;
+        }
+    }
   }
   return FMH_OK;
 }

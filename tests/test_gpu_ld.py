@@ -4,7 +4,8 @@ threshold words included - padding bits of the last word zero.
 
 Shapes are the smallest at which each part of the kernel can go wrong: a partial last dword and last 16-byte vector, one and several K
 slabs (256 bytes of a row per slab when nothing is missing, 128 otherwise), more than 65 535 columns, partial row tiles and d tiles,
-partners beyond the rows asked for and beyond the matrix, bands around the 32-bit word and the 64-wide tile.
+partners beyond the rows asked for and beyond the matrix, bands around the 32-bit word and the 64-wide tile.  The ways a matrix can be
+made (a foreign plane pitch, wrapped rows with junk padding, the generator, a re-pack in place) are covered by tests/test_gpu_cohort_fuzz.py.
 """
 
 import functools
