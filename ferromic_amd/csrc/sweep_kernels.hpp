@@ -577,6 +577,11 @@ __device__ __forceinline__ uint4 mask_vec(const void* base, uint32_t idx) {
   else return reinterpret_cast<const uint4*>(base)[idx];
 }
 
+// The called bits of a byte row's last 16-column vector that are entries of the row.  The bits behind them are padding, and on a wrapped matrix
+// (fmh_matrix_wrap) they are the caller's: whatever counts called entries over ALL columns without a group mask (n_all) must not count them -
+// a row with no called entry would else pass for one that has some, and W&C would report it as lacking variance instead of data.
+__device__ __forceinline__ uint32_t called_tail16(uint32_t columns) { return 0xFFFFu >> ((16u - (columns & 15u)) & 15u); }
+
 // Biallelic row: alt[p] = sum of allele bytes over called members, n[p] = called members.
 // The row is consumed in batches of U vectors per lane: the U global loads are issued back to back
 // (U KiB in flight per wave) before the first dot4, so memory-level parallelism does not depend on
@@ -591,6 +596,7 @@ __device__ __forceinline__ void count_row_biallelic(const MatrixView& mv, const 
   for (int p = 0; p < P; ++p) { alt[p] = 0; n[p] = 0; }
   n_all = 0;
   const uint32_t last = mv.nvec - 1;
+  const uint32_t tail16 = called_tail16(mv.columns);
   for (uint32_t v0 = gl; v0 < nvec_pad; v0 += 16 * U) {
     uint4 g[U];
     uint32_t bits16[U];
@@ -607,7 +613,7 @@ __device__ __forceinline__ void count_row_biallelic(const MatrixView& mv, const 
       uint4 cb;
       if (MISSING) {
         cb = called_bytes(bits16[u]);
-        if (NEED_ALL) n_all += v <= last ? __builtin_popcount(bits16[u]) : 0;
+        if (NEED_ALL) n_all += v < last ? __builtin_popcount(bits16[u]) : (v == last ? __builtin_popcount(bits16[u] & tail16) : 0);
       }
 #pragma unroll
       for (int p = 0; p < P; ++p) {
@@ -867,6 +873,7 @@ __device__ __forceinline__ void count_row_planes(const MatrixView& mv, const voi
   n_all = 0;
   allele_or = 0;
   const uint32_t last = mv.nvec - 1;
+  const uint32_t tail16 = called_tail16(mv.columns);
   for (uint32_t v0 = gl; v0 < nvec_pad; v0 += 16 * U) {
     uint4 g[U];
     uint32_t bits16[U];
@@ -885,7 +892,7 @@ __device__ __forceinline__ void count_row_planes(const MatrixView& mv, const voi
       uint4 cb = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
       if (MISSING) {
         cb = called_bytes(bits16[u]);
-        n_all += inside ? __builtin_popcount(bits16[u]) : 0;
+        n_all += v < last ? __builtin_popcount(bits16[u]) : (inside ? __builtin_popcount(bits16[u] & tail16) : 0);
         x.x &= cb.x * 0xFFu; x.y &= cb.y * 0xFFu; x.z &= cb.z * 0xFFu; x.w &= cb.w * 0xFFu;
       }
       allele_or |= inside ? or_bytes(x.x | x.y | x.z | x.w) : 0u;

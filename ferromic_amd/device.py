@@ -309,13 +309,13 @@ class DiversityResult:
     distinct: np.ndarray
 
 
-def diversity_sites(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None) -> DiversityResult:
+def diversity_sites(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None, stream=None) -> DiversityResult:
     rows = m.variants - row_begin if row_count is None else row_count
     d_pi, d_th = DeviceBuffer(m.device, 8 * rows), DeviceBuffer(m.device, 8 * rows)
     d_ca, d_di = DeviceBuffer(m.device, 4 * rows), DeviceBuffer(m.device, 4 * rows)
     totals = _abi.PopTotals()
     _abi.check(_abi.load().fmh_diversity_sites(m._h, g._h, row_begin, rows, d_pi.ptr, d_th.ptr, d_ca.ptr, d_di.ptr,
-                                               C.byref(totals), None))
+                                               C.byref(totals), stream))
     return DiversityResult(_pop_totals(totals), d_pi.to_numpy(np.float64, rows), d_th.to_numpy(np.float64, rows),
                            d_ca.to_numpy(np.uint32, rows), d_di.to_numpy(np.uint32, rows))
 
@@ -332,7 +332,7 @@ class WcResult:
     group_called: np.ndarray  # [P][rows]
 
 
-def wc_sweep(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None) -> WcResult:
+def wc_sweep(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional[int] = None, stream=None) -> WcResult:
     rows = m.variants - row_begin if row_count is None else row_count
     P = g.n_groups
     nw = 1 + P * (P - 1) // 2
@@ -340,7 +340,7 @@ def wc_sweep(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional
     d_s, d_n = DeviceBuffer(m.device, nw * rows), DeviceBuffer(m.device, 4 * P * rows)
     totals = _abi.WcTotals()
     _abi.check(_abi.load().fmh_wc_sweep(m._h, g._h, row_begin, rows, d_a.ptr, d_b.ptr, d_s.ptr, d_n.ptr,
-                                        C.byref(totals), None))
+                                        C.byref(totals), stream))
     return WcResult(np.array(totals.sum_a[:nw]), np.array(totals.sum_b[:nw]),
                     np.array(totals.informative_sites[:nw], dtype=np.uint64), int(totals.sites_attempted),
                     d_a.to_numpy(np.float64, nw * rows).reshape(nw, rows),
@@ -349,7 +349,7 @@ def wc_sweep(m: DeviceMatrix, g: Groups, row_begin: int = 0, row_count: Optional
                     d_n.to_numpy(np.uint32, P * rows).reshape(P, rows))
 
 
-def wc_sweep_many(m: DeviceMatrix, masks: np.ndarray, row_begin: int = 0, row_count: Optional[int] = None, sites: bool = True) -> WcResult:
+def wc_sweep_many(m: DeviceMatrix, masks: np.ndarray, row_begin: int = 0, row_count: Optional[int] = None, sites: bool = True, stream=None) -> WcResult:
     """fmh_wc_sweep_many: W&C for any number of groups (counting in batches of 8, arithmetic from count tables).
     sites=False: no per-site track is asked for - the regional sums come straight from the count tables (a, b, state, group_called = None)."""
     rows = m.variants - row_begin if row_count is None else row_count
@@ -359,14 +359,14 @@ def wc_sweep_many(m: DeviceMatrix, masks: np.ndarray, row_begin: int = 0, row_co
     if not sites:
         sum_a, sum_b = np.zeros(nw, dtype=np.float64), np.zeros(nw, dtype=np.float64)
         inf = np.zeros(nw, dtype=np.uint64)
-        _abi.check(_abi.load().fmh_wc_sweep_many(m._h, _ptr(masks), G, row_begin, rows, None, None, None, None, _ptr(sum_a), _ptr(sum_b), _ptr(inf), None))
+        _abi.check(_abi.load().fmh_wc_sweep_many(m._h, _ptr(masks), G, row_begin, rows, None, None, None, None, _ptr(sum_a), _ptr(sum_b), _ptr(inf), stream))
         return WcResult(sum_a, sum_b, inf, int(rows), None, None, None, None)
     d_a, d_b = DeviceBuffer(m.device, 8 * nw * rows), DeviceBuffer(m.device, 8 * nw * rows)
     d_s, d_n = DeviceBuffer(m.device, nw * rows), DeviceBuffer(m.device, 4 * G * rows)
     sum_a, sum_b = np.zeros(nw, dtype=np.float64), np.zeros(nw, dtype=np.float64)
     inf = np.zeros(nw, dtype=np.uint64)
     _abi.check(_abi.load().fmh_wc_sweep_many(m._h, _ptr(masks), G, row_begin, rows, d_a.ptr, d_b.ptr, d_s.ptr, d_n.ptr,
-                                             _ptr(sum_a), _ptr(sum_b), _ptr(inf), None))
+                                             _ptr(sum_a), _ptr(sum_b), _ptr(inf), stream))
     return WcResult(sum_a, sum_b, inf, int(rows),
                     d_a.to_numpy(np.float64, nw * rows).reshape(nw, rows),
                     d_b.to_numpy(np.float64, nw * rows).reshape(nw, rows),
@@ -392,15 +392,15 @@ PCA_SITE_UNCALLED = 1
 PCA_SITE_HIGH_ALLELE = 2
 
 
-def pca_scan_sites(m: DeviceMatrix, row_begin: int = 0, row_count: Optional[int] = None):
+def pca_scan_sites(m: DeviceMatrix, row_begin: int = 0, row_count: Optional[int] = None, stream=None):
     """fmh_pca_scan_sites: per row the count of called allele-1 entries (uint32) and the PCA_SITE_* flags (uint8)."""
     rc = m.variants - row_begin if row_count is None else row_count
     d_alt, d_flags = DeviceBuffer(m.device, max(4 * rc, 4)), DeviceBuffer(m.device, max(rc, 1))
-    _abi.check(_abi.load().fmh_pca_scan_sites(m._h, row_begin, rc, d_alt.ptr, d_flags.ptr, None))
+    _abi.check(_abi.load().fmh_pca_scan_sites(m._h, row_begin, rc, d_alt.ptr, d_flags.ptr, stream))
     return d_alt.to_numpy(np.uint32, rc), d_flags.to_numpy(np.uint8, rc)
 
 
-def pca_gram_device(m: DeviceMatrix, kept_rows, set_value, clear_value) -> DeviceBuffer:
+def pca_gram_device(m: DeviceMatrix, kept_rows, set_value, clear_value, stream=None) -> DeviceBuffer:
     """fmh_pca_gram into a fresh device buffer of (samples * 2) ** 2 doubles."""
     kept = np.ascontiguousarray(kept_rows, dtype=np.uint64)
     hi = np.ascontiguousarray(set_value, dtype=np.float64)
@@ -409,14 +409,14 @@ def pca_gram_device(m: DeviceMatrix, kept_rows, set_value, clear_value) -> Devic
         raise ValueError("kept_rows, set_value and clear_value must have one entry per kept site")
     n = m.samples * 2
     d_gram = DeviceBuffer(m.device, max(8 * n * n, 8))
-    _abi.check(_abi.load().fmh_pca_gram(m._h, _ptr(kept), kept.size, _ptr(hi), _ptr(lo), d_gram.ptr, None))
+    _abi.check(_abi.load().fmh_pca_gram(m._h, _ptr(kept), kept.size, _ptr(hi), _ptr(lo), d_gram.ptr, stream))
     return d_gram
 
 
-def pca_gram(m: DeviceMatrix, kept_rows, set_value, clear_value) -> np.ndarray:
+def pca_gram(m: DeviceMatrix, kept_rows, set_value, clear_value, stream=None) -> np.ndarray:
     """The standardised haplotype Gram Z Z^T / (n - 1) as an (n, n) float64 array."""
     n = m.samples * 2
-    return pca_gram_device(m, kept_rows, set_value, clear_value).to_numpy(np.float64, n * n).reshape(n, n)
+    return pca_gram_device(m, kept_rows, set_value, clear_value, stream).to_numpy(np.float64, n * n).reshape(n, n)
 
 
 def pca_gram_sharded_device(comm, m: DeviceMatrix, kept_rows, set_value, clear_value) -> DeviceBuffer:

@@ -143,7 +143,9 @@ int fmh_matrix_alloc(size_t variants, size_t samples, size_t ploidy, int with_mi
                      int device, fmh_matrix** out);
 /* Wrap caller-owned device memory (e.g. a torch uint8 tensor): d_data rows of `pitch` bytes
  * (pitch % 16 == 0, pitch >= samples*ploidy); d_called_bits_or_null rows of `bits_pitch` bytes
- * (bit h of a row set = entry h is called; bits_pitch % 4 == 0, 4-byte aligned). The wrapper never frees them. */
+ * (bit h of a row set = entry h is called; bits_pitch % 4 == 0, 4-byte aligned). The wrapper never frees them and never writes
+ * them.  The bytes and the called bits of a row past its last column, and the byte under an uncalled entry, may hold anything: neither
+ * fmh_matrix_pack nor a sweep, fmh_pairwise_differences or the PCA calls on the u8 rows count them. */
 int fmh_matrix_wrap(void* d_data, size_t pitch, void* d_called_bits_or_null, size_t bits_pitch,
                     size_t variants, size_t samples, size_t ploidy, uint8_t max_allele, int device,
                     fmh_matrix** out);

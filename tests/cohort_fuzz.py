@@ -24,6 +24,7 @@ The six origins:
 FMH_ROW_HI goes by (seed // 6) % 3: with origin = seed % 6 every origin meets every setting within the default 48 seeds."""
 
 import ctypes as C
+import functools
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -37,6 +38,7 @@ SEED_BASE = 31014  # the first base from 31000 on whose 48 default seeds meet ev
 DEFAULT_CASES = 48
 ORIGINS = ("create", "planes", "planes-pitch", "wrap-pack", "generate-pack", "regenerate")
 HOST_ORIGINS = ORIGINS[:4]
+GENERATED_ORIGINS = ORIGINS[4:]  # (tests/sweep_fuzz.py adds origins of its own whose data the host makes)
 SAMPLES = [1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 257, 500, 1025, 1300]
 ROWS = [1, 15, 17, 63, 65, 129, 257, 300, 600]
 ROW_HI = ("0", "2", None)
@@ -213,9 +215,29 @@ def values(case):
 
 
 # ---- host cohorts ------------------------------------------------------------------------------------------------------------------------
+CROWDED = "crowded"  # prefix of the kinds of tests/sweep_fuzz.py whose cohort is crowded_cohort
+
+
+@functools.lru_cache(maxsize=None)
+def crowded_cohort(rows, cols, max_allele, seed):
+    """(x, called) with every allele 0 .. max_allele equally common in every row and three entries in ten uncalled (every fourth row is
+    complete): both groups of a pair carry three alleles and more at nearly every site, and the first members of a group are often
+    uncalled - the sites at which the dense D_xy is added in first-occurrence order (sweep_kernels.hpp, first_member_column)."""
+    rng = np.random.default_rng(2000003 * rows + 7919 * cols + 31 * max_allele + seed)
+    x = rng.integers(0, max_allele + 1, size=(rows, cols), dtype=np.uint8)
+    called = rng.random((rows, cols)) >= 0.3
+    called[::4] = True
+    x[0, 0] = max_allele
+    x.setflags(write=False)
+    called.setflags(write=False)
+    return x, called
+
+
 def truth(case):
     """(x [rows][columns] uint8, called [rows][columns] bool or None) of an origin whose data the host makes; read-only and shared."""
-    assert case.origin in HOST_ORIGINS
+    assert case.origin not in GENERATED_ORIGINS
+    if case.kind.startswith(CROWDED):
+        return crowded_cohort(case.rows, case.columns, case.max_allele, case.seed)
     return cohort(case.rows, case.columns, case.max_allele, case.missing, seed=case.seed)
 
 
@@ -250,7 +272,7 @@ def generator_arguments(case, first=False):
 
 def generated(case, first=False):
     """(x, called or None) of a generate-pack / regenerate case from the host twin of the generator."""
-    assert case.origin not in HOST_ORIGINS
+    assert case.origin in GENERATED_ORIGINS
     x, called = host_generate(case.rows, case.columns, *generator_arguments(case, first))
     return x, (called if case.missing else None)
 
@@ -312,6 +334,22 @@ def _downloaded(dm, case):
     return x, ~miss
 
 
+def wrap(dev, case, pack):
+    """(dm, keepalive): fmh_matrix_wrap of wrap_blocks(case) uploaded into device blocks of the test's own, then (pack) fmh_matrix_pack."""
+    block, bits = wrap_blocks(case)
+    keepalive = [dev.DeviceBuffer.from_numpy(0, block)] + ([] if bits is None else [dev.DeviceBuffer.from_numpy(0, bits)])
+    try:
+        dm = dev.DeviceMatrix.wrap(keepalive[0].ptr, case.pitch, None if bits is None else keepalive[1].ptr, 0 if bits is None else case.bits_pitch,
+                                   case.rows, case.samples, case.ploidy, case.max_allele)
+        if pack:
+            dm.pack()
+    except Exception:
+        for b in keepalive:
+            b.free()
+        raise
+    return dm, keepalive
+
+
 def build(dev, case):
     """(dm, x, called, keepalive): the case's matrix made through its origin, and the cohort it holds.  For the generated origins the
     cohort is the matrix's own download - before the pack of generate-pack, when the matrix still answers with its byte rows.  keepalive
@@ -328,16 +366,7 @@ def build(dev, case):
         dm = dev.DeviceMatrix.from_host_planes(planes, called_plane, rows, samples, ploidy, max_allele)
     elif case.origin == "wrap-pack":
         x, called = truth(case)
-        block, bits = wrap_blocks(case)
-        keepalive = [dev.DeviceBuffer.from_numpy(0, block)] + ([] if bits is None else [dev.DeviceBuffer.from_numpy(0, bits)])
-        try:
-            dm = dev.DeviceMatrix.wrap(keepalive[0].ptr, case.pitch, None if bits is None else keepalive[1].ptr, 0 if bits is None else case.bits_pitch,
-                                       rows, samples, ploidy, max_allele)
-            dm.pack()
-        except Exception:
-            for b in keepalive:
-                b.free()
-            raise
+        dm, keepalive = wrap(dev, case, pack=True)
     else:
         dm = dev.DeviceMatrix.alloc(rows, samples, ploidy, case.missing, max_allele)
         try:
