@@ -25,6 +25,7 @@ from ._core import (  # noqa: E402,F401
     Kinship,
     LogisticScan,
     PairwiseDifference,
+    PolygenicScore,
     Population,
     SiteFrequencySpectrum,
     WcFstResult,
@@ -54,6 +55,7 @@ from ._core import (  # noqa: E402,F401
     pairwise_differences,
     per_chromosome_pca,
     per_site_diversity,
+    polygenic_score,
     segregating_sites,
     site_frequency_spectrum,
     watterson_theta,

@@ -247,6 +247,10 @@ SYMBOLS = {
     "fmh_logistic_score": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _i, _vp]),
     "fmh_logistic_score_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp]),
     "fmh_logistic_stats": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "fmh_score_sums": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmh_score_exponents": (_i, [_vp, _sz, _sz, _vp]),
+    "fmh_score_values": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fmh_score_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _i, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

@@ -104,6 +104,8 @@ const OptionRow kOptionRows[] = {
     {"FMH_QC_ITEM_ROWS", &Options::qc_item_rows, 0, nullptr},
     {"FMH_ASSOC_ITEM_ROWS", &Options::assoc_item_rows, 0, nullptr},
     {"FMH_ASSOC_BUDGET_BYTES", &Options::assoc_budget_bytes, (long long)1 << 30, nullptr},
+    {"FMH_SCORE_ITEM_ROWS", &Options::score_item_rows, 0, nullptr},
+    {"FMH_SCORE_BUDGET_BYTES", &Options::score_budget_bytes, (long long)1 << 30, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -36,6 +36,7 @@
 #include "../../include/ferromic_hip.h"
 #include "host_cpus.hpp"
 #include "pca_host.hpp"
+#include "score_host.hpp"
 
 namespace py = pybind11;
 using std::optional;

@@ -970,6 +970,7 @@ vector<uint32_t> sample_list_arg(const py::object& samples, int64_t limit) {
 #include "pymodule_qc.inc"
 #include "pymodule_assoc.inc"
 #include "pymodule_logistic.inc"
+#include "pymodule_score.inc"
 
 }  // namespace
 
@@ -1120,6 +1121,7 @@ PYBIND11_MODULE(_core, m) {
   bind_qc(m);
   bind_assoc(m, population);
   bind_logistic(m, population);
+  bind_score(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

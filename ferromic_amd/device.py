@@ -902,6 +902,111 @@ def assoc_stats(dosage_sum, called_sum, hom_ref, het, hom_alt, total, exponent, 
     return out
 
 
+# ---- polygenic scores: exact per-sample weighted dosage sums ----------------------------------------------------------------------------
+SCORE_DEFAULT_ITEM_ROWS = 4096   # FMH_SCORE_ITEM_ROWS unset
+SCORE_MAX_COLUMNS = 64
+SCORE_MAX_ROWS = 1 << 21
+SCORE_MODES = ("mean", "center", "zero")   # FMH_SCORE_MEAN, FMH_SCORE_CENTER, FMH_SCORE_ZERO
+
+
+@dataclass
+class ScoreSums:
+    dosage: np.ndarray              # [n][K] int64
+    called: Optional[np.ndarray]    # [n][K] int64, or None when the called sums were not asked for
+
+
+@dataclass
+class ScoreValues:
+    dosage: np.ndarray              # V [rows][K] int32
+    called: Optional[np.ndarray]    # U [rows][K] int32, or None without the site tracks
+    called_total: Optional[np.ndarray]   # T_U [K] int64
+    row_used: np.ndarray            # [rows] bool
+
+
+def score_sums(m: DeviceMatrix, values, called_values=None, samples=None, n_samples: Optional[int] = None, row_begin: int = 0,
+               row_count: Optional[int] = None, stream=None, fill: Optional[int] = None) -> ScoreSums:
+    """fmh_score_sums over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all): S = sum over rows of dosage x values and, with `called_values`, C = sum of called x called_values, [n][K]
+    int64.  `values` and `called_values` are [rows][K] int32.  `fill` pre-fills the outputs with that byte (tests: the call must write every
+    entry)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    if values.ndim != 2 or values.shape[0] != rows:
+        raise ValueError("values is [rows][K], one row per row of the range")
+    k = values.shape[1]
+    if called_values is not None:
+        called_values = np.ascontiguousarray(called_values, dtype=np.int32)
+        if called_values.shape != values.shape:
+            raise ValueError("called_values has the shape of values")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    nbytes = max(8 * n * k, 8)
+
+    def buffer():
+        return DeviceBuffer(m.device, nbytes) if fill is None else DeviceBuffer.from_numpy(m.device, np.full(nbytes, fill, dtype=np.uint8))
+
+    d_s = buffer()
+    d_c = buffer() if called_values is not None else None
+    _abi.check(_abi.load().fmh_score_sums(m._h, _ptr(samples), n, row_begin, rows, _ptr(values), _ptr(called_values), k, d_s.ptr,
+                                          None if d_c is None else d_c.ptr, stream))
+    return ScoreSums(d_s.to_numpy(np.int64, n * k).reshape(n, k), None if d_c is None else d_c.to_numpy(np.int64, n * k).reshape(n, k))
+
+
+def _score_weights(weights) -> np.ndarray:
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim == 1:
+        w = w.reshape(-1, 1)
+    if w.ndim != 2:
+        raise ValueError("weights is [rows] or [rows][K]")
+    return w
+
+
+def score_exponents(weights) -> np.ndarray:
+    """fmh_score_exponents (host only): per weight column the largest e with 2 max|w| 2^e <= 2^30; int32 [K]."""
+    w = _score_weights(weights)
+    e = np.zeros(max(w.shape[1], 1), dtype=np.int32)
+    _abi.check(_abi.load().fmh_score_exponents(_ptr(w), w.shape[0], w.shape[1], _ptr(e)))
+    return e[: w.shape[1]]
+
+
+def score_values(weights, exponents, hom_ref=None, het=None, hom_alt=None, called: Optional[bool] = None) -> ScoreValues:
+    """fmh_score_values (host only): V = rint(w 2^e) and, with the three site tracks, U = rint((mu w) 2^e) with its exact column totals;
+    which rows are used.  `called`: whether U is wanted (default: whenever the tracks are given)."""
+    w = _score_weights(weights)
+    rows, k = w.shape
+    e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+    if e.size != k:
+        raise ValueError("one exponent per weight column")
+    tracks = [None if a is None else np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (hom_ref, het, hom_alt)]
+    if any(a is not None and a.size != rows for a in tracks):
+        raise ValueError("the tracks have one entry per row")
+    want_u = all(a is not None for a in tracks) if called is None else bool(called)
+    v = np.zeros((rows, k), dtype=np.int32)
+    u = np.zeros((rows, k), dtype=np.int32) if want_u else None
+    total = np.zeros(k, dtype=np.int64) if want_u else None
+    used = np.zeros(max(rows, 1), dtype=np.uint8)
+    _abi.check(_abi.load().fmh_score_values(_ptr(w), rows, k, _ptr(e), *[_ptr(a) for a in tracks], _ptr(v), _ptr(u), _ptr(total), _ptr(used)))
+    return ScoreValues(v, u, total, used[:rows].astype(bool))
+
+
+def score_stats(dosage_sum, exponents, called_sum=None, called_total=None, mode: str = "mean") -> np.ndarray:
+    """fmh_score_stats (host only): the scores f64 [n][K] from the exact sums, mode "mean", "center" or "zero"."""
+    s = np.ascontiguousarray(dosage_sum, dtype=np.int64)
+    e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+    if s.ndim != 2 or s.shape[1] != e.size:
+        raise ValueError("dosage_sum is [n][K], exponents [K]")
+    c = None if called_sum is None else np.ascontiguousarray(called_sum, dtype=np.int64)
+    t = None if called_total is None else np.ascontiguousarray(called_total, dtype=np.int64).reshape(-1)
+    if (c is not None and c.shape != s.shape) or (t is not None and t.size != e.size):
+        raise ValueError("called_sum is [n][K], called_total [K]")
+    out = np.zeros(s.shape, dtype=np.float64)
+    _abi.check(_abi.load().fmh_score_stats(_ptr(s), _ptr(c), _ptr(t), _ptr(e), s.shape[0], s.shape[1], SCORE_MODES.index(mode), _ptr(out)))
+    return out
+
+
 # ---- logistic association scan: score test from exact class sums ------------------------------------------------------------------------
 LOGISTIC_MAX_SAMPLES = 1 << 21
 LOGISTIC_STATS = ("chi2", "z", "p", "beta", "se")

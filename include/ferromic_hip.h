@@ -81,7 +81,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_PD_SB   FMH_PD_OCC   FMH_PIPE   FMH_GRAPH   FMH_ROW_HI (0 | 1 | 2)   FMH_COLUMN_WINDOW (0 | 1 | 2)
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
- *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES
+ *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES   FMH_SCORE_ITEM_ROWS   FMH_SCORE_BUDGET_BYTES
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -893,6 +893,74 @@ int fmh_logistic_score_host(const long long* h_dosage_sum, const long long* h_ca
                             size_t n_basis, size_t n_phenotypes, double* h_score, double* h_variance);   /* host only, no device */
 int fmh_logistic_stats(const double* h_score, const double* h_variance, size_t count, double* h_chi2, double* h_z, double* h_p, double* h_beta,
                        double* h_se /* [count] each, or NULL */);   /* host only, no device */
+
+/* ---- polygenic scores: exact per-sample weighted dosage sums (an addition: the reference has none) ---------------------------------------
+ * What a study does with the beta column of an association scan: for every sample the sum over sites of weight x dosage, for up to 64
+ * weight columns at once (plink's --score; with centred weights the projection step of a genotype PCA).  It is fmh_assoc_sums transposed:
+ * the contraction runs over ROWS and the result is per SAMPLE.  Matrix, samples, c_i(r) and g_i(r) are fmh_assoc_sums': ploidy 2, a packed
+ * image, sample s owns columns 2s and 2s+1, the genotype is called iff both entries are called and both alleles are <= 1, every class is
+ * masked with the called plane.  n = n_samples; i is a position in the sample list.
+ *
+ * Device sums (fmh_score_sums).  Given V[row_count][K] and optionally U[row_count][K] (i32, host, row-major by row of the range), for every
+ * selected sample i, in list order, and k < K:
+ *     S[i][k] = sum_r c_i(r) * g_i(r) * V[r][k]   (dosage sum)        C[i][k] = sum_r c_i(r) * U[r][k]   (called sum; optional)
+ *   Both are exact `long long` device buffers [n][K], WRITTEN (not added).  Limits: 1 <= K <= 64, |V|, |U| <= 2^30, row_count <= 2^21, so
+ *   |S| <= 2^52, |C| <= 2^51 and |S + (T_U - C)| < 2^53 (T_U the column totals of U): every sum converts to f64 without rounding.  V and U
+ *   travel as four signed base-256 digits and the contraction over rows runs on the int8 matrix cores straight from the bit planes; an i32
+ *   digit accumulator of one work item holds at most 2 * item_rows * 128 <= 2^30; the items' i64 partials are added in row-block order.
+ *   C is computed iff BOTH h_called_values_or_null and d_called_sum_or_null are given.  A matrix that is biallelic with nothing missing
+ *   runs no second contraction: C is filled with the column totals of U.  Enqueues on `stream` and synchronises it.
+ *   Refusals, all before any launch, in this order.  FMH_ERR_INVALID: NULL matrix, dosage values or d_dosage_sum; called values without
+ *   d_called_sum or the reverse; n_samples == 0; K outside 1..64; row_count > 2^21; a value beyond +-2^30; a sample index out of range, or a
+ *   list that is not strictly ascending (n_samples beyond the matrix's samples without a list); a row range past the matrix.
+ *   FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix without a packed image (u8 rows only: call fmh_matrix_pack first); digits
+ *   and slabs above FMH_SCORE_BUDGET_BYTES (the message names the option).  row_count == 0 writes zeros and is FMH_OK.
+ *   Options: FMH_SCORE_ITEM_ROWS = the most rows of a work item (default 4 096; rounded up to a multiple of 64).  FMH_SCORE_BUDGET_BYTES =
+ *   the device bytes the call's digits (4 bytes per row and column, whole steps of 64 rows and groups of 16 columns) and slabs (8 bytes per
+ *   row block, sample of the covered groups of 256 and column), each twice when C is contracted, may take (default 1 GiB).  Neither changes
+ *   a result, nor do FMH_GRID_PER_CU and FMH_GRID_BLOCKS.
+ *
+ * Host functions (no device).  The operation order is fixed so that a plain Python loop over ints and floats reproduces every bit (the
+ * library is built with -ffp-contract=off).
+ *   fmh_score_exponents: h_weights f64 [n_rows][K] -> e[K].  e_k = the largest integer with 2 * max_r |w_rk| * 2^e_k <= 2^30 - the rule of
+ *     fmh_assoc_prepare's step 4 at 2 * max, taken without forming the product: max = f * 2^x with f in [0.5, 1) gives e = 30 - x when
+ *     f == 0.5, else 29 - x; e_k = 0 for a column of zeros.  The headroom of 2 is for U below (mu <= 2).  The exponent depends on the weights
+ *     alone, so a scan walked in row chunks uses one exponent and its i64 chunk sums add exactly.  Refusals (FMH_ERR_INVALID): K outside
+ *     1..64, a NULL pointer (h_weights with n_rows == 0 excepted), a non-finite weight.
+ *   fmh_score_values: the weights of a row chunk, e[K], and either the chunk's three u32 QC site tracks (fmh_genotype_counts, same rows and
+ *     samples) or all three NULL -> V [n_rows][K], U [n_rows][K] with its exact i64 column totals T_U[K] (both or neither; they need the
+ *     tracks), h_row_used u8 [n_rows].  Per row: N = hom_ref + het + hom_alt (without tracks every row counts as called).  A row with N == 0,
+ *     or whose weights are all zero, is unused: h_row_used = 0 and its V and U rows are zero.  Otherwise
+ *         mu = (double)(het + 2 * hom_alt) / (double)N;   V = (int32) rint(ldexp(w, e));   U = (int32) rint(ldexp(mu * w, e))
+ *     with the product mu * w taken first, in f64.  Refusals (FMH_ERR_INVALID): K outside 1..64; NULL exponents; one or two tracks; U without
+ *     T_U or the reverse, or without tracks; with n_rows > 0 a NULL weights, V or h_row_used; a non-finite weight; a weight with
+ *     |w| * 2^e > 2^29 (the exponent is not this column's).
+ *   fmh_score_stats: S, C, T_U, e, a mode -> f64 [n][K].  The integer in parentheses is formed in i64.
+ *         FMH_SCORE_MEAN    ldexp((double)(S + (T_U - C)), -e)   missing genotypes mean-imputed (plink's default)
+ *         FMH_SCORE_CENTER  ldexp((double)(S - C), -e)           sum of c (g - mu) w: missing contributes 0
+ *         FMH_SCORE_ZERO    ldexp((double)S, -e)                 missing contributes 0; needs neither C nor T_U
+ *     Sums of row chunks are added (i64) before this call: S, C and T_U are plain sums over rows.  Refusals (FMH_ERR_INVALID): K outside
+ *     1..64; an unknown mode; with n_samples > 0 a NULL S, e or output, C where the mode needs it, T_U in mode mean.  n_samples == 0 is FMH_OK.
+ * Not built: a run_vcf flag, sharding over devices (a caller splits rows and adds), haploid or u8-row matrices, variance-standardised
+ *   weights (a caller divides), a genotype-PCA projection API (FMH_SCORE_CENTER is its kernel), per-sample score files.
+ */
+#define FMH_SCORE_MEAN 0
+#define FMH_SCORE_CENTER 1
+#define FMH_SCORE_ZERO 2
+int fmh_score_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                   size_t row_begin, size_t row_count, const int32_t* h_dosage_values /* [row_count][n_columns] */,
+                   const int32_t* h_called_values_or_null /* [row_count][n_columns] */, size_t n_columns,
+                   long long* d_dosage_sum /* [n_samples][n_columns], device, written */,
+                   long long* d_called_sum_or_null /* [n_samples][n_columns], device, written */, void* stream);
+int fmh_score_exponents(const double* h_weights /* [n_rows][n_columns] */, size_t n_rows, size_t n_columns,
+                        int32_t* h_exponent /* [n_columns] */);   /* host only, no device */
+int fmh_score_values(const double* h_weights /* [n_rows][n_columns] */, size_t n_rows, size_t n_columns, const int32_t* h_exponent /* [n_columns] */,
+                     const uint32_t* h_hom_ref_or_null, const uint32_t* h_het_or_null, const uint32_t* h_hom_alt_or_null /* [n_rows] each, or all NULL */,
+                     int32_t* h_dosage_values /* [n_rows][n_columns] */, int32_t* h_called_values_or_null /* [n_rows][n_columns] */,
+                     long long* h_called_total_or_null /* [n_columns] */, uint8_t* h_row_used /* [n_rows] */);   /* host only, no device */
+int fmh_score_stats(const long long* h_dosage_sum, const long long* h_called_sum_or_null /* [n_samples][n_columns] each */,
+                    const long long* h_called_total_or_null, const int32_t* h_exponent /* [n_columns] each */, size_t n_samples, size_t n_columns,
+                    int mode /* FMH_SCORE_* */, double* h_score /* [n_samples][n_columns] */);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
