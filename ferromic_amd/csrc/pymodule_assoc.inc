@@ -1,5 +1,5 @@
 // pymodule_assoc.inc — ferromic.association_scan, Population.association_scan and the AssociationScan result (included inside
-// pymodule_stats.inc's namespace, after pymodule_qc.inc whose sample rules and array helpers it reuses).  An addition to the reference's
+// pymodule_stats.inc's namespace, after pymodule_rows.inc whose rows, sample rules and chunk tracks it uses).  An addition to the reference's
 // surface: it has no association scan; the definition is include/ferromic_hip.h's (fmh_assoc_prepare, fmh_assoc_sums, fmh_assoc_stats).
 // The exact sums come from the device, row chunk by row chunk; the statistics are computed from them on the host by the library as the
 // chunks come down; the GIL is released around the C calls.
@@ -68,8 +68,7 @@ AssocModel assoc_model(const py::object& phenotypes, const py::object& covariate
     status = fmh_assoc_prepare(y.data(), cin ? x.data() : nullptr, n, out.P, cin, out.values.data(), out.exponent.data(), out.total.data(), out.yy.data(),
                                &out.c, cin ? dropped.data() : nullptr);
   }
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());  // a non-finite input, too few samples, too many columns: the caller's arguments
-  fmh_check(status);
+  fmh_check_args(status);  // a non-finite input, too few samples, too many columns: the caller's arguments
   for (size_t j = 0; j < cin; ++j) (dropped[j] ? out.dropped : out.kept).push_back((int64_t)j);
   return out;
 }
@@ -87,22 +86,18 @@ AssociationScan association_from_sums(const py::object& dosage_sum, const py::ob
                                       uint64_t n_samples, size_t n_basis, const py::object& positions, const py::object& covariates_kept,
                                       const py::object& covariates_dropped) {
   AssociationScan out;
-  const vector<uint32_t> ref = qc_vector<uint32_t>(hom_ref, "hom_ref", 0, false);
-  const vector<uint32_t> h = qc_vector<uint32_t>(het, "het", ref.size(), true), alt = qc_vector<uint32_t>(hom_alt, "hom_alt", ref.size(), true);
+  const vector<uint32_t> ref = vector_arg<uint32_t>(hom_ref, "hom_ref", 0, false);
+  const vector<uint32_t> h = vector_arg<uint32_t>(het, "het", ref.size(), true), alt = vector_arg<uint32_t>(hom_alt, "hom_alt", ref.size(), true);
   auto yv = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(yy);
   if (!yv || yv.ndim() != 1 || yv.shape(0) < 1) value_error("yy must be a one-dimensional array with one entry per phenotype");
   const size_t rows = ref.size(), P = (size_t)yv.shape(0), K = n_basis + P;
-  const vector<long long> tot = qc_vector<long long>(total, "total", K, true);
-  const vector<int32_t> e = qc_vector<int32_t>(exponent, "exponent", K, true);
-  auto sums = [&](const py::object& obj, const char* name) {
-    auto arr = py::array_t<long long, py::array::c_style | py::array::forcecast>::ensure(obj);
-    if (!arr || (size_t)arr.size() != rows * K) value_error(string(name) + " must hold [rows][c + P] = " + std::to_string(rows * K) + " integers");
-    return vector<long long>(arr.data(), arr.data() + arr.size());
-  };
-  const vector<long long> S = sums(dosage_sum, "dosage_sum"), C = sums(called_sum, "called_sum");
-  if (!positions.is_none()) out.positions = qc_vector<int64_t>(positions, "positions", rows, true);
-  if (!covariates_kept.is_none()) out.kept = qc_vector<int64_t>(covariates_kept, "covariates_kept", n_basis, true);
-  if (!covariates_dropped.is_none()) out.dropped = qc_vector<int64_t>(covariates_dropped, "covariates_dropped", 0, false);
+  const vector<long long> tot = vector_arg<long long>(total, "total", K, true);
+  const vector<int32_t> e = vector_arg<int32_t>(exponent, "exponent", K, true);
+  const string shape = "hold [rows][c + P] = " + std::to_string(rows * K) + " integers";
+  const vector<long long> S = i64_table_arg(dosage_sum, "dosage_sum", rows * K, shape), C = i64_table_arg(called_sum, "called_sum", rows * K, shape);
+  if (!positions.is_none()) out.positions = vector_arg<int64_t>(positions, "positions", rows, true);
+  if (!covariates_kept.is_none()) out.kept = vector_arg<int64_t>(covariates_kept, "covariates_kept", n_basis, true);
+  if (!covariates_dropped.is_none()) out.dropped = vector_arg<int64_t>(covariates_dropped, "covariates_dropped", 0, false);
   out.n_samples = n_samples;
   out.reserve_rows(rows, P);
   int status;
@@ -111,46 +106,43 @@ AssociationScan association_from_sums(const py::object& dosage_sum, const py::ob
     status = fmh_assoc_stats(S.data(), C.data(), ref.data(), h.data(), alt.data(), rows, tot.data(), e.data(), yv.data(), n_samples, n_basis, P,
                              out.beta.data(), out.se.data(), out.t.data(), out.p.data());
   }
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());
-  fmh_check(status);
+  fmh_check_args(status);
   out.df = n_samples - n_basis - 2;
   fmh_check(assoc_site_columns(out, 0, rows, ref.data(), h.data(), alt.data()));
   return out;
 }
 
-AssociationScan association_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, const vector<uint32_t>& samples, const AssocModel& model,
-                                      vector<int64_t> positions) {
+AssociationScan association_over_rows(const RowsInPlay& in_play, const vector<uint32_t>& samples, const AssocModel& model) {
+  const ResidentRows rows = in_play.resident();
+  const shared_ptr<DevMatrix>& dm = rows.dm;
+  const size_t r0 = rows.r0, rc = rows.rc;
   AssociationScan out;
   const size_t n = model.n, c = model.c, P = model.P, K = c + P;
   out.n_samples = n;
   out.df = n - c - 2;
   out.kept = model.kept;
   out.dropped = model.dropped;
-  out.positions = std::move(positions);
+  out.positions = in_play.positions_copy();
   out.reserve_rows(dm ? rc : 0, P);
   if (!dm || rc == 0) return out;
-  long long budget = 0;
-  fmh_check(fmh_get_option("FMH_ASSOC_BUDGET_BYTES", &budget));
-  const size_t chunk_rows = std::min(rc, std::max<size_t>(1, (size_t)std::max<long long>(budget, 0) / (2 * K * sizeof(long long))));
-  DevBuf d_sums(dm->device, 2 * chunk_rows * K * sizeof(long long)), d_tracks(dm->device, 3 * chunk_rows * sizeof(uint32_t));
+  const size_t chunk_rows = chunk_rows_under("FMH_ASSOC_BUDGET_BYTES", rc, 2 * K * sizeof(long long));
+  DevBuf d_sums(dm->device, 2 * chunk_rows * K * sizeof(long long));
   long long* d_s = (long long*)d_sums.p;
   long long* d_c = d_s + chunk_rows * K;
-  uint32_t* t = (uint32_t*)d_tracks.p;
-  const fmh_genotype_site_out site{t, t + chunk_rows, t + 2 * chunk_rows};
+  ChunkTracks tracks(dm->device, chunk_rows);
   vector<long long> S(chunk_rows * K), C(chunk_rows * K);
-  vector<uint32_t> tracks(3 * chunk_rows);
   int status = FMH_OK;
   {
     py::gil_scoped_release nogil;
     const int dev = dm->device;
     for (size_t at = 0; at < rc && status == FMH_OK; at += chunk_rows) {
       const size_t count = std::min(chunk_rows, rc - at);
-      status = fmh_genotype_counts(dm->h, samples.data(), n, r0 + at, count, nullptr, nullptr, &site, nullptr, nullptr, nullptr);
+      status = fmh_genotype_counts(dm->h, samples.data(), n, r0 + at, count, nullptr, nullptr, &tracks.site, nullptr, nullptr, nullptr);
       if (status == FMH_OK) status = fmh_assoc_sums(dm->h, samples.data(), n, r0 + at, count, model.values.data(), K, d_s, d_c, nullptr);
       if (status == FMH_OK) status = fmh_copy_to_host(dev, S.data(), d_s, count * K * sizeof(long long), nullptr);
       if (status == FMH_OK) status = fmh_copy_to_host(dev, C.data(), d_c, count * K * sizeof(long long), nullptr);
-      if (status == FMH_OK) status = fmh_copy_to_host(dev, tracks.data(), t, 3 * chunk_rows * sizeof(uint32_t), nullptr);
-      const uint32_t *ref = tracks.data(), *het = ref + chunk_rows, *alt = het + chunk_rows;
+      if (status == FMH_OK) status = tracks.download();
+      const uint32_t *ref = tracks.ref(), *het = tracks.het(), *alt = tracks.alt();
       if (status == FMH_OK)
         status = fmh_assoc_stats(S.data(), C.data(), ref, het, alt, count, model.total.data(), model.exponent.data(), model.yy.data(), n, c, P,
                                  out.beta.data() + at * P, out.se.data() + at * P, out.t.data() + at * P, out.p.data() + at * P);
@@ -164,41 +156,17 @@ AssociationScan association_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0
 AssociationScan association_scan(const py::object& variants, const py::object& phenotypes, const py::object& covariates, const py::object& samples,
                                  const py::object& region) {
   auto store = store_from_python(variants);
-  if (store->S != 0 && store->P != 2) value_error("the association scan takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
+  diploid_only(store->P, (size_t)store->S, "the association scan takes");
   const vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
   const AssocModel model = assoc_model(phenotypes, covariates, list.size());
-  shared_ptr<const Store> sub = store;
-  bool empty = store->S == 0;
-  if (!empty && !region.is_none()) {
-    const Region reg = build_region(region);
-    const vector<int64_t> rows = region_len(reg) > 0 ? region_rows(*store, reg.start, reg.end) : vector<int64_t>();
-    if (rows.empty()) empty = true;
-    else sub = store_subset(store, rows);
-  }
-  if (empty) return association_over_rows(nullptr, 0, 0, list, model, {});
-  auto [dm, r0, rc] = sub->device_rows();
-  vector<int64_t> positions(sub->positions.begin(), sub->positions.begin() + (std::ptrdiff_t)std::min<size_t>(rc, sub->positions.size()));
-  return association_over_rows(dm, r0, rc, list, model, std::move(positions));
+  return association_over_rows(rows_in_play(store, region), list, model);
 }
 
-// the samples BOTH of whose haplotypes belong to the population, ascending, over its resident matrix: Population.genotype_qc's rule
 AssociationScan population_association_scan(const Population& pop, const py::object& phenotypes, const py::object& covariates) {
-  const int64_t ploidy = pop.dense ? pop.dense->ploidy : pop.store->P;
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count != 0 && ploidy != 2) value_error("the association scan takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(ploidy));
-  const int64_t limit = pop.dense ? pop.dense->samples : pop.store->first_sample_count();
-  vector<uint8_t> sides((size_t)std::max<int64_t>(limit, 0), 0);
-  for (auto& h : pop.haplotypes)
-    if (h.first >= 0 && h.first < limit) sides[(size_t)h.first] |= h.second == kLeft ? 1 : 2;
-  vector<uint32_t> list;
-  for (size_t s = 0; s < sides.size(); ++s)
-    if (sides[s] == 3) list.push_back((uint32_t)s);
+  diploid_only(pop, "the association scan takes");
+  const vector<uint32_t> list = population_samples(pop);
   const AssocModel model = assoc_model(phenotypes, covariates, list.size());
-  if (count == 0) return association_over_rows(nullptr, 0, 0, list, model, {});
-  const ResidentRows rows = resident_rows_of(pop);
-  const vector<int64_t>& all = pop.store->positions;
-  vector<int64_t> positions(all.begin(), all.begin() + (std::ptrdiff_t)std::min(rows.rc, all.size()));
-  return association_over_rows(rows.dm, rows.r0, rows.rc, list, model, std::move(positions));
+  return association_over_rows(rows_in_play(pop), list, model);
 }
 
 void bind_assoc(py::module_& m, py::class_<Population, shared_ptr<Population>>& population) {
@@ -210,12 +178,12 @@ void bind_assoc(py::module_& m, py::class_<Population, shared_ptr<Population>>& 
       .def_property_readonly("se", [](const AssociationScan& a) { return a.table(a.se); })
       .def_property_readonly("t", [](const AssociationScan& a) { return a.table(a.t); })
       .def_property_readonly("p", [](const AssociationScan& a) { return a.table(a.p); })
-      .def_property_readonly("n_called", [](const AssociationScan& a) { return qc_array(a.n_called); })
-      .def_property_readonly("alt_frequency", [](const AssociationScan& a) { return qc_array(a.alt_frequency); })
-      .def_property_readonly("positions", [](const AssociationScan& a) { return qc_array(a.positions); })
+      .def_property_readonly("n_called", [](const AssociationScan& a) { return array_of(a.n_called); })
+      .def_property_readonly("alt_frequency", [](const AssociationScan& a) { return array_of(a.alt_frequency); })
+      .def_property_readonly("positions", [](const AssociationScan& a) { return array_of(a.positions); })
       .def_property_readonly("df", [](const AssociationScan& a) { return a.df; })
-      .def_property_readonly("covariates_kept", [](const AssociationScan& a) { return qc_array(a.kept); })
-      .def_property_readonly("covariates_dropped", [](const AssociationScan& a) { return qc_array(a.dropped); })
+      .def_property_readonly("covariates_kept", [](const AssociationScan& a) { return array_of(a.kept); })
+      .def_property_readonly("covariates_dropped", [](const AssociationScan& a) { return array_of(a.dropped); })
       .def("__len__", [](const AssociationScan& a) { return a.rows; })
       .def("__repr__", &AssociationScan::repr);
   m.def("association_scan", &association_scan, py::arg("variants"), py::arg("phenotypes"), py::arg("covariates") = py::none(),

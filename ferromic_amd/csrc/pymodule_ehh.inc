@@ -101,9 +101,11 @@ EhhRequest ehh_parse_request(const py::object& focal, double min_ehh, const py::
   return req;
 }
 
-// `resident` is asked (and the matrix uploaded) only when there is a focal row to scan
-HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& positions, size_t count, const std::function<ResidentRows()>& resident) {
+// the rows in play are made resident (the matrix uploaded) only when there is a focal row to scan
+HaplotypeScan ehh_over_rows(const HapColumns& cols, EhhRequest req, const RowsInPlay& in_play) {
   HaplotypeScan out;
+  const size_t n = cols.n, count = in_play.count;
+  const vector<int64_t>& positions = in_play.positions();
   out.n = n;
   out.has_pairs = req.curve;
   out.max_extent = req.params.max_extent;
@@ -132,7 +134,7 @@ HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& pos
   out.stats.resize(F);
   if (req.curve) out.pairs.assign(F * 4 * out.max_extent, 0);
   if (F) {
-    const ResidentRows rows = resident();
+    const ResidentRows rows = in_play.resident(cols.mask);
     const DevMatrix& dm = *rows.dm;
     vector<uint64_t> device_focal = out.focal;
     for (uint64_t& f : device_focal) f += rows.r0;
@@ -167,34 +169,15 @@ HaplotypeScan ehh_over_rows(size_t n, EhhRequest req, const vector<int64_t>& pos
 HaplotypeScan ehh_of_variants(const py::object& variants, const py::object& haplotypes, const py::object& region, const EhhRequest& req) {
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   hap_sample_size(haps, nullptr);
-  optional<Region> reg;
-  if (!region.is_none()) reg = build_region(region);
+  const optional<Region> reg = region_arg(region);
   auto store = store_from_python(variants);
-  if (store->S == 0) return ehh_over_rows(haps.size(), req, {}, 0, nullptr);  // no variant, no columns to look the haplotypes up in
-  const vector<uint8_t> mask = store->mask_for(haps, store->first_sample_count());  // membership from the FIRST variant's sample count, as garud_h
-  const size_t n = hap_sample_size(haps, &mask);
-  shared_ptr<const Store> sub = store;
-  if (reg) {
-    const vector<int64_t> idx = region_len(*reg) > 0 ? region_rows(*store, reg->start, reg->end) : vector<int64_t>();
-    if (idx.empty()) return ehh_over_rows(n, req, {}, 0, nullptr);
-    sub = store_subset(store, idx);
-  }
-  return ehh_over_rows(n, req, sub->positions, (size_t)sub->S, [&] {
-    ResidentRows rows;
-    rows.mask = mask;
-    auto [dm, r0, rc] = sub->device_rows();
-    rows.dm = dm; rows.r0 = r0; rows.rc = rc;
-    return rows;
-  });
+  const HapColumns cols = hap_columns(*store, haps, hap_sample_size);
+  return ehh_over_rows(cols, req, rows_in_play(store, reg));
 }
 
 HaplotypeScan ehh_of_population(const Population& pop, const EhhRequest& req) {
   hap_sample_size(pop.haplotypes, nullptr);
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count == 0) return ehh_over_rows(pop.haplotypes.size(), req, {}, 0, nullptr);
-  const vector<uint8_t> mask = sfs_population_mask(pop);
-  const size_t n = hap_sample_size(pop.haplotypes, &mask);
-  return ehh_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), [&] { return resident_rows_of(pop); });
+  return ehh_over_rows(hap_columns(pop, hap_sample_size), req, rows_in_play(pop));
 }
 
 void bind_ehh(py::module_& m, py::class_<Population, shared_ptr<Population>>& population) {

@@ -173,7 +173,7 @@ FStatistics f_statistics(const py::object& populations, const py::object& blocks
   for (size_t g = 0; g < pops.size(); ++g) {
     sfs_sample_size(pops[g]->haplotypes, nullptr);
     if (count != 0) {
-      masks[g] = sfs_population_mask(*pops[g]);
+      masks[g] = population_mask(*pops[g]);
       sizes[g] = sfs_sample_size(pops[g]->haplotypes, &masks[g]);
     } else {
       sizes[g] = pops[g]->haplotypes.size();

@@ -106,12 +106,12 @@ size_t hap_sample_size(const vector<Hap>& haps, const vector<uint8_t>* mask) {
   return n;
 }
 
-// `resident` is asked (and the matrix uploaded) only when some window holds a row: an empty window is one class of everyone
-HaplotypeWindows hap_over_rows(size_t n, const HapRequest& req, const vector<int64_t>& positions, size_t count, bool partition,
-                               const std::function<ResidentRows()>& resident) {
+// the rows in play are made resident (the matrix uploaded) only when some window holds a row: an empty window is one class of everyone
+HaplotypeWindows hap_over_rows(const HapColumns& cols, const HapRequest& req, const RowsInPlay& in_play, bool partition) {
   HaplotypeWindows out;
+  const size_t n = cols.n;
   out.n = n;
-  out.ranges = hap_row_ranges(req, positions, count);
+  out.ranges = hap_row_ranges(req, in_play.positions(), in_play.count);
   out.has_first = partition;
   const size_t n_windows = out.ranges.size() / 2;
   fmh_hap_window everyone{};
@@ -127,7 +127,7 @@ HaplotypeWindows hap_over_rows(size_t n, const HapRequest& req, const vector<int
   bool any_row = false;
   for (size_t w = 0; w < n_windows; ++w) any_row = any_row || out.ranges[2 * w + 1] > out.ranges[2 * w];
   if (any_row) {
-    const ResidentRows rows = resident();
+    const ResidentRows rows = in_play.resident(cols.mask);
     vector<uint64_t> device_ranges = out.ranges;
     for (uint64_t& r : device_ranges) r += rows.r0;
     const DevMatrix& dm = *rows.dm;
@@ -153,35 +153,16 @@ HaplotypeWindows garud_h(const py::object& variants, const py::object& haplotype
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   hap_sample_size(haps, nullptr);
   const HapRequest req = hap_parse_request(windows, size, step);
-  optional<Region> reg;
-  if (!region.is_none()) reg = build_region(region);
+  const optional<Region> reg = region_arg(region);
   auto store = store_from_python(variants);
-  if (store->S == 0) return hap_over_rows(haps.size(), req, {}, 0, partition, nullptr);  // no variant, no columns to look the haplotypes up in
-  const vector<uint8_t> mask = store->mask_for(haps, store->first_sample_count());  // membership from the FIRST variant's sample count, as the spectra
-  const size_t n = hap_sample_size(haps, &mask);
-  shared_ptr<const Store> sub = store;
-  if (reg) {
-    const vector<int64_t> idx = region_len(*reg) > 0 ? region_rows(*store, reg->start, reg->end) : vector<int64_t>();
-    if (idx.empty()) return hap_over_rows(n, req, {}, 0, partition, nullptr);
-    sub = store_subset(store, idx);
-  }
-  return hap_over_rows(n, req, sub->positions, (size_t)sub->S, partition, [&] {
-    ResidentRows rows;
-    rows.mask = mask;
-    auto [dm, r0, rc] = sub->device_rows();
-    rows.dm = dm; rows.r0 = r0; rows.rc = rc;
-    return rows;
-  });
+  const HapColumns cols = hap_columns(*store, haps, hap_sample_size);
+  return hap_over_rows(cols, req, rows_in_play(store, reg), partition);
 }
 
 HaplotypeWindows population_garud_h(const Population& pop, const py::object& windows, const py::object& size, const py::object& step, bool partition) {
   hap_sample_size(pop.haplotypes, nullptr);
   const HapRequest req = hap_parse_request(windows, size, step);
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count == 0) return hap_over_rows(pop.haplotypes.size(), req, {}, 0, partition, nullptr);
-  const vector<uint8_t> mask = sfs_population_mask(pop);
-  const size_t n = hap_sample_size(pop.haplotypes, &mask);
-  return hap_over_rows(n, req, pop.store->positions, std::min(count, pop.store->positions.size()), partition, [&] { return resident_rows_of(pop); });
+  return hap_over_rows(hap_columns(pop, hap_sample_size), req, rows_in_play(pop), partition);
 }
 
 void bind_hap(py::module_& m) {

@@ -31,7 +31,9 @@ struct Kinship {
   string repr() const { return "Kinship(samples=" + std::to_string(n()) + ", sites=" + std::to_string(sites.size()) + ")"; }
 };
 
-Kinship kinship_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, vector<uint32_t> samples, const py::object& sites) {
+Kinship kinship_over_rows(const ResidentRows& rows, vector<uint32_t> samples, const py::object& sites) {
+  const shared_ptr<DevMatrix>& dm = rows.dm;
+  const size_t r0 = rows.r0, rc = rows.rc;
   Kinship out;
   out.samples = std::move(samples);
   const size_t n = out.n();
@@ -67,36 +69,14 @@ Kinship kinship_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc,
 
 Kinship kinship(const py::object& variants, const py::object& samples, const py::object& sites, const py::object& region) {
   auto store = store_from_python(variants);
-  if (store->S != 0 && store->P != 2) value_error("kinship takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
+  diploid_only(store->P, (size_t)store->S, "kinship takes");
   vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
-  shared_ptr<const Store> sub = store;
-  bool empty = store->S == 0;
-  if (!empty && !region.is_none()) {
-    const Region reg = build_region(region);
-    const vector<int64_t> rows = region_len(reg) > 0 ? region_rows(*store, reg.start, reg.end) : vector<int64_t>();
-    if (rows.empty()) empty = true;
-    else sub = store_subset(store, rows);
-  }
-  if (empty) return kinship_over_rows(nullptr, 0, 0, std::move(list), sites);
-  auto [dm, r0, rc] = sub->device_rows();
-  return kinship_over_rows(dm, r0, rc, std::move(list), sites);
+  return kinship_over_rows(rows_in_play(store, region).resident(), std::move(list), sites);
 }
 
-// the samples BOTH of whose haplotypes belong to the population, ascending, over its resident matrix
 Kinship population_kinship(const Population& pop, const py::object& sites) {
-  const int64_t ploidy = pop.dense ? pop.dense->ploidy : pop.store->P;
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count != 0 && ploidy != 2) value_error("kinship takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(ploidy));
-  const int64_t limit = pop.dense ? pop.dense->samples : pop.store->first_sample_count();
-  vector<uint8_t> sides((size_t)std::max<int64_t>(limit, 0), 0);
-  for (auto& h : pop.haplotypes)
-    if (h.first >= 0 && h.first < limit) sides[(size_t)h.first] |= h.second == kLeft ? 1 : 2;
-  vector<uint32_t> list;
-  for (size_t s = 0; s < sides.size(); ++s)
-    if (sides[s] == 3) list.push_back((uint32_t)s);
-  if (count == 0) return kinship_over_rows(nullptr, 0, 0, std::move(list), sites);
-  const ResidentRows rows = resident_rows_of(pop);
-  return kinship_over_rows(rows.dm, rows.r0, rows.rc, std::move(list), sites);
+  diploid_only(pop, "kinship takes");
+  return kinship_over_rows(rows_in_play(pop).resident(), population_samples(pop), sites);
 }
 
 void bind_kinship(py::module_& m) {

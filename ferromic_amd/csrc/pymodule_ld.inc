@@ -9,10 +9,12 @@ void ld_validate(size_t n_haplotypes, int64_t sites_apart, const char* what, con
   if (threshold && !(*threshold >= 0.0 && *threshold <= 1.0)) value_error("r2_threshold must lie in [0, 1]");  // NaN fails both comparisons
 }
 
-py::array_t<double> ld_r2_rows(const DevMatrix& dm, const vector<uint8_t>& mask, size_t r0, size_t rc, size_t band) {
+py::array_t<double> ld_r2_rows(const ResidentRows& rows, size_t band) {
+  const size_t r0 = rows.r0, rc = rows.rc;
   py::array_t<double> out(std::vector<py::ssize_t>{(py::ssize_t)rc, (py::ssize_t)band});
   if (rc == 0) return out;
-  const shared_ptr<Groups> gp = groups_for(dm, {mask});
+  const DevMatrix& dm = *rows.dm;
+  const shared_ptr<Groups> gp = groups_for(dm, {rows.mask});
   DevBuf d_r2(dm.device, rc * band * sizeof(double));
   fmh_ld_band_out bufs;
   memset(&bufs, 0, sizeof bufs);
@@ -28,10 +30,12 @@ py::array_t<double> ld_r2_rows(const DevMatrix& dm, const vector<uint8_t>& mask,
   return out;
 }
 
-py::array_t<bool> ld_prune_rows(const DevMatrix& dm, const vector<uint8_t>& mask, size_t r0, size_t rc, size_t window, double threshold) {
+py::array_t<bool> ld_prune_rows(const ResidentRows& rows, size_t window, double threshold) {
+  const size_t r0 = rows.r0, rc = rows.rc;
   py::array_t<bool> out((py::ssize_t)rc);
   if (rc == 0) return out;
-  const shared_ptr<Groups> gp = groups_for(dm, {mask});
+  const DevMatrix& dm = *rows.dm;
+  const shared_ptr<Groups> gp = groups_for(dm, {rows.mask});
   vector<uint8_t> keep(rc, 0);
   int status;
   {
@@ -44,53 +48,33 @@ py::array_t<bool> ld_prune_rows(const DevMatrix& dm, const vector<uint8_t>& mask
   return out;
 }
 
-// the rows of `region` (every variant when None) of a variant list; rows == 0 = nothing to do
-ResidentRows ld_rows_from_variants(const py::object& variants, const vector<Hap>& haps, const py::object& region) {
-  ResidentRows out;
+// the rows of `region` (every variant when None) of a variant list and the haplotypes' columns, membership from the FIRST variant's sample
+// count as per_site_diversity; `region` is read after the variants, and only when there is one
+ResidentRows ld_rows(const py::object& variants, const vector<Hap>& haps, const py::object& region) {
   auto store = store_from_python(variants);
-  if (store->S == 0) return out;
-  shared_ptr<const Store> sub = store;
-  if (!region.is_none()) {
-    const Region reg = build_region(region);
-    if (region_len(reg) <= 0) return out;
-    const vector<int64_t> rows = region_rows(*store, reg.start, reg.end);
-    if (rows.empty()) return out;
-    sub = store_subset(store, rows);
-  }
-  out.mask = store->mask_for(haps, store->first_sample_count());  // membership from the FIRST variant's sample count, as per_site_diversity
-  auto [dm, r0, rc] = sub->device_rows();
-  out.dm = dm; out.r0 = r0; out.rc = rc;
-  return out;
+  return rows_in_play(store, region).resident(store->mask_for(haps, store->first_sample_count()));
 }
 
 py::array_t<double> ld_r2(const py::object& variants, const py::object& haplotypes, int64_t max_sites_apart, const py::object& region) {
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   ld_validate(haps.size(), max_sites_apart, "max_sites_apart", nullptr);
-  const ResidentRows rows = ld_rows_from_variants(variants, haps, region);
-  if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
-  return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
+  return ld_r2_rows(ld_rows(variants, haps, region), (size_t)max_sites_apart);
 }
 
 py::array_t<bool> ld_prune(const py::object& variants, const py::object& haplotypes, int64_t window_sites, double r2_threshold, const py::object& region) {
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   ld_validate(haps.size(), window_sites, "window_sites", &r2_threshold);
-  const ResidentRows rows = ld_rows_from_variants(variants, haps, region);
-  if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
-  return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
+  return ld_prune_rows(ld_rows(variants, haps, region), (size_t)window_sites, r2_threshold);
 }
 
 py::array_t<double> population_ld_r2(const Population& pop, int64_t max_sites_apart) {
   ld_validate(pop.haplotypes.size(), max_sites_apart, "max_sites_apart", nullptr);
-  const ResidentRows rows = resident_rows_of(pop);
-  if (rows.rc == 0) return py::array_t<double>(std::vector<py::ssize_t>{0, (py::ssize_t)max_sites_apart});
-  return ld_r2_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)max_sites_apart);
+  return ld_r2_rows(resident_rows_of(pop), (size_t)max_sites_apart);
 }
 
 py::array_t<bool> population_ld_prune(const Population& pop, int64_t window_sites, double r2_threshold) {
   ld_validate(pop.haplotypes.size(), window_sites, "window_sites", &r2_threshold);
-  const ResidentRows rows = resident_rows_of(pop);
-  if (rows.rc == 0) return py::array_t<bool>((py::ssize_t)0);
-  return ld_prune_rows(*rows.dm, rows.mask, rows.r0, rows.rc, (size_t)window_sites, r2_threshold);
+  return ld_prune_rows(resident_rows_of(pop), (size_t)window_sites, r2_threshold);
 }
 
 void bind_ld(py::module_& m) {

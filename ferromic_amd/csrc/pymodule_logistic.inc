@@ -1,5 +1,5 @@
 // pymodule_logistic.inc — ferromic.logistic_scan, Population.logistic_scan and the LogisticScan result (included inside
-// pymodule_stats.inc's namespace, after pymodule_assoc.inc whose sample rules, site columns and array helpers it reuses).  An addition to the
+// pymodule_stats.inc's namespace, after pymodule_rows.inc whose rows, sample rules and chunk tracks it uses).  An addition to the
 // reference's surface; the definition is include/ferromic_hip.h's (fmh_logistic_null, fmh_assoc_homalt_sums, fmh_logistic_score,
 // fmh_logistic_stats).  The null models are fitted on the host once; the exact sums AND their reduction to a score and a variance per (row,
 // phenotype) run on the device, row chunk by row chunk and phenotype batch by phenotype batch: only two doubles per (row, phenotype) and the
@@ -97,8 +97,7 @@ LogisticModel logistic_model(const py::object& phenotypes, const py::object& cov
     status = fmh_logistic_null(y.data(), cin ? x.data() : nullptr, n, out.P, cin, out.values.data(), out.exponent.data(), out.total.data(), out.fitted.data(),
                                out.reason.data(), out.iterations.data(), (uint64_t*)out.n_cases.data(), &out.c, cin ? dropped.data() : nullptr);
   }
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());  // a phenotype that is not 0 / 1, a non-finite covariate, too few samples: the caller's
-  fmh_check(status);
+  fmh_check_args(status);  // a phenotype that is not 0 / 1, a non-finite covariate, too few samples: the caller's
   for (size_t j = 0; j < cin; ++j) (dropped[j] ? out.dropped : out.kept).push_back((int64_t)j);
   return out;
 }
@@ -128,15 +127,11 @@ LogisticScan logistic_from_sums(const py::object& dosage_sum, const py::object& 
                                 size_t n_basis, const py::object& fitted, const py::object& n_cases, const py::object& iterations, const py::object& positions,
                                 const py::object& covariates_kept, const py::object& covariates_dropped) {
   LogisticScan out;
-  const vector<uint32_t> ref = qc_vector<uint32_t>(hom_ref, "hom_ref", 0, false);
-  const vector<uint32_t> h = qc_vector<uint32_t>(het, "het", ref.size(), true), alt = qc_vector<uint32_t>(hom_alt, "hom_alt", ref.size(), true);
+  const vector<uint32_t> ref = vector_arg<uint32_t>(hom_ref, "hom_ref", 0, false);
+  const vector<uint32_t> h = vector_arg<uint32_t>(het, "het", ref.size(), true), alt = vector_arg<uint32_t>(hom_alt, "hom_alt", ref.size(), true);
   if (n_basis + 3 > 64) value_error("n_basis + 3 exceeds 64 value columns");
   const size_t rows = ref.size(), W = n_basis + 3, B = 64 / W;
-  auto flat = [&](const py::object& obj, const char* name) {
-    auto arr = py::array_t<long long, py::array::c_style | py::array::forcecast>::ensure(obj);
-    if (!arr) value_error(string(name) + " must be an integer array");
-    return vector<long long>(arr.data(), arr.data() + arr.size());
-  };
+  auto flat = [](const py::object& obj, const char* name) { return i64_table_arg(obj, name, kAnySize, "be an integer array"); };
   const vector<long long> tot = flat(total, "total");
   if (tot.empty() || tot.size() % W != 0) value_error("total must hold [P][c + 3] integers with P >= 1");
   const size_t P = tot.size() / W;
@@ -147,15 +142,15 @@ LogisticScan logistic_from_sums(const py::object& dosage_sum, const py::object& 
   if (H.size() != rows * P) value_error("homalt_sum must hold [rows][P] = " + std::to_string(rows * P) + " integers");
   out.fitted.assign(P, 1);
   if (!fitted.is_none()) {
-    const vector<uint8_t> f = qc_vector<uint8_t>(fitted, "fitted", P, true);
+    const vector<uint8_t> f = vector_arg<uint8_t>(fitted, "fitted", P, true);
     for (size_t i = 0; i < P; ++i) out.fitted[i] = f[i] ? 1 : 0;
   }
-  out.n_cases = n_cases.is_none() ? vector<uint64_t>(P, 0) : qc_vector<uint64_t>(n_cases, "n_cases", P, true);
-  out.iterations = iterations.is_none() ? vector<int32_t>(P, 0) : qc_vector<int32_t>(iterations, "iterations", P, true);
+  out.n_cases = n_cases.is_none() ? vector<uint64_t>(P, 0) : vector_arg<uint64_t>(n_cases, "n_cases", P, true);
+  out.iterations = iterations.is_none() ? vector<int32_t>(P, 0) : vector_arg<int32_t>(iterations, "iterations", P, true);
   out.reason.assign(P, 0);
-  if (!positions.is_none()) out.positions = qc_vector<int64_t>(positions, "positions", rows, true);
-  if (!covariates_kept.is_none()) out.kept = qc_vector<int64_t>(covariates_kept, "covariates_kept", n_basis, true);
-  if (!covariates_dropped.is_none()) out.dropped = qc_vector<int64_t>(covariates_dropped, "covariates_dropped", 0, false);
+  if (!positions.is_none()) out.positions = vector_arg<int64_t>(positions, "positions", rows, true);
+  if (!covariates_kept.is_none()) out.kept = vector_arg<int64_t>(covariates_kept, "covariates_kept", n_basis, true);
+  if (!covariates_dropped.is_none()) out.dropped = vector_arg<int64_t>(covariates_dropped, "covariates_dropped", 0, false);
   out.n_samples = n_samples;
   out.reserve_rows(rows, P);
   int status = FMH_OK;
@@ -182,34 +177,32 @@ LogisticScan logistic_from_sums(const py::object& dosage_sum, const py::object& 
     if (status == FMH_OK) status = out.finish();
     if (status == FMH_OK) status = logistic_site_columns(out, 0, rows, ref.data(), h.data(), alt.data());
   }
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());
-  fmh_check(status);
+  fmh_check_args(status);
   return out;
 }
 
-LogisticScan logistic_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, const vector<uint32_t>& samples, const LogisticModel& model,
-                                vector<int64_t> positions) {
+LogisticScan logistic_over_rows(const RowsInPlay& in_play, const vector<uint32_t>& samples, const LogisticModel& model) {
+  const ResidentRows rows = in_play.resident();
+  const shared_ptr<DevMatrix>& dm = rows.dm;
+  const size_t r0 = rows.r0, rc = rows.rc;
   LogisticScan out;
   const size_t n = model.n, c = model.c, P = model.P, W = model.width(), B = model.batch(), Bmax = std::min(B, P), Kmax = Bmax * W;
   logistic_take_model(out, model);
-  out.positions = std::move(positions);
+  out.positions = in_play.positions_copy();
   out.reserve_rows(dm ? rc : 0, P);
   if (!dm || rc == 0) return out;
-  long long budget = 0;
-  fmh_check(fmh_get_option("FMH_ASSOC_BUDGET_BYTES", &budget));
   // per row of a chunk: S and C [Kmax], H [Bmax], score and variance [Bmax]
   const size_t row_bytes = (2 * Kmax + 3 * Bmax) * sizeof(long long);
-  const size_t chunk_rows = std::min(rc, std::max<size_t>(1, (size_t)std::max<long long>(budget, 0) / row_bytes));
-  DevBuf d_sums(dm->device, chunk_rows * row_bytes), d_tracks(dm->device, 3 * chunk_rows * sizeof(uint32_t));
+  const size_t chunk_rows = chunk_rows_under("FMH_ASSOC_BUDGET_BYTES", rc, row_bytes);
+  DevBuf d_sums(dm->device, chunk_rows * row_bytes);
   long long* d_s = (long long*)d_sums.p;
   long long* d_c = d_s + chunk_rows * Kmax;
   long long* d_h = d_c + chunk_rows * Kmax;
   double* d_u = (double*)(d_h + chunk_rows * Bmax);
   double* d_v = d_u + chunk_rows * Bmax;
-  uint32_t* t = (uint32_t*)d_tracks.p;
-  const fmh_genotype_site_out site{t, t + chunk_rows, t + 2 * chunk_rows};
+  ChunkTracks tracks(dm->device, chunk_rows);
+  const fmh_genotype_site_out& site = tracks.site;
   vector<double> U(chunk_rows * Bmax), V(chunk_rows * Bmax);
-  vector<uint32_t> tracks(3 * chunk_rows);
   vector<int32_t> wcol(n * Bmax);
   int status = FMH_OK;
   {
@@ -236,9 +229,8 @@ LogisticScan logistic_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size
             out.variance[(at + i) * P + first + q] = V[i * Pb + q];
           }
       }
-      if (status == FMH_OK) status = fmh_copy_to_host(dev, tracks.data(), t, 3 * chunk_rows * sizeof(uint32_t), nullptr);
-      const uint32_t *ref = tracks.data(), *het = ref + chunk_rows, *alt = het + chunk_rows;
-      if (status == FMH_OK) status = logistic_site_columns(out, at, count, ref, het, alt);
+      if (status == FMH_OK) status = tracks.download();
+      if (status == FMH_OK) status = logistic_site_columns(out, at, count, tracks.ref(), tracks.het(), tracks.alt());
     }
     if (status == FMH_OK) status = out.finish();
   }
@@ -249,41 +241,17 @@ LogisticScan logistic_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size
 LogisticScan logistic_scan(const py::object& variants, const py::object& phenotypes, const py::object& covariates, const py::object& samples,
                            const py::object& region) {
   auto store = store_from_python(variants);
-  if (store->S != 0 && store->P != 2) value_error("the logistic scan takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
+  diploid_only(store->P, (size_t)store->S, "the logistic scan takes");
   const vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
   const LogisticModel model = logistic_model(phenotypes, covariates, list.size());
-  shared_ptr<const Store> sub = store;
-  bool empty = store->S == 0;
-  if (!empty && !region.is_none()) {
-    const Region reg = build_region(region);
-    const vector<int64_t> rows = region_len(reg) > 0 ? region_rows(*store, reg.start, reg.end) : vector<int64_t>();
-    if (rows.empty()) empty = true;
-    else sub = store_subset(store, rows);
-  }
-  if (empty) return logistic_over_rows(nullptr, 0, 0, list, model, {});
-  auto [dm, r0, rc] = sub->device_rows();
-  vector<int64_t> positions(sub->positions.begin(), sub->positions.begin() + (std::ptrdiff_t)std::min<size_t>(rc, sub->positions.size()));
-  return logistic_over_rows(dm, r0, rc, list, model, std::move(positions));
+  return logistic_over_rows(rows_in_play(store, region), list, model);
 }
 
-// the samples BOTH of whose haplotypes belong to the population, ascending, over its resident matrix: Population.association_scan's rule
 LogisticScan population_logistic_scan(const Population& pop, const py::object& phenotypes, const py::object& covariates) {
-  const int64_t ploidy = pop.dense ? pop.dense->ploidy : pop.store->P;
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count != 0 && ploidy != 2) value_error("the logistic scan takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(ploidy));
-  const int64_t limit = pop.dense ? pop.dense->samples : pop.store->first_sample_count();
-  vector<uint8_t> sides((size_t)std::max<int64_t>(limit, 0), 0);
-  for (auto& h : pop.haplotypes)
-    if (h.first >= 0 && h.first < limit) sides[(size_t)h.first] |= h.second == kLeft ? 1 : 2;
-  vector<uint32_t> list;
-  for (size_t s = 0; s < sides.size(); ++s)
-    if (sides[s] == 3) list.push_back((uint32_t)s);
+  diploid_only(pop, "the logistic scan takes");
+  const vector<uint32_t> list = population_samples(pop);
   const LogisticModel model = logistic_model(phenotypes, covariates, list.size());
-  if (count == 0) return logistic_over_rows(nullptr, 0, 0, list, model, {});
-  const ResidentRows rows = resident_rows_of(pop);
-  const vector<int64_t>& all = pop.store->positions;
-  vector<int64_t> positions(all.begin(), all.begin() + (std::ptrdiff_t)std::min(rows.rc, all.size()));
-  return logistic_over_rows(rows.dm, rows.r0, rows.rc, list, model, std::move(positions));
+  return logistic_over_rows(rows_in_play(pop), list, model);
 }
 
 void bind_logistic(py::module_& m, py::class_<Population, shared_ptr<Population>>& population) {
@@ -299,15 +267,15 @@ void bind_logistic(py::module_& m, py::class_<Population, shared_ptr<Population>
       .def_property_readonly("p", [](const LogisticScan& a) { return a.table(a.p); })
       .def_property_readonly("beta", [](const LogisticScan& a) { return a.table(a.beta); })
       .def_property_readonly("se", [](const LogisticScan& a) { return a.table(a.se); })
-      .def_property_readonly("n_called", [](const LogisticScan& a) { return qc_array(a.n_called); })
-      .def_property_readonly("alt_frequency", [](const LogisticScan& a) { return qc_array(a.alt_frequency); })
-      .def_property_readonly("positions", [](const LogisticScan& a) { return qc_array(a.positions); })
-      .def_property_readonly("n_cases", [](const LogisticScan& a) { return qc_array(a.n_cases); })
+      .def_property_readonly("n_called", [](const LogisticScan& a) { return array_of(a.n_called); })
+      .def_property_readonly("alt_frequency", [](const LogisticScan& a) { return array_of(a.alt_frequency); })
+      .def_property_readonly("positions", [](const LogisticScan& a) { return array_of(a.positions); })
+      .def_property_readonly("n_cases", [](const LogisticScan& a) { return array_of(a.n_cases); })
       .def_property_readonly("fitted", [](const LogisticScan& a) { return a.fitted_array(); })
-      .def_property_readonly("iterations", [](const LogisticScan& a) { return qc_array(a.iterations); })
-      .def_property_readonly("reason", [](const LogisticScan& a) { return qc_array(a.reason); })
-      .def_property_readonly("covariates_kept", [](const LogisticScan& a) { return qc_array(a.kept); })
-      .def_property_readonly("covariates_dropped", [](const LogisticScan& a) { return qc_array(a.dropped); })
+      .def_property_readonly("iterations", [](const LogisticScan& a) { return array_of(a.iterations); })
+      .def_property_readonly("reason", [](const LogisticScan& a) { return array_of(a.reason); })
+      .def_property_readonly("covariates_kept", [](const LogisticScan& a) { return array_of(a.kept); })
+      .def_property_readonly("covariates_dropped", [](const LogisticScan& a) { return array_of(a.dropped); })
       .def("__len__", [](const LogisticScan& a) { return a.rows; })
       .def("__repr__", &LogisticScan::repr);
   m.def("logistic_scan", &logistic_scan, py::arg("variants"), py::arg("phenotypes"), py::arg("covariates") = py::none(), py::arg("samples") = py::none(),

@@ -1,5 +1,5 @@
 // pymodule_qc.inc — ferromic.genotype_qc, Population.genotype_qc and the GenotypeQC result (included inside pymodule_stats.inc's namespace,
-// after pymodule_kinship.inc whose sample and sites rules it reuses).  An addition to the reference's surface: it has no genotype QC; the
+// after pymodule_rows.inc whose rows, sample and sites rules it uses).  An addition to the reference's surface: it has no genotype QC; the
 // definition is include/ferromic_hip.h's (fmh_genotype_counts, fmh_hwe_exact, fmh_genotype_site_stats, fmh_genotype_site_weights,
 // fmh_genotype_sample_stats).  Counts and the exact test's p come from the device; the other statistics are computed from the integers on
 // the host by the library; the GIL is released around the C calls.
@@ -50,19 +50,6 @@ struct GenotypeQC {
   string repr() const { return "GenotypeQC(samples=" + std::to_string(s_hom_ref.size()) + ", sites=" + std::to_string(hom_ref.size()) + ")"; }
 };
 
-template <class T> py::array_t<T> qc_array(const vector<T>& v) {
-  py::array_t<T> out((py::ssize_t)v.size());
-  if (!v.empty()) memcpy(out.mutable_data(), v.data(), v.size() * sizeof(T));
-  return out;
-}
-
-template <class T> vector<T> qc_vector(const py::object& obj, const char* name, size_t expect, bool check) {
-  auto arr = py::array_t<T, py::array::c_style | py::array::forcecast>::ensure(obj);
-  if (!arr || arr.ndim() != 1) value_error(string(name) + " must be a one-dimensional integer array");
-  if (check && (size_t)arr.shape(0) != expect) value_error(string(name) + " has " + std::to_string(arr.shape(0)) + " entries, expected " + std::to_string(expect));
-  return vector<T>(arr.data(), arr.data() + arr.shape(0));
-}
-
 // A result from counts that were computed before (no device): the exact test runs on the host twin.
 GenotypeQC genotype_qc_from_counts(const py::object& hom_ref, const py::object& het, const py::object& hom_alt, uint64_t n_samples,
                                    const py::object& sample_hom_ref, const py::object& sample_het, const py::object& sample_hom_alt, uint64_t kept_rows,
@@ -70,14 +57,14 @@ GenotypeQC genotype_qc_from_counts(const py::object& hom_ref, const py::object& 
   GenotypeQC out;
   out.n_samples = n_samples;
   out.kept_rows = kept_rows;
-  out.hom_ref = qc_vector<uint32_t>(hom_ref, "hom_ref", 0, false);
-  out.het = qc_vector<uint32_t>(het, "het", out.hom_ref.size(), true);
-  out.hom_alt = qc_vector<uint32_t>(hom_alt, "hom_alt", out.hom_ref.size(), true);
-  out.s_hom_ref = qc_vector<uint64_t>(sample_hom_ref, "sample_hom_ref", 0, false);
-  out.s_het = qc_vector<uint64_t>(sample_het, "sample_het", out.s_hom_ref.size(), true);
-  out.s_hom_alt = qc_vector<uint64_t>(sample_hom_alt, "sample_hom_alt", out.s_hom_ref.size(), true);
+  out.hom_ref = vector_arg<uint32_t>(hom_ref, "hom_ref", 0, false);
+  out.het = vector_arg<uint32_t>(het, "het", out.hom_ref.size(), true);
+  out.hom_alt = vector_arg<uint32_t>(hom_alt, "hom_alt", out.hom_ref.size(), true);
+  out.s_hom_ref = vector_arg<uint64_t>(sample_hom_ref, "sample_hom_ref", 0, false);
+  out.s_het = vector_arg<uint64_t>(sample_het, "sample_het", out.s_hom_ref.size(), true);
+  out.s_hom_alt = vector_arg<uint64_t>(sample_hom_alt, "sample_hom_alt", out.s_hom_ref.size(), true);
   out.has_f = !weighted_called.is_none();
-  if (out.has_f) out.s_weighted = qc_vector<uint64_t>(weighted_called, "weighted_called", out.s_hom_ref.size(), true);
+  if (out.has_f) out.s_weighted = vector_arg<uint64_t>(weighted_called, "weighted_called", out.s_hom_ref.size(), true);
   out.has_hwe = true;
   out.hwe_p.assign(out.hom_ref.size(), 0.0);
   int status;
@@ -90,8 +77,9 @@ GenotypeQC genotype_qc_from_counts(const py::object& hom_ref, const py::object& 
   return out;
 }
 
-GenotypeQC genotype_qc_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, vector<uint32_t> samples, const py::object& sites, bool hwe,
-                                 bool inbreeding) {
+GenotypeQC genotype_qc_over_rows(const ResidentRows& rows, vector<uint32_t> samples, const py::object& sites, bool hwe, bool inbreeding) {
+  const shared_ptr<DevMatrix>& dm = rows.dm;
+  const size_t r0 = rows.r0, rc = rows.rc;
   GenotypeQC out;
   out.samples = std::move(samples);
   const size_t n = out.samples.size();
@@ -142,36 +130,14 @@ GenotypeQC genotype_qc_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, siz
 GenotypeQC genotype_qc(const py::object& variants, const py::object& samples, const py::object& sites, const py::object& region, bool hwe,
                        bool inbreeding) {
   auto store = store_from_python(variants);
-  if (store->S != 0 && store->P != 2) value_error("genotype QC takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
+  diploid_only(store->P, (size_t)store->S, "genotype QC takes");
   vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
-  shared_ptr<const Store> sub = store;
-  bool empty = store->S == 0;
-  if (!empty && !region.is_none()) {
-    const Region reg = build_region(region);
-    const vector<int64_t> rows = region_len(reg) > 0 ? region_rows(*store, reg.start, reg.end) : vector<int64_t>();
-    if (rows.empty()) empty = true;
-    else sub = store_subset(store, rows);
-  }
-  if (empty) return genotype_qc_over_rows(nullptr, 0, 0, std::move(list), sites, hwe, inbreeding);
-  auto [dm, r0, rc] = sub->device_rows();
-  return genotype_qc_over_rows(dm, r0, rc, std::move(list), sites, hwe, inbreeding);
+  return genotype_qc_over_rows(rows_in_play(store, region).resident(), std::move(list), sites, hwe, inbreeding);
 }
 
-// the samples BOTH of whose haplotypes belong to the population, ascending, over its resident matrix: Population.kinship's rule
 GenotypeQC population_genotype_qc(const Population& pop, const py::object& sites, bool hwe, bool inbreeding) {
-  const int64_t ploidy = pop.dense ? pop.dense->ploidy : pop.store->P;
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count != 0 && ploidy != 2) value_error("genotype QC takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(ploidy));
-  const int64_t limit = pop.dense ? pop.dense->samples : pop.store->first_sample_count();
-  vector<uint8_t> sides((size_t)std::max<int64_t>(limit, 0), 0);
-  for (auto& h : pop.haplotypes)
-    if (h.first >= 0 && h.first < limit) sides[(size_t)h.first] |= h.second == kLeft ? 1 : 2;
-  vector<uint32_t> list;
-  for (size_t s = 0; s < sides.size(); ++s)
-    if (sides[s] == 3) list.push_back((uint32_t)s);
-  if (count == 0) return genotype_qc_over_rows(nullptr, 0, 0, std::move(list), sites, hwe, inbreeding);
-  const ResidentRows rows = resident_rows_of(pop);
-  return genotype_qc_over_rows(rows.dm, rows.r0, rows.rc, std::move(list), sites, hwe, inbreeding);
+  diploid_only(pop, "genotype QC takes");
+  return genotype_qc_over_rows(rows_in_play(pop).resident(), population_samples(pop), sites, hwe, inbreeding);
 }
 
 void bind_qc(py::module_& m) {
@@ -185,21 +151,21 @@ void bind_qc(py::module_& m) {
         return out;
       })
       .def_property_readonly("kept_rows", [](const GenotypeQC& q) { return q.kept_rows; })
-      .def_property_readonly("hom_ref", [](const GenotypeQC& q) { return qc_array(q.hom_ref); })
-      .def_property_readonly("het", [](const GenotypeQC& q) { return qc_array(q.het); })
-      .def_property_readonly("hom_alt", [](const GenotypeQC& q) { return qc_array(q.hom_alt); })
-      .def_property_readonly("call_rate", [](const GenotypeQC& q) { return qc_array(q.call_rate); })
-      .def_property_readonly("alt_frequency", [](const GenotypeQC& q) { return qc_array(q.alt_frequency); })
-      .def_property_readonly("maf", [](const GenotypeQC& q) { return qc_array(q.maf); })
-      .def_property_readonly("f_is", [](const GenotypeQC& q) { return qc_array(q.f_is); })
-      .def_property_readonly("hwe_p", [](const GenotypeQC& q) -> py::object { return q.has_hwe ? py::object(qc_array(q.hwe_p)) : py::object(py::none()); })
-      .def_property_readonly("sample_hom_ref", [](const GenotypeQC& q) { return qc_array(q.s_hom_ref); })
-      .def_property_readonly("sample_het", [](const GenotypeQC& q) { return qc_array(q.s_het); })
-      .def_property_readonly("sample_hom_alt", [](const GenotypeQC& q) { return qc_array(q.s_hom_alt); })
-      .def_property_readonly("sample_weighted_called", [](const GenotypeQC& q) -> py::object { return q.has_f ? py::object(qc_array(q.s_weighted)) : py::object(py::none()); })
-      .def_property_readonly("sample_call_rate", [](const GenotypeQC& q) { return qc_array(q.s_call_rate); })
-      .def_property_readonly("sample_het_rate", [](const GenotypeQC& q) { return qc_array(q.s_het_rate); })
-      .def_property_readonly("sample_f", [](const GenotypeQC& q) -> py::object { return q.has_f ? py::object(qc_array(q.s_f)) : py::object(py::none()); })
+      .def_property_readonly("hom_ref", [](const GenotypeQC& q) { return array_of(q.hom_ref); })
+      .def_property_readonly("het", [](const GenotypeQC& q) { return array_of(q.het); })
+      .def_property_readonly("hom_alt", [](const GenotypeQC& q) { return array_of(q.hom_alt); })
+      .def_property_readonly("call_rate", [](const GenotypeQC& q) { return array_of(q.call_rate); })
+      .def_property_readonly("alt_frequency", [](const GenotypeQC& q) { return array_of(q.alt_frequency); })
+      .def_property_readonly("maf", [](const GenotypeQC& q) { return array_of(q.maf); })
+      .def_property_readonly("f_is", [](const GenotypeQC& q) { return array_of(q.f_is); })
+      .def_property_readonly("hwe_p", [](const GenotypeQC& q) -> py::object { return q.has_hwe ? py::object(array_of(q.hwe_p)) : py::object(py::none()); })
+      .def_property_readonly("sample_hom_ref", [](const GenotypeQC& q) { return array_of(q.s_hom_ref); })
+      .def_property_readonly("sample_het", [](const GenotypeQC& q) { return array_of(q.s_het); })
+      .def_property_readonly("sample_hom_alt", [](const GenotypeQC& q) { return array_of(q.s_hom_alt); })
+      .def_property_readonly("sample_weighted_called", [](const GenotypeQC& q) -> py::object { return q.has_f ? py::object(array_of(q.s_weighted)) : py::object(py::none()); })
+      .def_property_readonly("sample_call_rate", [](const GenotypeQC& q) { return array_of(q.s_call_rate); })
+      .def_property_readonly("sample_het_rate", [](const GenotypeQC& q) { return array_of(q.s_het_rate); })
+      .def_property_readonly("sample_f", [](const GenotypeQC& q) -> py::object { return q.has_f ? py::object(array_of(q.s_f)) : py::object(py::none()); })
       .def("site_filter", &GenotypeQC::site_filter, py::arg("min_call_rate") = py::none(), py::arg("min_maf") = py::none(),
            py::arg("min_hwe_p") = py::none())
       .def("sample_filter", &GenotypeQC::sample_filter, py::arg("min_call_rate") = py::none(), py::arg("max_abs_f") = py::none())

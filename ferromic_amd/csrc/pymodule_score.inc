@@ -1,5 +1,5 @@
 // pymodule_score.inc — ferromic.polygenic_score, Population.polygenic_score and the PolygenicScore result (included inside
-// pymodule_stats.inc's namespace, after pymodule_assoc.inc whose sample rules and array helpers it reuses).  An addition to the reference's
+// pymodule_stats.inc's namespace, after pymodule_rows.inc whose rows, sample rules and chunk tracks it uses).  An addition to the reference's
 // surface: it has no scores; the definition is include/ferromic_hip.h's (fmh_score_exponents, fmh_score_values, fmh_score_sums,
 // fmh_score_stats).  The exact sums come from the device, row chunk by row chunk, and are added in i64; the scores are computed from the
 // totals on the host by the library, once; the GIL is released around the C calls.
@@ -53,8 +53,7 @@ ScoreWeights score_weights_arg(const py::object& weights, size_t rows) {
   out.w.assign(arr.data(), arr.data() + rows * out.K);
   out.exponents.assign(out.K, 0);
   const int status = fmh_score_exponents(out.w.data(), rows, out.K, out.exponents.data());
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());  // a non-finite weight
-  fmh_check(status);
+  fmh_check_args(status);  // a non-finite weight
   out.keep.assign(rows, 0);
   for (size_t r = 0; r < rows; ++r)
     for (size_t k = 0; k < out.K; ++k) out.keep[r] |= out.w[r * out.K + k] != 0.0 ? 1 : 0;
@@ -67,30 +66,25 @@ PolygenicScore score_from_sums(const py::object& dosage_sum, const py::object& e
                                const py::object& positions) {
   PolygenicScore out;
   out.mode = score_mode_arg(missing, center);
-  out.exponents = qc_vector<int32_t>(exponents, "exponents", 0, false);
+  out.exponents = vector_arg<int32_t>(exponents, "exponents", 0, false);
   out.K = out.exponents.size();
   if (out.K < 1 || out.K > 64) value_error(std::to_string(out.K) + " weight columns: 1 to 64 are taken");
-  auto sums = [&](const py::object& obj, const char* name, size_t expect) {
-    auto arr = py::array_t<long long, py::array::c_style | py::array::forcecast>::ensure(obj);
-    if (!arr || (expect != (size_t)-1 && (size_t)arr.size() != expect)) value_error(string(name) + " must hold [samples][K] integers");
-    return vector<long long>(arr.data(), arr.data() + arr.size());
-  };
-  const vector<long long> S = sums(dosage_sum, "dosage_sum", (size_t)-1);
+  const vector<long long> S = i64_table_arg(dosage_sum, "dosage_sum", kAnySize, "hold [samples][K] integers");
   if (S.size() % out.K != 0) value_error("dosage_sum must hold [samples][K] integers, K = " + std::to_string(out.K));
   out.n = S.size() / out.K;
   vector<long long> C, T;
   if (out.mode != FMH_SCORE_ZERO) {
     if (called_sum.is_none()) value_error("modes mean and center need called_sum");
-    C = sums(called_sum, "called_sum", S.size());
+    C = i64_table_arg(called_sum, "called_sum", S.size(), "hold [samples][K] integers");
   }
   if (out.mode == FMH_SCORE_MEAN) {
     if (called_total.is_none()) value_error("mode mean needs called_total");
-    T = qc_vector<long long>(called_total, "called_total", out.K, true);
+    T = vector_arg<long long>(called_total, "called_total", out.K, true);
   }
   out.rows_used = rows_used;
-  if (!n_called.is_none()) out.n_called = qc_vector<uint64_t>(n_called, "n_called", out.n, true);
-  if (!sample_dosage_sum.is_none()) out.dosage_sum = qc_vector<uint64_t>(sample_dosage_sum, "sample_dosage_sum", out.n, true);
-  if (!positions.is_none()) out.positions = qc_vector<int64_t>(positions, "positions", 0, false);
+  if (!n_called.is_none()) out.n_called = vector_arg<uint64_t>(n_called, "n_called", out.n, true);
+  if (!sample_dosage_sum.is_none()) out.dosage_sum = vector_arg<uint64_t>(sample_dosage_sum, "sample_dosage_sum", out.n, true);
+  if (!positions.is_none()) out.positions = vector_arg<int64_t>(positions, "positions", 0, false);
   out.score.assign(out.n * out.K, 0.0);
   int status;
   {
@@ -98,18 +92,19 @@ PolygenicScore score_from_sums(const py::object& dosage_sum, const py::object& e
     status = fmh_score_stats(S.data(), C.empty() ? nullptr : C.data(), T.empty() ? nullptr : T.data(), out.exponents.data(), out.n, out.K, out.mode,
                              out.score.data());
   }
-  if (status == FMH_ERR_INVALID) value_error(fmh_last_error());
-  fmh_check(status);
+  fmh_check_args(status);
   return out;
 }
 
-PolygenicScore score_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_t rc, const vector<uint32_t>& samples, const ScoreWeights& weights, int mode,
-                               vector<int64_t> positions) {
+PolygenicScore score_over_rows(const RowsInPlay& in_play, const vector<uint32_t>& samples, const ScoreWeights& weights, int mode) {
+  const ResidentRows rows = in_play.resident();
+  const shared_ptr<DevMatrix>& dm = rows.dm;
+  const size_t r0 = rows.r0, rc = rows.rc;
   PolygenicScore out;
   const size_t n = samples.size(), K = weights.K;
   out.n = n; out.K = K; out.mode = mode;
   out.exponents = weights.exponents;
-  out.positions = std::move(positions);
+  out.positions = in_play.positions_copy();
   out.score.assign(n * K, 0.0);
   out.n_called.assign(n, 0);
   out.dosage_sum.assign(n, 0);
@@ -126,17 +121,15 @@ PolygenicScore score_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_
     if (budget > 0 && fmh_host::score_call_bytes(mid, covered, K, item_rows, called) <= (size_t)budget) { chunk_rows = mid; lo = mid + 1; }
     else hi = mid - 1;
   }
-  DevBuf d_sums(dm->device, 2 * n * K * sizeof(long long)), d_tracks(dm->device, 3 * chunk_rows * sizeof(uint32_t));
+  DevBuf d_sums(dm->device, 2 * n * K * sizeof(long long));
+  ChunkTracks tracks(dm->device, chunk_rows);
   DevBuf d_classes(dm->device, 3 * n * sizeof(unsigned long long));
   long long* d_s = (long long*)d_sums.p;
   long long* d_c = d_s + n * K;
-  uint32_t* t = (uint32_t*)d_tracks.p;
   unsigned long long* cls = (unsigned long long*)d_classes.p;
-  const fmh_genotype_site_out site{t, t + chunk_rows, t + 2 * chunk_rows};
   const fmh_genotype_sample_out sample{cls, cls + n, cls + 2 * n, nullptr};
   vector<long long> S(n * K), C(n * K), sum_s(n * K, 0), sum_c(n * K, 0), T(K), total(K, 0);
   vector<int32_t> V(chunk_rows * K), U(chunk_rows * K);
-  vector<uint32_t> tracks(3 * chunk_rows);
   vector<uint8_t> used(chunk_rows);
   vector<unsigned long long> classes(3 * n);
   int status = FMH_OK;
@@ -146,11 +139,10 @@ PolygenicScore score_over_rows(const shared_ptr<DevMatrix>& dm, size_t r0, size_
     status = fmh_device_zero(dev, cls, 3 * n * sizeof(unsigned long long), nullptr);
     for (size_t at = 0; at < rc && status == FMH_OK; at += chunk_rows) {
       const size_t count = std::min(chunk_rows, rc - at);
-      status = fmh_genotype_counts(dm->h, samples.data(), n, r0 + at, count, weights.keep.data() + at, nullptr, &site, &sample, nullptr, nullptr);
-      if (status == FMH_OK) status = fmh_copy_to_host(dev, tracks.data(), t, 3 * chunk_rows * sizeof(uint32_t), nullptr);
-      const uint32_t *ref = tracks.data(), *het = ref + chunk_rows, *alt = het + chunk_rows;
+      status = fmh_genotype_counts(dm->h, samples.data(), n, r0 + at, count, weights.keep.data() + at, nullptr, &tracks.site, &sample, nullptr, nullptr);
+      if (status == FMH_OK) status = tracks.download();
       if (status == FMH_OK)
-        status = fmh_score_values(weights.w.data() + at * K, count, K, weights.exponents.data(), ref, het, alt, V.data(), called ? U.data() : nullptr,
+        status = fmh_score_values(weights.w.data() + at * K, count, K, weights.exponents.data(), tracks.ref(), tracks.het(), tracks.alt(), V.data(), called ? U.data() : nullptr,
                                   called ? T.data() : nullptr, used.data());
       if (status == FMH_OK)
         status = fmh_score_sums(dm->h, samples.data(), n, r0 + at, count, V.data(), called ? U.data() : nullptr, K, d_s, called ? d_c : nullptr, nullptr);
@@ -178,44 +170,22 @@ PolygenicScore polygenic_score(const py::object& variants, const py::object& wei
                                const string& missing, bool center) {
   const int mode = score_mode_arg(missing, center);
   auto store = store_from_python(variants);
-  if (store->S != 0 && store->P != 2) value_error("the polygenic score takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(store->P));
+  diploid_only(store->P, (size_t)store->S, "the polygenic score takes");
   const vector<uint32_t> list = sample_list_arg(samples, store->first_sample_count());
-  shared_ptr<const Store> sub = store;
-  bool empty = store->S == 0;
-  if (!empty && !region.is_none()) {
-    const Region reg = build_region(region);
-    const vector<int64_t> rows = region_len(reg) > 0 ? region_rows(*store, reg.start, reg.end) : vector<int64_t>();
-    if (rows.empty()) empty = true;
-    else sub = store_subset(store, rows);
-  }
-  const ScoreWeights w = score_weights_arg(weights, empty ? 0 : (size_t)sub->S);
+  const RowsInPlay rows = rows_in_play(store, region);
+  const ScoreWeights w = score_weights_arg(weights, rows.count);
   if (list.empty()) value_error("at least one sample is required for a polygenic score");
-  if (empty) return score_over_rows(nullptr, 0, 0, list, w, mode, {});
-  auto [dm, r0, rc] = sub->device_rows();
-  vector<int64_t> positions(sub->positions.begin(), sub->positions.begin() + (std::ptrdiff_t)std::min<size_t>(rc, sub->positions.size()));
-  return score_over_rows(dm, r0, rc, list, w, mode, std::move(positions));
+  return score_over_rows(rows, list, w, mode);
 }
 
-// the samples BOTH of whose haplotypes belong to the population, ascending, over its resident matrix: Population.genotype_qc's rule
 PolygenicScore population_polygenic_score(const Population& pop, const py::object& weights, const string& missing, bool center) {
   const int mode = score_mode_arg(missing, center);
-  const int64_t ploidy = pop.dense ? pop.dense->ploidy : pop.store->P;
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count != 0 && ploidy != 2) value_error("the polygenic score takes diploid genotypes (ploidy 2), got ploidy " + std::to_string(ploidy));
-  const int64_t limit = pop.dense ? pop.dense->samples : pop.store->first_sample_count();
-  vector<uint8_t> sides((size_t)std::max<int64_t>(limit, 0), 0);
-  for (auto& h : pop.haplotypes)
-    if (h.first >= 0 && h.first < limit) sides[(size_t)h.first] |= h.second == kLeft ? 1 : 2;
-  vector<uint32_t> list;
-  for (size_t s = 0; s < sides.size(); ++s)
-    if (sides[s] == 3) list.push_back((uint32_t)s);
-  const ScoreWeights w = score_weights_arg(weights, count);
+  diploid_only(pop, "the polygenic score takes");
+  const vector<uint32_t> list = population_samples(pop);
+  const RowsInPlay rows = rows_in_play(pop);
+  const ScoreWeights w = score_weights_arg(weights, rows.count);
   if (list.empty()) value_error("at least one sample with both haplotypes in the population is required for a polygenic score");
-  if (count == 0) return score_over_rows(nullptr, 0, 0, list, w, mode, {});
-  const ResidentRows rows = resident_rows_of(pop);
-  const vector<int64_t>& all = pop.store->positions;
-  vector<int64_t> positions(all.begin(), all.begin() + (std::ptrdiff_t)std::min(rows.rc, all.size()));
-  return score_over_rows(rows.dm, rows.r0, rows.rc, list, w, mode, std::move(positions));
+  return score_over_rows(rows, list, w, mode);
 }
 
 void bind_score(py::module_& m, py::class_<Population, shared_ptr<Population>>& population) {
@@ -225,11 +195,11 @@ void bind_score(py::module_& m, py::class_<Population, shared_ptr<Population>>& 
                   py::arg("n_called") = py::none(), py::arg("sample_dosage_sum") = py::none(), py::arg("positions") = py::none())
       .def_property_readonly("score", [](const PolygenicScore& a) { return a.table(false); })
       .def_property_readonly("average", [](const PolygenicScore& a) { return a.table(true); })
-      .def_property_readonly("n_called", [](const PolygenicScore& a) { return qc_array(a.n_called); })
-      .def_property_readonly("dosage_sum", [](const PolygenicScore& a) { return qc_array(a.dosage_sum); })
+      .def_property_readonly("n_called", [](const PolygenicScore& a) { return array_of(a.n_called); })
+      .def_property_readonly("dosage_sum", [](const PolygenicScore& a) { return array_of(a.dosage_sum); })
       .def_property_readonly("rows_used", [](const PolygenicScore& a) { return a.rows_used; })
-      .def_property_readonly("exponents", [](const PolygenicScore& a) { return qc_array(a.exponents); })
-      .def_property_readonly("positions", [](const PolygenicScore& a) { return qc_array(a.positions); })
+      .def_property_readonly("exponents", [](const PolygenicScore& a) { return array_of(a.exponents); })
+      .def_property_readonly("positions", [](const PolygenicScore& a) { return array_of(a.positions); })
       .def_property_readonly("mode", [](const PolygenicScore& a) { return string(a.mode_name()); })
       .def("__len__", [](const PolygenicScore& a) { return a.n; })
       .def("__repr__", &PolygenicScore::repr);

@@ -138,11 +138,11 @@ SfsRuns sfs_runs(const vector<int64_t>& positions, size_t count, size_t r0, cons
   return out;
 }
 
-// the spectra of a group of n haplotypes over the windows (None: every row); positions = those of the `count` rows that `resident` says
-// where to find - it is asked (and the matrix uploaded) only when some window holds a row
-SiteFrequencySpectrum sfs_over_rows(size_t n, const vector<int64_t>& positions, size_t count, const optional<vector<Region>>& windows,
-                                    const std::function<ResidentRows()>& resident) {
+// the spectra of a group of haplotypes over the windows (None: every row) of the rows in play, which are made resident (the matrix
+// uploaded) only when some window holds a row
+SiteFrequencySpectrum sfs_over_rows(const HapColumns& cols, const RowsInPlay& in_play, const optional<vector<Region>>& windows) {
   SiteFrequencySpectrum out;
+  const size_t n = cols.n, count = in_play.count;
   out.n = n;
   out.windowed = windows.has_value();
   out.n_windows = windows ? windows->size() : 1;
@@ -152,11 +152,11 @@ SiteFrequencySpectrum sfs_over_rows(size_t n, const vector<int64_t>& positions, 
   out.incomplete.assign(out.n_windows, 0);
   if (count == 0) return out;
   SfsRuns runs;
-  if (windows) runs = sfs_runs(positions, count, 0, *windows);
+  if (windows) runs = sfs_runs(in_play.positions(), count, 0, *windows);
   else { runs.ranges = {(uint64_t)0, (uint64_t)count}; runs.window_of = {0}; }
   const size_t n_runs = runs.window_of.size();
   if (n_runs == 0) return out;
-  const ResidentRows rows = resident();
+  const ResidentRows rows = in_play.resident(cols.mask);
   for (uint64_t& r : runs.ranges) r += rows.r0;
   const DevMatrix& dm = *rows.dm;
   const shared_ptr<Groups> gp = groups_for(dm, {rows.mask});
@@ -191,39 +191,16 @@ SiteFrequencySpectrum site_frequency_spectrum(const py::object& variants, const 
   const vector<Hap> haps = parse_haplotypes(haplotypes);
   sfs_sample_size(haps, nullptr);
   const optional<vector<Region>> wins = sfs_parse_windows(windows);
-  optional<Region> reg;
-  if (!region.is_none()) reg = build_region(region);
+  const optional<Region> reg = region_arg(region);
   auto store = store_from_python(variants);
-  if (store->S == 0) return sfs_over_rows(haps.size(), {}, 0, wins, nullptr);  // no variant, no columns to look the haplotypes up in
-  const vector<uint8_t> mask = store->mask_for(haps, store->first_sample_count());  // membership from the FIRST variant's sample count, as ld_r2
-  const size_t n = sfs_sample_size(haps, &mask);
-  shared_ptr<const Store> sub = store;
-  if (reg) {
-    const vector<int64_t> idx = region_len(*reg) > 0 ? region_rows(*store, reg->start, reg->end) : vector<int64_t>();
-    if (idx.empty()) return sfs_over_rows(n, {}, 0, wins, nullptr);
-    sub = store_subset(store, idx);
-  }
-  return sfs_over_rows(n, sub->positions, (size_t)sub->S, wins, [&] {
-    ResidentRows rows;
-    rows.mask = mask;
-    auto [dm, r0, rc] = sub->device_rows();
-    rows.dm = dm; rows.r0 = r0; rows.rc = rc;
-    return rows;
-  });
-}
-
-vector<uint8_t> sfs_population_mask(const Population& pop) {
-  return pop.dense ? pop.dense->mask_for(pop.haplotypes) : pop.store->mask_for(pop.haplotypes, pop.store->first_sample_count());
+  const HapColumns cols = hap_columns(*store, haps, sfs_sample_size);
+  return sfs_over_rows(cols, rows_in_play(store, reg), wins);
 }
 
 SiteFrequencySpectrum population_sfs(const Population& pop, const py::object& windows) {
   sfs_sample_size(pop.haplotypes, nullptr);
   const optional<vector<Region>> wins = sfs_parse_windows(windows);
-  const size_t count = pop.dense ? (size_t)pop.dense->variants : (size_t)pop.store->S;
-  if (count == 0) return sfs_over_rows(pop.haplotypes.size(), {}, 0, wins, nullptr);
-  const vector<uint8_t> mask = sfs_population_mask(pop);
-  const size_t n = sfs_sample_size(pop.haplotypes, &mask);
-  return sfs_over_rows(n, pop.store->positions, std::min(count, pop.store->positions.size()), wins, [&] { return resident_rows_of(pop); });
+  return sfs_over_rows(hap_columns(pop, sfs_sample_size), rows_in_play(pop), wins);
 }
 
 JointSiteFrequencySpectrum joint_site_frequency_spectrum(const py::object& a, const py::object& b) {
@@ -233,21 +210,18 @@ JointSiteFrequencySpectrum joint_site_frequency_spectrum(const py::object& a, co
   const bool same_store = !p1->dense && !p2->dense && p1->store == p2->store;
   if (!same_dense && !same_store)
     value_error("the joint site frequency spectrum needs two populations over ONE resident matrix: make both with with_haplotypes from one Population");
-  const size_t count = p1->dense ? (size_t)p1->dense->variants : (size_t)p1->store->S;
-  ResidentRows r1, r2;
-  if (count != 0) {
-    r1.mask = sfs_population_mask(*p1);
-    r2.mask = sfs_population_mask(*p2);
-  }
   JointSiteFrequencySpectrum out;
-  out.n0 = count ? sfs_sample_size(p1->haplotypes, &r1.mask) : (sfs_sample_size(p1->haplotypes, nullptr), p1->haplotypes.size());
-  out.n1 = count ? sfs_sample_size(p2->haplotypes, &r2.mask) : (sfs_sample_size(p2->haplotypes, nullptr), p2->haplotypes.size());
+  sfs_sample_size(p1->haplotypes, nullptr);
+  const HapColumns c1 = hap_columns(*p1, sfs_sample_size);
+  sfs_sample_size(p2->haplotypes, nullptr);
+  const HapColumns c2 = hap_columns(*p2, sfs_sample_size);
+  out.n0 = c1.n;
+  out.n1 = c2.n;
   out.counts.assign((out.n0 + 1) * (out.n1 + 1), 0);
-  if (count == 0) return out;
-  r1 = resident_rows_of(*p1);
-  r2.mask = sfs_population_mask(*p2);
+  if (variant_count(*p1) == 0) return out;
+  const ResidentRows r1 = resident_rows_of(*p1);
   const DevMatrix& dm = *r1.dm;
-  const shared_ptr<Groups> gp = groups_for(dm, {r1.mask, r2.mask});
+  const shared_ptr<Groups> gp = groups_for(dm, {r1.mask, c2.mask});
   DevBuf d_sfs(dm.device, out.counts.size() * sizeof(uint64_t));
   fmh_sfs_skipped skipped{0, 0};
   int status;

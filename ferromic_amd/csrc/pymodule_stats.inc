@@ -905,61 +905,8 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
   return total > 0 ? optional<double>((double)ones / (double)total) : std::nullopt;
 }
 
-// ---- what the device statistics below share: the resident rows they run over, and their `samples` and `sites` arguments -----------------
-// rows of a resident matrix and the columns in play: (matrix, first row, rows, column mask); rows == 0 = nothing to do
-struct ResidentRows {
-  shared_ptr<DevMatrix> dm;
-  size_t r0 = 0, rc = 0;
-  vector<uint8_t> mask;
-};
-
-// a Population's own haplotypes over its resident matrix: the dense one of from_numpy, else the variant store's
-ResidentRows resident_rows_of(const Population& pop) {
-  ResidentRows out;
-  if (pop.dense) {
-    if (pop.dense->variants == 0) return out;
-    out.mask = pop.dense->mask_for(pop.haplotypes);
-    out.dm = pop.dense->device_matrix();
-    out.rc = out.dm->variants;
-    return out;
-  }
-  if (pop.store->S == 0) return out;
-  out.mask = pop.store->mask_for(pop.haplotypes, pop.store->first_sample_count());
-  auto [dm, r0, rc] = pop.store->device_rows();
-  out.dm = dm; out.r0 = r0; out.rc = rc;
-  return out;
-}
-
-// the `sites` argument: None, or a boolean array with one entry per row in play
-vector<uint8_t> site_mask_arg(const py::object& sites, size_t rows, bool* given) {
-  *given = !sites.is_none();
-  vector<uint8_t> keep;
-  if (!*given) return keep;
-  auto arr = py::array_t<bool, py::array::c_style | py::array::forcecast>::ensure(sites);
-  if (!arr || arr.ndim() != 1) value_error("sites must be a one-dimensional boolean array");
-  if ((size_t)arr.shape(0) != rows) value_error("sites has " + std::to_string(arr.shape(0)) + " entries for " + std::to_string(rows) + " rows");
-  keep.resize(rows);
-  const bool* p = arr.data();
-  for (size_t i = 0; i < rows; ++i) keep[i] = p[i] ? 1 : 0;
-  return keep;
-}
-
-// the `samples` argument: None = every sample, else strictly ascending sample numbers below `limit`
-vector<uint32_t> sample_list_arg(const py::object& samples, int64_t limit) {
-  vector<uint32_t> out;
-  if (samples.is_none()) {
-    for (int64_t s = 0; s < limit; ++s) out.push_back((uint32_t)s);
-    return out;
-  }
-  for (const py::handle& item : py::iter(samples)) {
-    if (!is_intlike(item)) raise(PyExc_TypeError, "samples must be integers");
-    const int64_t s = to_i64(item);
-    if (s < 0 || s >= limit) value_error("sample " + std::to_string(s) + " is outside the variants' " + std::to_string(limit) + " samples");
-    if (!out.empty() && (int64_t)out.back() >= s) value_error("samples must be strictly ascending");
-    out.push_back((uint32_t)s);
-  }
-  return out;
-}
+// ---- what the device statistics below share: the rows they run over, the samples and haplotypes in play, their argument rules ---------------
+#include "pymodule_rows.inc"
 
 #include "pymodule_ld.inc"
 #include "pymodule_sfs.inc"
