@@ -207,6 +207,7 @@ SYMBOLS = {
     "fmh_groups_sizes": (_i, [_vp, _P(_i), _P(_u64)]),
     "fmh_sweep_window": (_i, [_vp, _vp, _i, _P(_u32), _P(_u32), _P(_i)]),
     "fmh_sweep_tiled": (_i, [_vp, _vp, _i, _P(_i), _P(_sz)]),
+    "fmh_sweep_prefix": (_i, [_vp, _vp, _i, _P(_i), _P(_u32), _P(_sz)]),
     "fmh_population_summaries": (_i, [_vp, _vp, _sz, _sz, _i, _vp, _vp, _P(PopTotals), _vp]),
     "fmh_hudson_sweep": (_i, [_vp, _vp, _sz, _sz, _i, _P(HudsonSites), _P(HudsonTotals), _vp]),
     "fmh_hudson_from_counts": (_i, [_i, _vp, _vp, _u64, _vp, _vp, _u64, _sz, _i, _i, _P(HudsonSites), _P(HudsonTotals), _vp]),

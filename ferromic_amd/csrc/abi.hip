@@ -91,6 +91,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_TILED_PLANES", &Options::tiled_planes, 1, nullptr},
     {"FMH_TILED_BYTES", &Options::tiled_bytes, (long long)16 << 30, nullptr},
     {"FMH_TILED", &Options::tiled, -1, nullptr},
+    {"FMH_PREFIX_COUNTS", &Options::prefix_counts, 1, nullptr},
     {"FMH_TILED_BATCH", &Options::tiled_batch, 0, nullptr},
     {"FMH_PCA_EIGEN", &Options::pca_eigen, 0, "host=1,rocsolver=2,auto=0"},
     {"FMH_PCA_SPLITS", &Options::pca_splits, 0, nullptr},
@@ -420,21 +421,63 @@ static void free_planes(fmh_matrix* m) {
   pool_free(m->device, m->row_gap);
   pool_free(m->device, m->row_alt);
   pool_free(m->device, m->p0t);
+  pool_free(m->device, m->p0c);
   m->p0 = m->p1 = m->p2 = m->pc = nullptr;
   m->row_hi = m->row_gap = nullptr;
   m->row_alt = nullptr;
   m->p0t = nullptr;
   m->p0t_bytes = 0;
+  m->p0c = nullptr;
+  m->p0c_bytes = 0;
 }
 // after the planes of a matrix have been written, beside the row totals and under the same eligibility: plane 0 once more, tile-transposed
 // (tile_planes_kernel), for the sweeps of sweep_tiled.hip.  FMH_TILED_PLANES=0: no image; 1 (default): matrices of at least 4 096 rows whose image fits under
 // FMH_TILED_BYTES and leaves as much again free on the device; 2: any size, no free-memory test (tests).  Rebuilt by EVERY call that wrote the
 // planes and dropped by every call that builds none, like the row totals; a refusal or a failed allocation leaves no image, and every sweep then
 // takes the row-major routes.
-static void drop_tiled_planes(fmh_matrix* m) {
+static void drop_prefix_counts(fmh_matrix* m) {
+  pool_free(m->device, m->p0c);
+  m->p0c = nullptr;
+  m->p0c_bytes = 0;
+}
+static void drop_tiled_planes(fmh_matrix* m) {  // (the prefix counts live beside the image: no image, no table)
+  drop_prefix_counts(m);
   pool_free(m->device, m->p0t);
   m->p0t = nullptr;
   m->p0t_bytes = 0;
+}
+// after the image has been rebuilt: the prefix counts of plane 0 at every vector boundary (prefix_counts_kernel), from
+// which the tiled sweeps answer every group that is one column range without reading its whole vectors.  Only beside the image - its
+// eligibility and size policy are the image's - and on rows of at most 65 535 columns (u16 entries).  FMH_PREFIX_COUNTS=0: no table; 1
+// (default): matrices of at least 4 096 rows, while as much again stays free on the device; 2: beside the image at any size, no free-memory
+// test (tests).  Rebuilt by every call that rebuilt the image and dropped by every call that drops it; a refusal or a failed allocation
+// leaves no table, and every sweep then reads its window.
+static int build_prefix_counts(fmh_matrix* m) {
+  const long long mode = options().prefix_counts.load();
+  const size_t bytes = (m->variants + 63) / 64 * ((size_t)m->pvec + 1) * 128;
+  bool want = m->p0t && m->columns <= 65535 && mode != 0 && (mode == 2 || m->variants >= 4096);
+  if (want && mode != 2 && (!m->p0c || m->p0c_bytes != bytes)) {
+    size_t free_b = 0, total_b = 0;
+    FMH_TRY(use_device(m->device));
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); want = false; }
+    else if (free_b / 2 < bytes) want = false;
+  }
+  if (!want) { drop_prefix_counts(m); return FMH_OK; }
+  if (m->p0c && m->p0c_bytes != bytes) drop_prefix_counts(m);
+  if (!m->p0c) {
+    if (pool_malloc(m->device, (void**)&m->p0c, bytes) != hipSuccess) { m->p0c = nullptr; (void)hipGetLastError(); return FMH_OK; }  // no table: the window
+    m->p0c_bytes = bytes;
+  }
+  const size_t tiles = (m->variants + 63) / 64;
+  const int blocks = (int)std::min<size_t>((tiles + 3) / 4, 1 << 20);
+  hipLaunchKernelGGL(prefix_counts_kernel, dim3(blocks), dim3(256), 0, hipStreamPerThread, (const uint8_t*)m->p0t, tiles, m->pvec, m->columns, m->p0c);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(hipStreamPerThread);
+  if (e != hipSuccess) {
+    drop_prefix_counts(m);
+    return fail(FMH_ERR_HIP, "building the prefix counts failed: %s", hipGetErrorString(e));
+  }
+  return FMH_OK;
 }
 static int build_tiled_planes(fmh_matrix* m) {
   const long long mode = options().tiled_planes.load();
@@ -502,6 +545,7 @@ static int build_row_totals(fmh_matrix* m) {
 static int mark_upper_plane_rows(fmh_matrix* m) {
   FMH_TRY(build_row_totals(m));
   FMH_TRY(build_tiled_planes(m));
+  FMH_TRY(build_prefix_counts(m));
   const long long mode = options().row_hi.load();
   if ((!m->p1 && !m->pc) || m->variants == 0 || mode == 0 || (mode != 2 && m->variants < 4096)) {
     pool_free(m->device, m->row_hi);
@@ -894,6 +938,19 @@ extern "C" int fmh_groups_create(const fmh_matrix* m, const uint8_t* h_mask, int
         if (seen[h]) disjoint = false;
         seen[h] = 1;
       }
+    }
+    // one column range: as many members as the columns from the first one to the last one
+    for (int p = 0; p < n_groups; ++p) {
+      uint32_t first = 0, last = 0;
+      bool any = false;
+      for (uint32_t h = 0; h < m->columns; ++h) {
+        if (!h_mask[(size_t)p * m->columns + h]) continue;
+        if (!any) { first = h; any = true; }
+        last = h;
+      }
+      g->col_first[p] = any ? first : 0;
+      g->col_end[p] = any ? last + 1 : 0;
+      g->contiguous[p] = any && g->sizes[p] == (uint64_t)(last - first) + 1;
     }
     bool covers = true;
     for (uint32_t h = 0; h < m->columns && covers; ++h) covers = seen[h] != 0;

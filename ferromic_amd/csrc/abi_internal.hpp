@@ -80,6 +80,7 @@ struct Options {
   std::atomic<long long> tiled_planes{1};        // FMH_TILED_PLANES: the tile-transposed image of plane 0 (fmh_matrix::p0t): 0 = never built; 1 (default) = packed biallelic matrices of >= 4 096 rows with nothing missing, while the image fits under FMH_TILED_BYTES and as much again stays free; 2 = at any size, no free-memory test
   std::atomic<long long> tiled_bytes{(long long)16 << 30};  // FMH_TILED_BYTES: the largest image FMH_TILED_PLANES=1 builds
   std::atomic<long long> tiled{-1};              // FMH_TILED: 0 = sweeps take the row-major routes even where the image exists (the A side of every A/B); 1 = the tiled route wherever it is built; -1 = where it measured ahead (tiled_route_default)
+  std::atomic<long long> prefix_counts{1};       // FMH_PREFIX_COUNTS: the per-row prefix counts of plane 0 at every vector boundary (fmh_matrix::p0c): 0 = never built, never read; 1 (default) = beside the image, on matrices of >= 4 096 rows and at most 65 535 columns while as much again stays free; 2 = beside the image at any size, no free-memory test
   std::atomic<long long> tiled_batch{0};         // FMH_TILED_BATCH = 10 | 5 | 2: the half batch of the tiled sweep (measurements); 0 = by the window (sweep_tiled.hip)
   std::atomic<long long> pca_eigen{0};           // FMH_PCA_EIGEN = host | rocsolver: the PCA's symmetric eigen solver; 0 = rocSOLVER, the host solver when it cannot be loaded
   std::atomic<long long> pca_splits{0};          // FMH_PCA_SPLITS: K splits of the PCA Gram (1 = none); 0 = by the tile count
@@ -306,6 +307,11 @@ struct fmh_matrix {
   // wherever row_alt is.  A column window of a sweep is then whole KiB of every tile: no fetched line holds a byte the sweep does not need.
   uint8_t* p0t = nullptr;
   size_t p0t_bytes = 0;
+  // prefix counts of plane 0: for image tile T, boundary b in [0, pvec] and row slot s, the u16 at byte
+  // ((T * (pvec + 1) + b) * 64 + s) * 2 is the popcount of that row over vectors [0, b) - one 128-byte line per boundary and tile; b = pvec equals
+  // row_alt.  Only beside p0t and on rows of at most 65 535 columns; rebuilt or dropped wherever p0t is.
+  uint16_t* p0c = nullptr;
+  size_t p0c_bytes = 0;
   uint8_t* row_hi = nullptr;  // with p1: one byte per row, non-zero when the row has a bit in plane 1 or 2 (written wherever the planes are)
   size_t plane_pitch = 0;
   uint32_t pvec = 0;
@@ -326,5 +332,8 @@ struct fmh_groups {
   // the groups are pairwise disjoint / cover every column - together: a partition, the case in which one group's counts follow from the row totals
   uint32_t vec_first[FMH_MAX_GROUPS] = {0}, vec_last[FMH_MAX_GROUPS] = {0};
   bool disjoint = false, covers = false;
+  // contiguous[p]: the members of group p are exactly the columns [col_first[p], col_end[p]), at least one of them
+  uint32_t col_first[FMH_MAX_GROUPS] = {0}, col_end[FMH_MAX_GROUPS] = {0};
+  bool contiguous[FMH_MAX_GROUPS] = {false};
   std::vector<uint8_t> host_mask;  // [n_groups][columns] as handed in (the wide-matrix W&C route re-batches the groups)
 };

@@ -568,7 +568,7 @@ int sharded_enqueue(fmh_comm* c, const fmh_matrix* m, const fmh_groups* g, int m
     const void* ptrs[8] = {m, g, st, harmonic, m->p0, m->data, g->masks, g->mask_bits};
     put(ptrs, sizeof ptrs); put(&mode, sizeof mode); put(&gen, sizeof gen); put(&m->variants, sizeof m->variants); put(&m->columns, sizeof m->columns);
     put(&m->plane_pitch, sizeof m->plane_pitch); put(&m->pitch, sizeof m->pitch); put(g->sizes, sizeof g->sizes); put(&s.kind, sizeof s.kind);
-    const void* outs[17] = {a.alt, a.called, a.fst, a.dxy, a.pi1, a.pi2, a.num, a.den, a.site_pi, a.site_theta, a.site_distinct, a.wc_a, a.wc_b, a.wc_state, a.acounts, m->row_alt, m->p0t};  // (the row totals and the tiled image a windowed sweep reads: a re-pack may drop or move them)
+    const void* outs[18] = {a.alt, a.called, a.fst, a.dxy, a.pi1, a.pi2, a.num, a.den, a.site_pi, a.site_theta, a.site_distinct, a.wc_a, a.wc_b, a.wc_state, a.acounts, m->row_alt, m->p0t, m->p0c};  // (the row totals, the tiled image and the prefix counts a windowed sweep reads: a re-pack may drop or move them)
     put(outs, sizeof outs); put(&a.row_begin, sizeof a.row_begin); put(&a.row_count, sizeof a.row_count); put(&a.formula, sizeof a.formula);
     put(&a.hudson_formula_p1, sizeof a.hudson_formula_p1);
     if (!s.graph || s.graph_key != key) {

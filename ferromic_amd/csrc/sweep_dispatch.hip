@@ -1,6 +1,6 @@
 // sweep_dispatch.hip — every sweep's way to its kernel: plan (sweep_plan.hpp), kernel arguments, the route's launcher (sweep_*.hip),
 // finalize.  enqueue_sweep serves the blocking statistic entry points of abi.hip (through run_sweep) and the sharded sweeps of comm.hip;
-// fmh_sweep_window and fmh_sweep_tiled report what the plan of the next sweep says.
+// fmh_sweep_window, fmh_sweep_tiled and fmh_sweep_prefix report what the plan of the next sweep says.
 #include "abi_internal.hpp"
 #include "sweep_plan.hpp"
 
@@ -23,6 +23,7 @@ static PlanOptions snapshot_plan_options() {
   s.wc_exact = o.wc_exact.load();
   s.column_window = o.column_window.load();
   s.tiled = o.tiled.load();
+  s.prefix_counts = o.prefix_counts.load();
   return s;
 }
 static SweepPlan plan_of(const fmh_matrix* m, const fmh_groups* g, int mode, size_t row_count) {
@@ -49,6 +50,15 @@ extern "C" int fmh_sweep_tiled(const fmh_matrix* m, const fmh_groups* g, int mod
   FMH_TRY(check_probe(m, g));
   if (tiled) *tiled = plan_of(m, g, mode, 1).tiled ? 1 : 0;
   if (image_bytes) *image_bytes = m->p0t ? m->p0t_bytes : 0;
+  return FMH_OK;
+}
+
+extern "C" int fmh_sweep_prefix(const fmh_matrix* m, const fmh_groups* g, int mode, int* uses_table, uint32_t* vectors_read, size_t* table_bytes) {
+  FMH_TRY(check_probe(m, g));
+  const SweepPlan plan = plan_of(m, g, mode, 1);
+  if (uses_table) *uses_table = plan.prefix ? 1 : 0;
+  if (vectors_read) *vectors_read = plan.prefix ? plan.prefix_vecs : plan.win.count;
+  if (table_bytes) *table_bytes = m->p0c ? m->p0c_bytes : 0;
   return FMH_OK;
 }
 
@@ -113,6 +123,15 @@ int fmhi::enqueue_sweep(const fmh_matrix* m, const fmh_groups* g, int mode, Swee
     a.mask_bits = g->mask_bits + (size_t)win.first * 8;  // one 16-bit word per 16 columns: eight per vector
     a.derived_group = win.derived;
     a.row_alt = win.derived >= 0 ? m->row_alt : nullptr;
+  }
+  // the table form: the whole image, the prefix counts and the counted groups' entries and edges; the masks are not read
+  a.prefix = nullptr;
+  if (plan.prefix) {
+    a.mv.data = m->p0t;
+    a.mv.nvec = plan.prefix_vecs;
+    a.prefix = m->p0c;
+    a.prefix_group[0] = plan.prefix_group[0];
+    a.prefix_group[1] = plan.prefix_group[1];
   }
   a.flat_slots = 0;
   a.flat_defer = 1;

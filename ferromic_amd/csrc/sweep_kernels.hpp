@@ -68,6 +68,16 @@ struct WcShape {
 };
 constexpr int kMaxWcSlots = 1 + (8 * 7) / 2;
 
+// One counted group of a sweep whose members are one column range, answered from the prefix counts of plane 0 (fmh_matrix::p0c, DESIGN.md
+// section 3.5d): its whole vectors [b_lo, b_hi) are P[b_hi] - P[b_lo] (b = 0 means "not loaded": P[0] = 0, and b_lo = b_hi = 0 when the range
+// holds no whole vector), and the at most two vectors it shares with other columns are read and counted under edge_mask.
+struct PrefixGroup {
+  uint32_t b_lo, b_hi;
+  uint32_t n_edges;          // 0, 1 or 2
+  uint32_t edge_vec[2];      // vector index in the row; unused slots: 0 with a zero mask
+  uint32_t edge_mask[2][4];  // the group's members among the 128 columns of that vector
+};
+
 struct SweepArgs {
   MatrixView mv;
   const uint8_t* masks;   // device [P][mask_pitch] 0/1 bytes, zero beyond the row
@@ -113,6 +123,10 @@ struct SweepArgs {
   // block partials
   double* part_f64;        // [grid][kMaxF64]
   unsigned long long* part_u64;  // [grid][kMaxU64]
+  // the table form of the tiled route (sweep_kernel_tiled_prefix): the prefix counts, null on every other launch, and the counted group(s) in
+  // the kernel's order (both groups, the only one, or the one that is not derived); mv.data is then the whole image and mv.nvec is unused
+  const uint16_t* prefix;
+  PrefixGroup prefix_group[2];
 };
 
 // slots of the per-block partial vectors

@@ -2,7 +2,7 @@
 // workgroup takes and the deferral's room, or the status and message of a combination that is refused.  plan_sweep() is a pure function of
 // its arguments: it makes no HIP call, reads no option, no environment and no global (sweep_plan_check.hip runs it on a machine without a
 // GPU and tests/sweep_plans.tsv holds what it must answer).  enqueue_sweep (sweep_dispatch.hip) fills the kernel arguments from the plan and
-// dispatches on plan.route; the probes (fmh_sweep_window, fmh_sweep_tiled) and the helpers of the statistic entry points read the same plan
+// dispatches on plan.route; the probes (fmh_sweep_window, fmh_sweep_tiled, fmh_sweep_prefix) and the helpers of the statistic entry points read the same plan
 // or the predicates below, so that no caller re-derives a piece of the decision.
 #pragma once
 
@@ -18,7 +18,7 @@ namespace fmhi {
 // The switches a plan depends on, read once per enqueue (snapshot_plan_options, sweep_dispatch.hip).
 struct PlanOptions {
   long long layout_bytes = 0, mask_mode = -1, defer_tiles = 0, packed_lpr = 0, packed_unroll = 0, packed_no_prefetch = 0, counts_mfma = 0, unroll = 0;
-  long long flat = -1, wc_exact = 1, column_window = 1, tiled = -1;
+  long long flat = -1, wc_exact = 1, column_window = 1, tiled = -1, prefix_counts = 1;
 };
 // The device's two LDS figures (abi.hip): what a workgroup's masks may take, and the LDS of a CU.
 struct LdsFigures {
@@ -68,6 +68,11 @@ struct SweepPlan {
   ColumnWindow win{0, 0, -1};
   bool windowed = false;
   bool tiled = false;  // the sweep reads the tile-transposed image (decided with the window, before any refusal: the probes report both)
+  // the table form of the tiled route (plan_prefix): every counted group is answered from the prefix counts; `win` stays the hull the groups
+  // span (what fmh_sweep_window reports on every route), prefix_vecs is what the kernel still reads per row: the groups' edge vectors
+  bool prefix = false;
+  uint32_t prefix_vecs = 0;
+  fmh::PrefixGroup prefix_group[2] = {};  // the counted groups in the kernel's order
   SweepRoute route = SweepRoute::none;
   int lpr = 16, unroll = 4;
   uint32_t nvec_pad = 0;
@@ -138,6 +143,41 @@ inline bool plan_tiled(const fmh_matrix& m, const fmh_groups& g, int mode, bool 
   return o.tiled > 0 || tiled_route_default(win.count, m.pvec);
 }
 
+// One contiguous group [c0, c1) of a row of `pvec` vectors and `columns` columns as two table entries and at most two edge vectors.  Whole
+// vectors: [ceil(c0 / 128), floor(c1 / 128)), and up to boundary pvec when the range ends with the row (P[pvec] is the row total: the last
+// vector's columns past the row are not counted there).  What is left of the range on either side is an edge: part of one vector, read and
+// counted under a mask.  A range inside one vector is that vector alone.
+inline fmh::PrefixGroup plan_prefix_group(uint32_t c0, uint32_t c1, uint32_t pvec, uint32_t columns) {
+  fmh::PrefixGroup g{};
+  auto edge = [&](uint32_t lo, uint32_t hi) {  // columns [lo, hi) of one vector
+    const uint32_t k = g.n_edges++, v = lo / 128;
+    g.edge_vec[k] = v;
+    for (uint32_t c = lo; c < hi; ++c) g.edge_mask[k][(c - v * 128) / 32] |= 1u << (c % 32);
+  };
+  const uint32_t v_lo = (c0 + 127) / 128, v_hi = c1 == columns ? pvec : c1 / 128;
+  if (v_lo > v_hi) { edge(c0, c1); return g; }
+  if (c0 % 128) edge(c0, std::min(v_lo * 128, c1));  // (a range that starts inside the row's last vector ends with the row, not the vector)
+  if (v_hi < pvec && v_hi * 128 < c1) edge(v_hi * 128, c1);
+  if (v_hi > v_lo) { g.b_lo = v_lo; g.b_hi = v_hi; }
+  return g;
+}
+
+// The table form: on the tiled route of a matrix that holds the prefix counts, when EVERY counted group (all but the
+// derived one) is one column range.  A sweep with a counted group that is not keeps today's window for all of its groups; one that counts
+// nothing (a single group of every column) reads no vector either way.  FMH_PREFIX_COUNTS=0 keeps the window with the table present.
+inline void plan_prefix(SweepPlan& p, const fmh_matrix& m, const fmh_groups& g, const PlanOptions& o) {
+  if (!p.tiled || !m.p0c || o.prefix_counts == 0 || g.n_groups > 2) return;
+  int n = 0;
+  for (int i = 0; i < g.n_groups; ++i) {
+    if (i == p.win.derived) continue;
+    if (!g.contiguous[i] || g.col_end[i] > m.columns) return;
+    p.prefix_group[n++] = plan_prefix_group(g.col_first[i], g.col_end[i], m.pvec, m.columns);
+  }
+  if (n == 0) return;
+  p.prefix = true;
+  for (int q = 0; q < n; ++q) p.prefix_vecs += p.prefix_group[q].n_edges;
+}
+
 __attribute__((format(printf, 3, 4))) inline const SweepPlan& plan_refuse(SweepPlan& p, int status, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -159,6 +199,7 @@ inline SweepPlan plan_sweep(const fmh_matrix& m, const fmh_groups& g, int mode, 
   const uint32_t row_vecs = p.win.count;  // vectors a row of this sweep has: what sizes lanes per row, batch depth, LDS and deferral below
   p.windowed = packed && (p.win.first != 0 || p.win.count != m.pvec || p.win.derived >= 0);
   p.tiled = plan_tiled(m, g, mode, packed, flat_wanted, p.win, opt);
+  plan_prefix(p, m, g, opt);
   if (row_count == 0) { p.empty = true; return p; }
   p.unroll = opt.unroll == 8 ? 8 : 4;
   p.nvec_pad = (uint32_t)round_up(m.nvec, 16 * p.unroll);

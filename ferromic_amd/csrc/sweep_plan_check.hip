@@ -1,9 +1,13 @@
 // sweep_plan_check.hip — prints the plan (sweep_plan.hpp) of a fixed list of sweeps, one tab-separated line per case with every field of
-// the plan; tests/test_sweep_plan_cpu.py compares the output with tests/sweep_plans.tsv line by line.  The handles are built on the host
+// the plan; tests/test_sweep_plan_cpu.py compares the output with tests/sweep_plans.tsv line by line.  `sweep_plan_check prefix` prints the
+// table form's cases instead (plan_prefix: groups given as column ranges on matrices that hold the prefix counts), which
+// tests/test_prefix_plan_cpu.py checks against the definition.  The handles are built on the host
 // with dummy device pointers that are never dereferenced, and no HIP runtime call is made: the program runs on a machine without a GPU.
 // `make plan_check` builds it; the expected table was produced by the decision code as it stood before the plan existed.
 #include <cstdio>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "sweep_plan.hpp"
 
@@ -159,9 +163,110 @@ void run(const char* set, const MatrixSpec& ms, const Sweep& sw, Geometry geo, b
   print_case(std::string(set) + "/" + matrix_name(ms, o.layout_bytes) + tail, m, g, sw.mode, row_count, o, lds);
 }
 
+// ---- the table form (plan_prefix): groups as column ranges [c0, c1), several ranges = a group that is not contiguous -----------------------
+struct Range {
+  uint32_t c0, c1;
+};
+struct RangeGroup {
+  std::vector<Range> ranges;
+};
+fmh_groups make_range_groups(const fmh_matrix& m, const std::vector<RangeGroup>& gs) {
+  fmh_groups g;
+  const int n = (int)gs.size();
+  g.n_groups = n;
+  g.padded = n <= 1 ? 1 : 2;
+  g.masks = kPtr;
+  g.mask_bits = (uint16_t*)kPtr;
+  g.pitch = m.pitch;
+  g.mask_pitch = (m.pitch + 2047) / 2048 * 2048;
+  g.columns = m.columns;
+  std::vector<int> seen(m.columns, 0);
+  for (int i = 0; i < n; ++i) {
+    uint32_t lo = UINT32_MAX, hi = 0, size = 0;
+    for (const Range& r : gs[i].ranges) {
+      lo = std::min(lo, r.c0);
+      hi = std::max(hi, r.c1);
+      size += r.c1 - r.c0;
+      for (uint32_t c = r.c0; c < r.c1; ++c) ++seen[c];
+    }
+    g.sizes[i] = size;
+    g.vec_first[i] = lo / 128;
+    g.vec_last[i] = (hi - 1) / 128;
+    g.col_first[i] = lo;
+    g.col_end[i] = hi;
+    g.contiguous[i] = size == hi - lo;
+  }
+  g.disjoint = g.covers = true;
+  for (int s : seen) {
+    if (s > 1) g.disjoint = false;
+    if (s == 0) g.covers = false;
+  }
+  return g;
+}
+void print_prefix_case(const char* what, uint32_t W, const std::vector<RangeGroup>& gs, int mode, const PlanOptions& o, bool table) {
+  fmh_matrix m = make_matrix(MatrixSpec{kPackedOnly, 1, false, W});
+  m.p0c = table ? (uint16_t*)kPtr : nullptr;
+  m.p0c_bytes = table ? 1 : 0;
+  const fmh_groups g = make_range_groups(m, gs);
+  const SweepPlan p = plan_sweep(m, g, mode, 5000, o, kLds160);
+  std::string name = std::string(what) + "/w" + std::to_string(W) + "/c" + std::to_string(m.columns) + "/m" + std::to_string(mode) + "/";
+  for (size_t i = 0; i < gs.size(); ++i) {
+    if (i) name += "|";
+    for (size_t k = 0; k < gs[i].ranges.size(); ++k) name += (k ? "+" : "") + std::to_string(gs[i].ranges[k].c0) + "-" + std::to_string(gs[i].ranges[k].c1);
+  }
+  printf("%s\t%d\t%s\t%d\t%d\t%u\t%u\t%u\t%d", name.c_str(), p.status, route_name(p.route), (int)p.tiled, (int)p.prefix, p.prefix_vecs, p.win.first, p.win.count, p.win.derived);
+  const int counted = p.prefix ? g.n_groups - (p.win.derived >= 0 ? 1 : 0) : 0;
+  for (int q = 0; q < counted; ++q) {
+    const PrefixGroup& pg = p.prefix_group[q];
+    printf("\t%u,%u,%u", pg.b_lo, pg.b_hi, pg.n_edges);
+    for (int k = 0; k < 2; ++k) printf(",%u:%08x.%08x.%08x.%08x", pg.edge_vec[k], pg.edge_mask[k][0], pg.edge_mask[k][1], pg.edge_mask[k][2], pg.edge_mask[k][3]);
+  }
+  printf("\n");
+  ++g_cases;
+}
+int prefix_cases() {
+  PlanOptions on;
+  on.tiled = 1;  // the route wherever it is built: the table form is decided on top of it
+  const int one = kModeSummary | kModeDiversity, two = kModeSummary | kModeHudson;
+  // 1. the edges first: a range of whole vectors only (no vector read), one that ends / starts on a vector boundary, one column inside it, a
+  //    range inside one vector, two adjacent partial vectors with nothing whole between them, the whole row
+  for (uint32_t W : {1u, 2u, 3u, 40u}) {
+    const uint32_t cols = W * 128 - 5;
+    std::vector<Range> rs = {{0, cols}, {0, 1}, {cols - 1, cols}, {3, 100u < cols ? 100u : cols - 1}};
+    if (W >= 2) for (Range r : {Range{0, 128}, Range{0, 127}, Range{0, 129}, Range{1, 128}, Range{128, cols}, Range{127, cols}, Range{129, cols}, Range{100, 200}, Range{127, 129}}) rs.push_back(r);
+    if (W >= 3) for (Range r : {Range{128, 256}, Range{128, 257}, Range{127, 256}, Range{129, 255}, Range{130, 140}, Range{1, cols - 1}}) rs.push_back(r);
+    if (W == 40) for (Range r : {Range{0, 2500}, Range{2500, cols}, Range{1280, 3840}, Range{1281, 3839}, Range{4992, cols}, Range{4991, cols}, Range{4993, cols - 1}}) rs.push_back(r);
+    for (const Range& r : rs) print_prefix_case("one", W, {RangeGroup{{r}}}, one, on, true);
+    // two groups: a partition (one derived, the other from the table), two ranges with a gap (both counted), ranges that share a vector
+    std::vector<std::pair<Range, Range>> pairs = {{{0, cols / 2}, {cols / 2, cols}}, {{0, 64u < cols / 2 ? 64u : 1u}, {cols / 2, cols}}, {{cols / 2, cols}, {0, cols / 2}}};
+    if (W >= 2) for (auto pr : {std::pair<Range, Range>{{0, 128}, {128, cols}}, {{0, 100}, {110, 200}}, {{10, 128}, {128, 250}}}) pairs.push_back(pr);
+    if (W == 40) for (auto pr : {std::pair<Range, Range>{{0, 2500}, {2500, cols}}, {{0, 2560}, {2560, cols}}, {{100, 1000}, {3000, 4000}}, {{0, 4900}, {4900, cols}}}) pairs.push_back(pr);
+    for (const auto& pr : pairs) print_prefix_case("two", W, {RangeGroup{{pr.first}}, RangeGroup{{pr.second}}}, two, on, true);
+  }
+  // 2. a counted group that is not one range keeps the window, whatever the other one is; a derived one does not matter
+  print_prefix_case("split", 40, {RangeGroup{{{0, 100}, {200, 300}}}}, one, on, true);
+  print_prefix_case("split", 40, {RangeGroup{{{0, 100}, {200, 300}}}, RangeGroup{{{1000, 2000}}}}, two, on, true);
+  print_prefix_case("split", 40, {RangeGroup{{{1000, 2000}}}, RangeGroup{{{0, 1000}, {2000, 5115}}}}, two, on, true);   // the split group is derived
+  print_prefix_case("split", 40, {RangeGroup{{{0, 1000}, {2000, 5115}}}, RangeGroup{{{1000, 2000}}}}, two, on, true);
+  // 3. no table, the table switched off, the route switched off, the default route rule (seven eighths of the row), W&C
+  PlanOptions off = on, untiled = on, dflt;
+  off.prefix_counts = 0;
+  untiled.tiled = 0;
+  const std::vector<RangeGroup> half = {RangeGroup{{{0, 2500}}}, RangeGroup{{{2500, 5115}}}};
+  print_prefix_case("notable", 40, half, two, on, false);
+  print_prefix_case("off", 40, half, two, off, true);
+  print_prefix_case("untiled", 40, half, two, untiled, true);
+  print_prefix_case("default", 40, half, two, dflt, true);
+  print_prefix_case("default", 40, {RangeGroup{{{0, 2500}}}, RangeGroup{{{2500, 5000}}}}, two, dflt, true);  // 40 of 40 vectors: the row-major route
+  print_prefix_case("wc", 40, half, kModeWc, on, true);
+  fprintf(stderr, "sweep_plan_check: %zu prefix cases\n", g_cases);
+  return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "prefix") return prefix_cases();
   const PlanOptions defaults;
   PlanOptions bytes_forced;
   bytes_forced.layout_bytes = 1;

@@ -41,11 +41,42 @@ int launch_counted(const SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int
   return launch_batch<P, MODE, P>(a, st, ctx, grid);
 }
 
+// the table form: every counted group from the prefix counts and its edge vectors (at least one group is counted)
+template <int P, int MODE, int C>
+int launch_prefix(const SweepArgs& args, hipStream_t st, const LaunchCtx& ctx, int* grid_out) {
+  if constexpr (C < 1) return fail(FMH_ERR_INVALID, "the table form of the tiled route counts at least one group");
+  else {
+    auto kern = sweep_kernel_tiled_prefix<P, MODE, C>;
+    static thread_local OccupancyCache cache;
+    int occ = 0;
+    FMH_TRY(cached_occupancy(kern, kBlock, 0, 8, false, cache, 0, &occ));
+    return timed_launch(kern, persistent_grid(occ, args.row_count, kWavesPerBlock, ctx), kBlock, 0, st, ctx, args, grid_out);
+  }
+}
+template <int P, int MODE>
+int launch_prefix_counted(const SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int* grid) {
+  if (a.derived_group >= 0) return launch_prefix<P, MODE, P - 1>(a, st, ctx, grid);
+  return launch_prefix<P, MODE, P>(a, st, ctx, grid);
+}
+
 }  // namespace
 
 // a.mv.data = the image at the window's first vector, a.mv.nvec = the window's vectors, a.mv.pitch = 16 x the vectors of a whole row,
 // a.mask_bits at the window's first vector; a.derived_group / a.row_alt as on the row-major routes
 int launch_sweep_tiled(int P, int mode, const SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int* grid) {
+  if (a.prefix) {  // a.mv.data = the whole image, a.prefix_group = the counted group(s): enqueue_sweep filled them from the plan
+    const uint32_t pvec = (uint32_t)(a.mv.pitch / 16);
+    if (a.derived_group >= P || (a.derived_group >= 0 && !a.row_alt)) return fail(FMH_ERR_INVALID, "the tiled route takes a derived group with its row totals");
+    for (int q = 0; q < P - (a.derived_group >= 0 ? 1 : 0); ++q) {
+      const PrefixGroup& g = a.prefix_group[q];
+      if (g.b_lo > g.b_hi || g.b_hi > pvec || g.n_edges > 2 || (g.n_edges > 0 && g.edge_vec[0] >= pvec) || (g.n_edges > 1 && g.edge_vec[1] >= pvec))
+        return fail(FMH_ERR_INVALID, "a prefix-count group outside the row's %u vectors", pvec);
+    }
+#define ROW(PV, MODEV) if (P == PV && mode == (MODEV)) return launch_prefix_counted<PV, MODEV>(a, st, ctx, grid);
+    FMH_TILED_BUILDS(ROW)
+#undef ROW
+    return fail(FMH_ERR_UNSUPPORTED, "no tiled sweep kernel for %d groups in mode %d", P, mode);
+  }
   if (a.mv.nvec < 1 || a.mv.pitch < (size_t)a.mv.nvec * 16 || a.derived_group >= P || (a.derived_group >= 0 && !a.row_alt))
     return fail(FMH_ERR_INVALID, "the tiled route takes a window of 1..pitch / 16 vectors and a derived group with its row totals");
 #define ROW(PV, MODEV) if (P == PV && mode == (MODEV)) return launch_counted<PV, MODEV>(a, st, ctx, grid);

@@ -1,5 +1,6 @@
 // sweep_tiled_kernels.hpp — the sweep over the TILE-TRANSPOSED image of plane 0 (fmh_matrix::p0t): packed biallelic
-// matrices with nothing missing, one or two groups, every mode but W&C.  Included by sweep_tiled.hip only.
+// matrices with nothing missing, one or two groups, every mode but W&C; and its table form over the prefix counts (fmh_matrix::p0c, section
+// 3.5d; sweep_kernel_tiled_prefix at the end of the file).  Included by sweep_tiled.hip only.
 //
 //   * the image: the 16 bytes of row r, vector v live at byte (((r >> 6) * pvec + v) * 64 + (r & 63)) * 16 - the 64 rows of an image tile share
 //     the lines of one vector column, so a column window of `n` vectors is n contiguous KiB per tile and every byte of every fetched line
@@ -138,6 +139,88 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel_tiled(const SweepArgs A) 
       } else {
 #pragma unroll
         for (int p = 0; p < P; ++p) alt_mine[p] = C > 0 && p == cg ? cnt[0] : 0u;
+      }
+      derive_group<P>(A.derived_group, row_alt, alt_mine);
+      SiteTally<P> mine;
+      WcSite<P> wc;
+      double hud_dot = 0.0;
+#pragma unroll
+      for (int p = 0; p < P; ++p) { mine.n[p] = A.group_size[p]; mine.alt[p] = alt_mine[p]; mine.distinct[p] = 0; mine.ssq[p] = 0; }
+      mine.n_all = A.mv.columns;
+      finish_biallelic_site<P, MODE>(mine, hud_dot);
+      const size_t my_rel = tile * kTileRows + (size_t)lane;
+      site_epilogue<P, MODE, false, false>(A, my_rel, my_rel < A.row_count, mine, hud_dot, wc, T);
+    }
+  }
+  reduce_block_totals<P, MODE>(A, T);
+}
+
+// The table form: every counted group is one column range, so its whole vectors are two entries of the prefix counts
+// (A.prefix: for image tile T, boundary b and row slot s the u16 at ((T * (pvec + 1) + b) * 64 + s) - 128 contiguous bytes per wave
+// instruction) and only the at most two vectors the range shares with other columns are read from the image and counted, under masks that
+// arrive as kernel arguments.  A group with no whole vector loads no entry, one with no shared vector loads no vector (all wave-uniform).
+// Tile -> wave -> lane, the clamp of the rows past the end, derive_group, finish_biallelic_site, site_epilogue, the stores and
+// reduce_block_totals are sweep_kernel_tiled's: the same integers reach the same f64 operations in the same order.  The next tile's loads
+// are issued before this tile's epilogue and land under it.
+template <int P, int MODE, int C>
+__global__ __launch_bounds__(kBlock) void sweep_kernel_tiled_prefix(const SweepArgs A) {
+  static_assert(P <= 2 && C <= P && C >= P - 1 && C >= 1 && (MODE & kModeWc) == 0, "one or two groups, at most one of them derived, not W&C");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  LaneTotals<P, MODE> T;
+  T.clear();
+  const size_t ntiles = (A.row_count + kTileRows - 1) / kTileRows;
+  const size_t tile_stride = (size_t)gridDim.x * kWavesPerBlock;
+  size_t tile = (size_t)blockIdx.x * kWavesPerBlock + (size_t)wave;
+  if (tile < ntiles) {
+    const uint32_t pvec = (uint32_t)(A.mv.pitch / 16);
+    const int cg = C == P ? 0 : 1 - A.derived_group;
+    struct TileIn {
+      uint32_t row_alt, hi[C], lo[C];
+      uint4 e[C][2];
+    };
+    // this lane's row of relative tile t (rows past the end re-read the last one: their results are discarded), its image tile and its slot there
+    auto load_tile = [&](size_t t, TileIn& in) {
+      const size_t rel = t * kTileRows + (size_t)lane;
+      const size_t row = A.row_begin + (rel < A.row_count ? rel : A.row_count - 1);
+      const size_t it = row >> 6, slot = row & 63;
+      in.row_alt = A.derived_group >= 0 ? A.row_alt[row] : 0u;
+      const uint16_t* pc = A.prefix + it * ((size_t)pvec + 1) * 64 + slot;
+      const uint8_t* px = A.mv.data + (it * pvec * 64 + slot) * 16;
+#pragma unroll
+      for (int q = 0; q < C; ++q) {
+        const PrefixGroup& g = A.prefix_group[q];
+        in.hi[q] = g.b_hi ? (uint32_t)pc[(size_t)g.b_hi * 64] : 0u;
+        in.lo[q] = g.b_lo ? (uint32_t)pc[(size_t)g.b_lo * 64] : 0u;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) in.e[q][k] = (uint32_t)k < g.n_edges ? load_stream(px + (size_t)g.edge_vec[k] * 1024) : make_uint4(0, 0, 0, 0);
+      }
+    };
+    TileIn in;
+    load_tile(tile, in);
+    for (; tile < ntiles; tile += tile_stride) {
+      uint32_t cnt[C];
+#pragma unroll
+      for (int q = 0; q < C; ++q) {
+        const PrefixGroup& g = A.prefix_group[q];
+        cnt[q] = in.hi[q] - in.lo[q];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          cnt[q] = bcnt_add(in.e[q][k].x & g.edge_mask[k][0], cnt[q]);
+          cnt[q] = bcnt_add(in.e[q][k].y & g.edge_mask[k][1], cnt[q]);
+          cnt[q] = bcnt_add(in.e[q][k].z & g.edge_mask[k][2], cnt[q]);
+          cnt[q] = bcnt_add(in.e[q][k].w & g.edge_mask[k][3], cnt[q]);
+        }
+      }
+      const uint32_t row_alt = in.row_alt;
+      load_tile(tile + tile_stride < ntiles ? tile + tile_stride : tile, in);  // after the last tile: its own rows once more (cache hits, unused)
+      uint32_t alt_mine[P];
+      if constexpr (C == P) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) alt_mine[p] = cnt[p];
+      } else {
+#pragma unroll
+        for (int p = 0; p < P; ++p) alt_mine[p] = p == cg ? cnt[0] : 0u;
       }
       derive_group<P>(A.derived_group, row_alt, alt_mine);
       SiteTally<P> mine;

@@ -248,6 +248,34 @@ __global__ __launch_bounds__(256) void tile_planes_kernel(const uint8_t* __restr
   }
 }
 
+// prefix counts of plane 0 from the tile-transposed image (fmh_matrix::p0c): for image tile T, boundary b in [0, pvec] and row slot s, the u16 at
+// ((T * (pvec + 1) + b) * 64 + s) is the popcount of that row over vectors [0, b) - columns past the row's last one are not counted, so b = pvec is
+// row_alt; rows past the last one of the last tile are zero in the image, hence here.  One wave per image tile, lane = row slot: a KiB in and 128
+// bytes out per vector, both contiguous.  The caller guarantees columns <= 65 535.
+__global__ __launch_bounds__(256) void prefix_counts_kernel(const uint8_t* __restrict__ p0t, size_t tiles, uint32_t pvec, uint32_t columns,
+                                                            uint16_t* __restrict__ p0c) {
+  const uint32_t lane = threadIdx.x & 63;
+  const size_t waves = (size_t)gridDim.x * 4;
+  for (size_t tile = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); tile < tiles; tile += waves) {
+    const uint8_t* src = p0t + (tile * pvec * 64 + lane) * 16;
+    uint16_t* dst = p0c + tile * ((size_t)pvec + 1) * 64 + lane;
+    uint32_t acc = 0;
+#pragma unroll 8
+    for (uint32_t v = 0; v < pvec; ++v) {
+      dst[(size_t)v * 64] = (uint16_t)acc;
+      const uint4 a = *reinterpret_cast<const uint4*>(src + (size_t)v * 1024);
+      const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t lo = v * 128 + 32 * k;  // column of the word's bit 0
+        const uint32_t keep = lo + 32 <= columns ? ~0u : (lo >= columns ? 0u : (1u << (columns - lo)) - 1u);
+        acc += __popc(w[k] & keep);
+      }
+    }
+    dst[(size_t)pvec * 64] = (uint16_t)acc;
+  }
+}
+
 // row_hi[r] = 1 when row r of a packed multi-allelic matrix has a bit in plane 1 or plane 2 (a called allele above 1), else 0: the sweeps
 // read the upper planes of those rows only (MatrixView::row_hi).  Sixteen lanes per row, as many 16-byte vectors each as the row needs.
 __global__ __launch_bounds__(256) void row_hi_kernel(const uint8_t* __restrict__ p1, const uint8_t* __restrict__ p2, size_t plane_pitch, size_t rows,

@@ -217,6 +217,14 @@ def sweep_tiled(m: DeviceMatrix, g: Groups, mode: int):
     return bool(tiled.value), image_bytes.value
 
 
+def sweep_prefix(m: DeviceMatrix, g: Groups, mode: int):
+    """fmh_sweep_prefix: (whether the next sweep of `mode` answers its counted groups from the prefix counts, the plane vectors per row it
+    still reads, the table's bytes or 0)."""
+    uses, vecs, table_bytes = C.c_int(), C.c_uint32(), C.c_size_t()
+    _abi.check(_abi.load().fmh_sweep_prefix(m._h, g._h, mode, C.byref(uses), C.byref(vecs), C.byref(table_bytes)))
+    return bool(uses.value), vecs.value, table_bytes.value
+
+
 def _pop_totals(t: _abi.PopTotals) -> Dict[str, float]:
     return dict(haplotype_capacity=int(t.haplotype_capacity), segregating_sites=int(t.segregating_sites),
                 uncallable_sites=int(t.uncallable_sites), pi_sum=float(t.pi_sum))

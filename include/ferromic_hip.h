@@ -218,6 +218,19 @@ int fmh_sweep_window(const fmh_matrix* m, const fmh_groups* g, int mode, uint32_
  * sums are the same bits at equal grids and agree within 1e-9 otherwise (the routes differ in occupancy, hence in their default grids). */
 int fmh_sweep_tiled(const fmh_matrix* m, const fmh_groups* g, int mode, int* tiled, size_t* image_bytes);
 
+/* Host only: whether the next sweep of `mode` over these groups answers its counted groups from the PREFIX COUNTS of bit plane 0 (*uses_table = 1),
+ * how many 16-byte plane vectors per row it still reads (*vectors_read: with the table the groups' partial edge vectors, at most two per counted
+ * group and possibly none; without it the window's vectors, fmh_sweep_window's n_vec), and the size of the table (*table_bytes, 0 when the matrix
+ * holds none).  The table stores, for every row and every vector boundary b = 0 .. vectors_per_row, the alt count of the row's columns before
+ * 128 b as a u16 at byte ((tile * (vectors_per_row + 1) + b) * 64 + (r & 63)) * 2 with tile = r >> 6; it is built beside the tile-transposed image,
+ * under that image's rules, on rows of at most 65 535 columns, and costs 2 * (vectors_per_row + 1) bytes per row.  A group whose members are exactly
+ * one column range [c0, c1) is then the difference of two entries plus the masked counts of the vectors that hold c0 and c1 when those are not
+ * multiples of 128 - integers, so per-site results and regional sums are the bits of the window's.  The table form is taken on the tiled route
+ * (fmh_sweep_tiled) when EVERY counted group is such a range; the derived group (fmh_sweep_window) is chosen as without the table and is still not
+ * counted.  FMH_PREFIX_COUNTS: 0 = no table is built and none is read, 1 = default: matrices of at least 4 096 rows while as much again stays free on
+ * the device, 2 = beside the image at any size without the free-memory test. */
+int fmh_sweep_prefix(const fmh_matrix* m, const fmh_groups* g, int mode, int* uses_table, uint32_t* vectors_read, size_t* table_bytes);
+
 /* ---- per-population summary sweep ------------------------------------------------------------ */
 typedef struct {
   uint64_t haplotype_capacity; /* mask popcount — DensePopulationSummary.haplotype_capacity (1466) */
