@@ -18,6 +18,7 @@ from ._core import (  # noqa: E402,F401
     GenotypeQC,
     HaplotypeScan,
     HaplotypeWindows,
+    HomozygosityRuns,
     HudsonDxyResult,
     HudsonFstResult,
     HudsonFstSite,
@@ -56,6 +57,7 @@ from ._core import (  # noqa: E402,F401
     per_chromosome_pca,
     per_site_diversity,
     polygenic_score,
+    runs_of_homozygosity,
     segregating_sites,
     site_frequency_spectrum,
     watterson_theta,

@@ -137,6 +137,23 @@ class GenotypeSampleStatsOut(C.Structure):
     _fields_ = [("h_call_rate", C.c_void_p), ("h_het_rate", C.c_void_p), ("h_f", C.c_void_p)]
 
 
+class RohParams(C.Structure):
+    _fields_ = [("window", C.c_uint32), ("window_het", C.c_uint32), ("window_missing", C.c_uint32), ("need", C.c_uint8 * 65),
+                ("reserved", C.c_uint8 * 3), ("min_sites", C.c_uint32), ("min_length", C.c_uint32), ("max_gap", C.c_uint32),
+                ("max_bp_per_site", C.c_uint32), ("max_het", C.c_uint32), ("max_missing", C.c_uint32), ("n_bins", C.c_uint32),
+                ("bin_edges", C.c_uint32 * 7)]
+
+
+class RohSegment(C.Structure):
+    _fields_ = [("sample", C.c_uint32), ("n_sites", C.c_uint32), ("n_het", C.c_uint32), ("n_missing", C.c_uint32),
+                ("first_row", C.c_uint64), ("last_row", C.c_uint64)]
+
+
+class RohOut(C.Structure):
+    _fields_ = [("d_n_runs", C.c_void_p), ("d_sum_sites", C.c_void_p), ("d_sum_length", C.c_void_p), ("d_longest_length", C.c_void_p),
+                ("d_bin_runs", C.c_void_p), ("d_bin_length", C.c_void_p)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -252,6 +269,10 @@ SYMBOLS = {
     "fmh_score_exponents": (_i, [_vp, _sz, _sz, _vp]),
     "fmh_score_values": (_i, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fmh_score_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _i, _vp]),
+    "fmh_roh_scan": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(RohParams), _P(RohOut), _vp, _sz, _P(_u64), _vp]),
+    "fmh_roh_scan_host": (_i, [_vp, _vp, _sz, _sz, _P(RohParams), _P(RohOut), _vp, _sz, _P(_u64)]),
+    "fmh_roh_need": (_i, [_d, _u32, _vp]),
+    "fmh_roh_sort_segments": (_i, [_vp, _sz]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

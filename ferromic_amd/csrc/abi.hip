@@ -107,6 +107,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_ASSOC_BUDGET_BYTES", &Options::assoc_budget_bytes, (long long)1 << 30, nullptr},
     {"FMH_SCORE_ITEM_ROWS", &Options::score_item_rows, 0, nullptr},
     {"FMH_SCORE_BUDGET_BYTES", &Options::score_budget_bytes, (long long)1 << 30, nullptr},
+    {"FMH_ROH_ITEM_ROWS", &Options::roh_item_rows, 0, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -918,6 +918,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_assoc.inc"
 #include "pymodule_logistic.inc"
 #include "pymodule_score.inc"
+#include "pymodule_roh.inc"
 
 }  // namespace
 
@@ -1069,6 +1070,7 @@ PYBIND11_MODULE(_core, m) {
   bind_assoc(m, population);
   bind_logistic(m, population);
   bind_score(m, population);
+  bind_roh(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

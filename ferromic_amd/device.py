@@ -1140,6 +1140,115 @@ def logistic_stats(score, variance, outputs=LOGISTIC_STATS) -> Dict[str, np.ndar
     return out
 
 
+# ---- runs of homozygosity: per-sample sliding-window scan along the kept rows ---------------------------------------------------------------
+ROH_DEFAULT_ITEM_ROWS = 4096   # FMH_ROH_ITEM_ROWS unset
+ROH_TABLES = ("n_runs", "sum_sites", "sum_length", "longest_length")
+ROH_SEGMENT_DTYPE = np.dtype([("sample", np.uint32), ("n_sites", np.uint32), ("n_het", np.uint32), ("n_missing", np.uint32),
+                              ("first_row", np.uint64), ("last_row", np.uint64)])
+ROH_NO_LIMIT = 0xFFFFFFFF
+
+
+def roh_need(threshold: float, window: int) -> np.ndarray:
+    """fmh_roh_need (host only): need[65], need[c] for c = 1..window the smallest h >= 1 with h >= threshold * c."""
+    need = np.zeros(65, dtype=np.uint8)
+    _abi.check(_abi.load().fmh_roh_need(float(threshold), int(window), _ptr(need)))
+    return need
+
+
+def roh_params(window=50, window_het=1, window_missing=5, threshold=0.05, need=None, min_sites=100, min_length=1_000_000, max_gap=1_000_000,
+               max_bp_per_site=50_000, max_het=None, max_missing=None, bin_edges=()) -> "_abi.RohParams":
+    """fmh_roh_params with PLINK's defaults; `need` overrides the table of `threshold`; len(bin_edges) + 1 bins when edges are given
+    (bin_edges=None or (): no bins; n_bins may also be set on the result)."""
+    p = _abi.RohParams()
+    p.window, p.window_het, p.window_missing = int(window), int(window_het), int(window_missing)
+    table = roh_need(threshold, window) if need is None else np.ascontiguousarray(need, dtype=np.uint8)
+    for c in range(65):
+        p.need[c] = int(table[c])
+    p.min_sites, p.min_length, p.max_gap, p.max_bp_per_site = int(min_sites), int(min_length), int(max_gap or 0), int(max_bp_per_site or 0)
+    p.max_het = ROH_NO_LIMIT if max_het is None else int(max_het)
+    p.max_missing = ROH_NO_LIMIT if max_missing is None else int(max_missing)
+    edges = list(bin_edges or ())
+    p.n_bins = len(edges) + 1 if edges else 0
+    for b, e in enumerate(edges[:7]):
+        p.bin_edges[b] = int(e)
+    return p
+
+
+@dataclass
+class RohResult:
+    tables: Dict[str, np.ndarray]        # n_runs, sum_sites, sum_length, longest_length: [n] uint64; bin_runs, bin_length: [n][n_bins]
+    segments: Optional[np.ndarray]       # ROH_SEGMENT_DTYPE [min(count, capacity)], in the order they were stored, or None
+    count: Optional[int]                 # the exact number of qualifying runs, or None when segments were not asked for
+
+
+def _roh_result(n, n_bins, get, segments, count):
+    tables = {name: get(name, n) for name in ROH_TABLES}
+    for name in ("bin_runs", "bin_length"):
+        tables[name] = get(name, n * n_bins).reshape(n, n_bins)
+    return RohResult(tables, segments, count)
+
+
+def roh_scan(m: DeviceMatrix, params, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+             positions=None, capacity: Optional[int] = None, stream=None) -> RohResult:
+    """fmh_roh_scan over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all).  `positions` [variants] uint32 (indexed by matrix row) or None.  `capacity`: None = no segments, else the
+    elements of the segment buffer (0: the runs are counted only)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        if positions.size != m.variants:
+            raise ValueError("positions has one entry per row of the matrix")
+    nb = int(params.n_bins)
+    names = ROH_TABLES + ("bin_runs", "bin_length")
+    sizes = {name: n * (nb if name.startswith("bin_") else 1) for name in names}
+    bufs = {name: DeviceBuffer.from_numpy(m.device, np.full(max(sizes[name], 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)) for name in names}
+    out = _abi.RohOut(*[bufs[name].ptr for name in names])
+    d_seg = DeviceBuffer(m.device, max(capacity, 1) * ROH_SEGMENT_DTYPE.itemsize) if capacity else None
+    count = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_roh_scan(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params), C.byref(out),
+                                        d_seg.ptr if d_seg else None, capacity or 0, C.byref(count) if capacity is not None else None, stream))
+    segments = None
+    if capacity is not None:
+        segments = d_seg.to_numpy(ROH_SEGMENT_DTYPE, min(int(count.value), capacity)) if d_seg else np.zeros(0, dtype=ROH_SEGMENT_DTYPE)
+    return _roh_result(n, nb, lambda name, size: bufs[name].to_numpy(np.uint64, size), segments, int(count.value) if capacity is not None else None)
+
+
+def roh_scan_host(state, params, x=None, capacity: Optional[int] = None) -> RohResult:
+    """fmh_roh_scan_host (host only): the same scan over `state` uint8 [K][n] (0 HOM, 1 HET, 2 MISS) and `x` uint32 [K] or None."""
+    state = np.ascontiguousarray(state, dtype=np.uint8)
+    K, n = state.shape
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.size != K:
+            raise ValueError("x has one entry per kept row")
+    nb = int(params.n_bins)
+    names = ROH_TABLES + ("bin_runs", "bin_length")
+    host = {name: np.full(max(n * (nb if name.startswith("bin_") else 1), 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) for name in names}
+    out = _abi.RohOut(*[host[name].ctypes.data for name in names])
+    seg = np.zeros(max(capacity or 0, 1), dtype=ROH_SEGMENT_DTYPE)
+    count = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_roh_scan_host(_ptr(state) if state.size else None, _ptr(x), K, n, C.byref(params), C.byref(out),
+                                             _ptr(seg) if capacity else None, capacity or 0, C.byref(count) if capacity is not None else None))
+    segments = seg[: min(int(count.value), capacity)].copy() if capacity is not None else None
+    return _roh_result(n, nb, lambda name, size: host[name][:size].copy(), segments, int(count.value) if capacity is not None else None)
+
+
+def roh_sort_segments(segments: np.ndarray) -> np.ndarray:
+    """fmh_roh_sort_segments (host only): a copy ordered by (sample, first_row)."""
+    out = np.ascontiguousarray(segments, dtype=ROH_SEGMENT_DTYPE).copy()
+    _abi.check(_abi.load().fmh_roh_sort_segments(_ptr(out) if out.size else None, out.size))
+    return out
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -82,6 +82,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
  *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES   FMH_SCORE_ITEM_ROWS   FMH_SCORE_BUDGET_BYTES
+ *   FMH_ROH_ITEM_ROWS
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -974,6 +975,82 @@ int fmh_score_values(const double* h_weights /* [n_rows][n_columns] */, size_t n
 int fmh_score_stats(const long long* h_dosage_sum, const long long* h_called_sum_or_null /* [n_samples][n_columns] each */,
                     const long long* h_called_total_or_null, const int32_t* h_exponent /* [n_columns] each */, size_t n_samples, size_t n_columns,
                     int mode /* FMH_SCORE_* */, double* h_score /* [n_samples][n_columns] */);   /* host only, no device */
+
+/* ---- runs of homozygosity: per-sample ROH scan from the bit planes (an addition: the reference has none) --------------------------------
+ * Where along the rows each individual is autozygous and for how long: PLINK's --homozyg sliding window, every quantity an integer.  This
+ * text is the DEFINITION; the device (fmh_roh_scan), the host twin (fmh_roh_scan_host) and a plain Python loop agree on every integer.
+ * Matrix, samples, `called` and dosage are fmh_genotype_counts': ploidy 2, a packed image, sample s owns columns 2s and 2s+1, the genotype
+ * is called iff both entries are called and both alleles are <= 1, every plane is masked with the called plane (row_gap / row_hi are
+ * honoured).  n = n_samples; i is a position in the sample list.
+ * Kept rows.  k = 0 .. K-1 are the rows of [row_begin, row_begin + row_count) whose h_keep_or_null byte is non-zero (NULL: every row), in
+ *   ascending order.  x(k) is the position of kept row k: h_positions_or_null[variants] u32, indexed by matrix row as fmh_ehh_scan takes it
+ *   and non-decreasing over the range; NULL means x is the row number.  Only differences of x are used.
+ * State of sample i at kept row k: HOM (called, dosage 0 or 2), HET (called, dosage 1), MISS (not called).
+ * Parameters (fmh_roh_params), all integers: window W (1..64), window_het, window_missing, need[65], min_sites, min_length, max_gap
+ *   (0 = none), max_bp_per_site (0 = none), max_het, max_missing (UINT32_MAX = none), n_bins <= 8 with bin_edges[0 .. n_bins-2] strictly
+ *   ascending (n_bins bins have n_bins - 1 edges; the other entries are ignored).
+ * Windows.
+ *   1. Window t, 0 <= t <= K-W, covers kept rows [t, t+W).  K < W: no window and no run.
+ *   2. Window t is homozygous for a sample iff its HET count <= window_het and its MISS count <= window_missing.
+ * In-run rows.
+ *   3. Row k is covered by the windows t in [max(0, k-W+1), min(k, K-W)]: n_cov(k) of them (fewer near both ends), n_hom(k) of those
+ *      homozygous.  Row k is IN A RUN iff n_hom(k) >= need[n_cov(k)].
+ *   4. fmh_roh_need(threshold, W, need) (host only) fills need[c] for c = 1..W: the smallest integer h >= 1 with
+ *      (double)h >= threshold * (double)c, the product formed once in f64; need[0] and need[W+1 ..] are set to 0 and never read.  This is
+ *      PLINK's --homozyg-window-threshold made an integer table once: the device compares integers only.  Refusals (FMH_ERR_INVALID):
+ *      NULL need, W outside 1..64, a threshold that is not within 0 .. 2 (above 1 no row can be in a run; need stays a byte).
+ * Runs.
+ *   5. break(k), k >= 1, iff max_gap > 0 and x(k) - x(k-1) > max_gap.
+ *   6. A run [f, l] is a maximal stretch of consecutive kept rows that are all in a run, with no break(k) for f < k <= l.
+ *   7. n_sites = l - f + 1; n_het and n_missing = its rows in state HET / MISS; length = x(l) - x(f) + 1 (u64).
+ *   8. A run QUALIFIES iff n_sites >= min_sites, length >= min_length, n_het <= max_het, n_missing <= max_missing, and max_bp_per_site == 0
+ *      or length <= max_bp_per_site * n_sites (the product in u64).
+ * Outputs, exact integers.  Per selected sample, at its list position, device u64 [n], WRITTEN (fmh_roh_out; any pointer may be NULL):
+ *   n_runs, sum_sites, sum_length, longest_length over the sample's qualifying runs, and with n_bins > 0 bin_runs[n][n_bins] and
+ *   bin_length[n][n_bins]: a run falls in bin b = the number of edges <= its length.
+ *   Segments (optional): fmh_roh_segment { sample, n_sites, n_het, n_missing, first_row, last_row }; `sample` is i, the run's position in
+ *   the sample list; rows are those of the matrix relative to row_begin.  d_segments_or_null is a DEVICE buffer of segment_capacity
+ *   elements (NULL: capacity 0); *h_segment_count receives the exact number of qualifying runs of the call even when it exceeds the
+ *   capacity, and the buffer then holds min(count, capacity) distinct true segments in unspecified order.  fmh_roh_sort_segments (host
+ *   only) orders host segments by (sample, first_row).
+ * fmh_roh_scan enqueues on `stream` and synchronises it.  K == 0 or K < W is FMH_OK with zero tables and count 0.
+ * Refusals, all before any launch, in this order.  FMH_ERR_INVALID: NULL matrix or params; n_samples == 0; a sample index out of range or
+ *   a list that is not strictly ascending; a row range past the matrix; window outside 1..64; n_bins > 8 or edges not strictly ascending;
+ *   positions that descend in the range; every output NULL (no table, no segment buffer, no count); a segment buffer without a count
+ *   pointer.  FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix without a packed image (call fmh_matrix_pack first); a range of
+ *   2^32 - 1 rows or more.
+ * Option: FMH_ROH_ITEM_ROWS = the most kept rows of a work item (default 4 096; rounded up to a multiple of 64).  It changes no result, nor
+ *   do FMH_GRID_PER_CU and FMH_GRID_BLOCKS.
+ * fmh_roh_scan_host (host only, no device): the same parameters over h_state u8 [K][n] (0 HOM, 1 HET, 2 MISS) and h_x u32 [K]
+ *   (non-decreasing; NULL = k); the tables and segments are host arrays (fmh_roh_out's pointers are then host pointers), rows of a
+ *   segment are kept rows k.  A serial state machine over the whole range.  Refusals (FMH_ERR_INVALID): NULL params; n == 0; NULL state
+ *   with K > 0; window, bins, descending x, outputs and segments as above; a state above 2.
+ * Not built: sharding over devices, run_vcf wiring, u8 rows, end-trimming of hets at run edges (PLINK trims; a run here is the maximal
+ *   stretch of in-run rows).
+ */
+typedef struct {
+  uint32_t window, window_het, window_missing;
+  uint8_t need[65];                 /* need[c], c = 1..window (fmh_roh_need) */
+  uint8_t reserved[3];
+  uint32_t min_sites, min_length, max_gap, max_bp_per_site, max_het, max_missing;
+  uint32_t n_bins;                  /* 0..8 */
+  uint32_t bin_edges[7];            /* the first n_bins - 1 are read */
+} fmh_roh_params;
+typedef struct { uint32_t sample, n_sites, n_het, n_missing; uint64_t first_row, last_row; } fmh_roh_segment;
+typedef struct {
+  unsigned long long *d_n_runs, *d_sum_sites, *d_sum_length, *d_longest_length;  /* each [n], written; any may be NULL */
+  unsigned long long *d_bin_runs, *d_bin_length;                                  /* each [n][n_bins], written; any may be NULL */
+} fmh_roh_out;
+int fmh_roh_scan(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                 size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count] */,
+                 const uint32_t* h_positions_or_null /* [variants] */, const fmh_roh_params* params, const fmh_roh_out* out_or_null,
+                 fmh_roh_segment* d_segments_or_null, size_t segment_capacity, uint64_t* h_segment_count /* may be NULL without a buffer */,
+                 void* stream);
+int fmh_roh_scan_host(const uint8_t* h_state /* [n_kept][n_samples] */, const uint32_t* h_x_or_null /* [n_kept] */, size_t n_kept, size_t n_samples,
+                      const fmh_roh_params* params, const fmh_roh_out* out_or_null /* host pointers */, fmh_roh_segment* h_segments_or_null,
+                      size_t segment_capacity, uint64_t* h_segment_count);   /* host only, no device */
+int fmh_roh_need(double threshold, uint32_t window, uint8_t* need /* [65] */);   /* host only, no device */
+int fmh_roh_sort_segments(fmh_roh_segment* h_segments, size_t count);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
