@@ -19,6 +19,7 @@ from ._core import (  # noqa: E402,F401
     HaplotypeScan,
     HaplotypeWindows,
     HomozygosityRuns,
+    IbdSegments,
     HudsonDxyResult,
     HudsonFstResult,
     HudsonFstSite,
@@ -44,6 +45,7 @@ from ._core import (  # noqa: E402,F401
     hudson_fst,
     hudson_fst_sites,
     hudson_fst_with_sites,
+    ibd_segments,
     ihs,
     inversion_allele_frequency,
     joint_site_frequency_spectrum,

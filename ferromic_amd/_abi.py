@@ -154,6 +154,20 @@ class RohOut(C.Structure):
                 ("d_bin_runs", C.c_void_p), ("d_bin_length", C.c_void_p)]
 
 
+class IbdParams(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("min_sites", C.c_uint32), ("min_length", C.c_uint32), ("max_gap", C.c_uint32),
+                ("max_bp_per_site", C.c_uint32), ("max_missing", C.c_uint32)]
+
+
+class IbdSegment(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("n_sites", C.c_uint32), ("n_missing", C.c_uint32),
+                ("first_row", C.c_uint64), ("last_row", C.c_uint64)]
+
+
+class IbdOut(C.Structure):
+    _fields_ = [("d_n_segments", C.c_void_p), ("d_sum_sites", C.c_void_p), ("d_sum_length", C.c_void_p), ("d_longest_length", C.c_void_p)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -273,6 +287,9 @@ SYMBOLS = {
     "fmh_roh_scan_host": (_i, [_vp, _vp, _sz, _sz, _P(RohParams), _P(RohOut), _vp, _sz, _P(_u64)]),
     "fmh_roh_need": (_i, [_d, _u32, _vp]),
     "fmh_roh_sort_segments": (_i, [_vp, _sz]),
+    "fmh_ibd_scan": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(IbdParams), _P(IbdOut), _vp, _sz, _P(_u64), _vp]),
+    "fmh_ibd_scan_host": (_i, [_vp, _vp, _sz, _sz, _P(IbdParams), _P(IbdOut), _vp, _sz, _P(_u64)]),
+    "fmh_ibd_sort_segments": (_i, [_vp, _sz]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

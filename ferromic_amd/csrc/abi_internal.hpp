@@ -97,6 +97,8 @@ struct Options {
   std::atomic<long long> score_item_rows{0};     // FMH_SCORE_ITEM_ROWS: rows per work item of the polygenic score's sums kernel, rounded up to a multiple of 64; 0 = 4 096
   std::atomic<long long> score_budget_bytes{(long long)1 << 30};  // FMH_SCORE_BUDGET_BYTES: device bytes the digits and slabs of one fmh_score_sums call may take; ferromic.polygenic_score sizes its row chunks by it
   std::atomic<long long> roh_item_rows{0};       // FMH_ROH_ITEM_ROWS: kept rows per work item of the runs-of-homozygosity scan kernel, rounded up to a multiple of 64; 0 = 4 096
+  std::atomic<long long> ibd_item_rows{0};       // FMH_IBD_ITEM_ROWS: kept rows per row block of the IBD pair kernel, rounded up to a multiple of 64; 0 = sized by the launch
+  std::atomic<long long> ibd_budget_bytes{(long long)4 << 30};  // FMH_IBD_BUDGET_BYTES: device bytes the sample-major bit image and the block records of one fmh_ibd_scan call may take
   std::atomic<long long> graph{0};               // FMH_GRAPH: 1 = replay a repeated pipelined sweep on a local communicator from a captured hipGraph
   std::atomic<unsigned long long> generation{0}; // bumped by every fmh_set_option: a captured launch is never replayed across an option change
 };

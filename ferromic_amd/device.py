@@ -1249,6 +1249,89 @@ def roh_sort_segments(segments: np.ndarray) -> np.ndarray:
     return out
 
 
+# ---- IBD segments: pairwise shared-segment scan along the kept rows ----------------------------------------------------------------------------
+IBD1, IBD2 = 1, 2
+IBD_TABLES = ("n_segments", "sum_sites", "sum_length", "longest_length")
+IBD_SEGMENT_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("n_sites", np.uint32), ("n_missing", np.uint32),
+                              ("first_row", np.uint64), ("last_row", np.uint64)])
+IBD_NO_LIMIT = 0xFFFFFFFF
+
+
+def ibd_params(mode=IBD1, min_sites=436, min_length=7_000_000, max_gap=1_000_000, max_bp_per_site=0, max_missing=None) -> "_abi.IbdParams":
+    """fmh_ibd_params with IBIS's defaults (7 cM read at 1 cM per Mb, 436 markers); mode is IBD1, IBD2, "ibd1" or "ibd2"."""
+    p = _abi.IbdParams()
+    p.mode = {"ibd1": IBD1, "ibd2": IBD2}.get(mode, mode) if isinstance(mode, str) else int(mode)
+    p.min_sites, p.min_length, p.max_gap, p.max_bp_per_site = int(min_sites), int(min_length), int(max_gap or 0), int(max_bp_per_site or 0)
+    p.max_missing = IBD_NO_LIMIT if max_missing is None else int(max_missing)
+    return p
+
+
+@dataclass
+class IbdResult:
+    tables: Dict[str, np.ndarray]        # n_segments, sum_sites, sum_length, longest_length: [n][n] uint64
+    segments: Optional[np.ndarray]       # IBD_SEGMENT_DTYPE [min(count, capacity)], in the order they were stored, or None
+    count: Optional[int]                 # the exact number of qualifying runs, or None when segments were not asked for
+
+
+def ibd_scan(m: DeviceMatrix, params, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+             positions=None, capacity: Optional[int] = None, stream=None, tables=IBD_TABLES) -> IbdResult:
+    """fmh_ibd_scan over rows [row_begin, row_begin + row_count) for all pairs of the samples `samples` (ascending sample numbers; None = the
+    first n_samples, default all).  `positions` [variants] uint32 (indexed by matrix row) or None.  `capacity`: None = no segments, else the
+    elements of the segment buffer (0: the runs are counted only).  `tables`: the tables asked for; they are pre-filled with junk."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        if positions.size != m.variants:
+            raise ValueError("positions has one entry per row of the matrix")
+    bufs = {name: DeviceBuffer.from_numpy(m.device, np.full(max(n * n, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)) for name in tables}
+    out = _abi.IbdOut(*[bufs[name].ptr if name in bufs else None for name in IBD_TABLES])
+    d_seg = DeviceBuffer(m.device, max(capacity, 1) * IBD_SEGMENT_DTYPE.itemsize) if capacity else None
+    count = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_ibd_scan(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params),
+                                        C.byref(out) if tables else None, d_seg.ptr if d_seg else None, capacity or 0,
+                                        C.byref(count) if capacity is not None else None, stream))
+    segments = None
+    if capacity is not None:
+        segments = d_seg.to_numpy(IBD_SEGMENT_DTYPE, min(int(count.value), capacity)) if d_seg else np.zeros(0, dtype=IBD_SEGMENT_DTYPE)
+    return IbdResult({name: bufs[name].to_numpy(np.uint64, n * n).reshape(n, n) for name in tables}, segments,
+                     int(count.value) if capacity is not None else None)
+
+
+def ibd_scan_host(dosage, params, x=None, capacity: Optional[int] = None) -> IbdResult:
+    """fmh_ibd_scan_host (host only): the same scan over `dosage` uint8 [K][n] (0, 1, 2; 3 = not called) and `x` uint32 [K] or None."""
+    dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
+    K, n = dosage.shape
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.size != K:
+            raise ValueError("x has one entry per kept row")
+    host = {name: np.full(max(n * n, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) for name in IBD_TABLES}
+    out = _abi.IbdOut(*[host[name].ctypes.data for name in IBD_TABLES])
+    seg = np.zeros(max(capacity or 0, 1), dtype=IBD_SEGMENT_DTYPE)
+    count = C.c_uint64(0)
+    _abi.check(_abi.load().fmh_ibd_scan_host(_ptr(dosage) if dosage.size else None, _ptr(x), K, n, C.byref(params), C.byref(out),
+                                             _ptr(seg) if capacity else None, capacity or 0, C.byref(count) if capacity is not None else None))
+    segments = seg[: min(int(count.value), capacity)].copy() if capacity is not None else None
+    return IbdResult({name: host[name][: n * n].copy().reshape(n, n) for name in IBD_TABLES}, segments,
+                     int(count.value) if capacity is not None else None)
+
+
+def ibd_sort_segments(segments: np.ndarray) -> np.ndarray:
+    """fmh_ibd_sort_segments (host only): a copy ordered by (a, b, first_row)."""
+    out = np.ascontiguousarray(segments, dtype=IBD_SEGMENT_DTYPE).copy()
+    _abi.check(_abi.load().fmh_ibd_sort_segments(_ptr(out) if out.size else None, out.size))
+    return out
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -82,7 +82,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
  *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES   FMH_SCORE_ITEM_ROWS   FMH_SCORE_BUDGET_BYTES
- *   FMH_ROH_ITEM_ROWS
+ *   FMH_ROH_ITEM_ROWS   FMH_IBD_ITEM_ROWS   FMH_IBD_BUDGET_BYTES
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -1051,6 +1051,70 @@ int fmh_roh_scan_host(const uint8_t* h_state /* [n_kept][n_samples] */, const ui
                       size_t segment_capacity, uint64_t* h_segment_count);   /* host only, no device */
 int fmh_roh_need(double threshold, uint32_t window, uint8_t* need /* [65] */);   /* host only, no device */
 int fmh_roh_sort_segments(fmh_roh_segment* h_segments, size_t count);   /* host only, no device */
+
+/* ---- IBD segments: pairwise shared-segment scan from the bit planes (an addition: the reference has none) -------------------------------
+ * Where along the rows two diploid samples share a segment identical by descent and for how long: the IBS detector of IBIS, TRUFFLE,
+ * GERMLINE and PLINK's --segment on unphased genotypes, every quantity an integer.  This text is the DEFINITION; the device
+ * (fmh_ibd_scan), the host twin (fmh_ibd_scan_host) and a plain Python loop agree on every integer.
+ * Matrix, samples, `called` and dosage are fmh_genotype_counts' / fmh_roh_scan's: ploidy 2, a packed image, sample s owns columns 2s and
+ * 2s+1, the genotype is called iff both entries are called and both alleles are <= 1, every plane is masked with the called plane
+ * (row_gap / row_hi are honoured).  n = n_samples; i < j are positions in the sample list; the pairs are all n (n - 1) / 2 unordered
+ * pairs of the list.
+ * Kept rows k = 0 .. K-1, their positions x(k) and break(k) are exactly fmh_roh_scan's ("Kept rows" and rule 5): the h_keep_or_null
+ *   bytes; h_positions_or_null[variants] u32 indexed by matrix row, non-decreasing over the range, NULL meaning the row number;
+ *   break(k), k >= 1, iff max_gap > 0 and x(k) - x(k-1) > max_gap.
+ * State of pair (i, j) at kept row k: MISS if either genotype is not called; otherwise DISC iff
+ *   mode FMH_IBD1: one dosage is 0 and the other is 2 (opposite homozygotes, IBS0);
+ *   mode FMH_IBD2: the dosages differ;
+ *   otherwise CONC.
+ * Runs.
+ *   1. A run [f, l] is a maximal stretch of consecutive kept rows none of which is DISC, with no break(k) for f < k <= l.  MISS rows are
+ *      compatible and may stand at either end: there is no trimming.  No error tolerance: a single DISC row ends a run.
+ *   2. n_sites = l - f + 1; n_missing = the run's MISS rows; length = x(l) - x(f) + 1 (u64).
+ *   3. A run QUALIFIES iff n_sites >= min_sites, length >= min_length, n_missing <= max_missing (UINT32_MAX = none), and
+ *      max_bp_per_site == 0 or length <= max_bp_per_site * n_sites (the product in u64).
+ * Parameters: fmh_ibd_params { mode, min_sites, min_length, max_gap (0 = none), max_bp_per_site (0 = none), max_missing }.
+ * Outputs, exact integers.  Tables (fmh_ibd_out; any pointer may be NULL), each a device u64 [n][n], WRITTEN, not added into: both
+ *   triangles are filled and the diagonal is 0; over the pair's qualifying runs n_segments, sum_sites, sum_length, longest_length.
+ *   Segments (optional): fmh_ibd_segment { a, b, n_sites, n_missing, first_row, last_row }; a < b are list positions; rows are those of
+ *   the matrix relative to row_begin.  d_segments_or_null is a DEVICE buffer of segment_capacity elements (NULL: capacity 0);
+ *   *h_segment_count receives the exact number of qualifying runs of the call even when it exceeds the capacity, and the buffer then
+ *   holds min(count, capacity) distinct true segments in unspecified order.  fmh_ibd_sort_segments (host only) orders host segments by
+ *   (a, b, first_row).
+ * fmh_ibd_scan enqueues on `stream` and synchronises it.  K == 0 or n == 1 is FMH_OK with zero tables and count 0.
+ * Refusals, all before any launch, in this order.  FMH_ERR_INVALID: NULL matrix or params; n_samples == 0; a sample index out of range or
+ *   a list that is not strictly ascending; a row range past the matrix; a mode other than FMH_IBD1 / FMH_IBD2; positions that descend in
+ *   the range; every output NULL (no table, no segment buffer, no count); a segment buffer without a count pointer.
+ *   FMH_ERR_UNSUPPORTED, with a message: ploidy != 2; a matrix without a packed image (call fmh_matrix_pack first); a range of 2^32 - 1
+ *   rows or more; scratch (the sample-major bit image plus the block records) above FMH_IBD_BUDGET_BYTES (the message names the bytes
+ *   needed and the option); more than 2^31 work items.
+ * Options: FMH_IBD_ITEM_ROWS = the kept rows of a row block (rounded up to a multiple of 64; default: one block when the pair tiles alone
+ *   give every workgroup of the grid several items, otherwise as many equal blocks as reach that, fewer when the budget asks);
+ *   FMH_IBD_BUDGET_BYTES (default 4 GiB) bounds the scratch of a call.  Neither changes a result, nor do FMH_GRID_PER_CU and
+ *   FMH_GRID_BLOCKS.
+ * fmh_ibd_scan_host (host only, no device): the same parameters over h_dosage u8 [K][n] (0, 1, 2; 3 = not called) and h_x u32 [K]
+ *   (non-decreasing; NULL = k); the tables and segments are host arrays (fmh_ibd_out's pointers are then host pointers), rows of a
+ *   segment are kept rows k.  A serial loop per pair over the whole range.  Refusals (FMH_ERR_INVALID): NULL params; n == 0; NULL dosage
+ *   with K > 0; mode, descending x, outputs and segments as above; a dosage above 3.  FMH_ERR_UNSUPPORTED: 2^32 - 1 kept rows or more.
+ * Not built: error tolerance inside a segment, trimming MISS rows at run ends, a minimum count of informative sites, explicit pair lists
+ *   or pairs between two sample lists, genetic-map lengths, length bins on the device, sharding over devices, run_vcf wiring, u8 rows.
+ */
+#define FMH_IBD1 1
+#define FMH_IBD2 2
+typedef struct { uint32_t mode, min_sites, min_length, max_gap, max_bp_per_site, max_missing; } fmh_ibd_params;
+typedef struct { uint32_t a, b, n_sites, n_missing; uint64_t first_row, last_row; } fmh_ibd_segment;
+typedef struct {
+  unsigned long long *d_n_segments, *d_sum_sites, *d_sum_length, *d_longest_length;  /* each [n][n], written; any may be NULL */
+} fmh_ibd_out;
+int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                 size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count] */,
+                 const uint32_t* h_positions_or_null /* [variants] */, const fmh_ibd_params* params, const fmh_ibd_out* out_or_null,
+                 fmh_ibd_segment* d_segments_or_null, size_t segment_capacity, uint64_t* h_segment_count /* may be NULL without a buffer */,
+                 void* stream);
+int fmh_ibd_scan_host(const uint8_t* h_dosage /* [n_kept][n_samples]: 0, 1, 2, 3 = not called */, const uint32_t* h_x_or_null /* [n_kept] */,
+                      size_t n_kept, size_t n_samples, const fmh_ibd_params* params, const fmh_ibd_out* out_or_null /* host pointers */,
+                      fmh_ibd_segment* h_segments_or_null, size_t segment_capacity, uint64_t* h_segment_count);   /* host only, no device */
+int fmh_ibd_sort_segments(fmh_ibd_segment* h_segments, size_t count);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
