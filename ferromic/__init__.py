@@ -11,6 +11,7 @@ _abi.load()
 from ._core import (  # noqa: E402,F401
     AssociationScan,
     ChromosomePcaResult,
+    Clumps,
     DiversitySite,
     FStatEstimate,
     FStatistics,
@@ -39,6 +40,7 @@ from ._core import (  # noqa: E402,F401
     ehh_scan,
     f_statistics,
     garud_h,
+    genotype_ld,
     genotype_qc,
     global_pca,
     hudson_dxy,
@@ -50,6 +52,7 @@ from ._core import (  # noqa: E402,F401
     inversion_allele_frequency,
     joint_site_frequency_spectrum,
     kinship,
+    ld_clump,
     ld_prune,
     ld_r2,
     logistic_scan,

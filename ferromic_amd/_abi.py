@@ -168,6 +168,15 @@ class IbdOut(C.Structure):
     _fields_ = [("d_n_segments", C.c_void_p), ("d_sum_sites", C.c_void_p), ("d_sum_length", C.c_void_p), ("d_longest_length", C.c_void_p)]
 
 
+class GenoLdCounts(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("sum_a", C.c_uint32), ("sum_b", C.c_uint32), ("sq_a", C.c_uint32), ("sq_b", C.c_uint32),
+                ("cross", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ClumpParams(C.Structure):
+    _fields_ = [("p1", C.c_double), ("p2", C.c_double), ("r2", C.c_double), ("window", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -290,6 +299,11 @@ SYMBOLS = {
     "fmh_ibd_scan": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(IbdParams), _P(IbdOut), _vp, _sz, _P(_u64), _vp]),
     "fmh_ibd_scan_host": (_i, [_vp, _vp, _sz, _sz, _P(IbdParams), _P(IbdOut), _vp, _sz, _P(_u64)]),
     "fmh_ibd_sort_segments": (_i, [_vp, _sz]),
+    "fmh_clump": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _P(ClumpParams), _vp, _vp, _P(_u64), _vp]),
+    "fmh_geno_ld_pairs": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "fmh_geno_ld_r2": (_i, [_vp, _sz, _vp]),
+    "fmh_geno_ld_pairs_host": (_i, [_vp, _sz, _sz, _vp, _vp, _sz, _vp]),
+    "fmh_clump_host": (_i, [_vp, _vp, _vp, _sz, _sz, _P(ClumpParams), _vp, _vp, _P(_u64)]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

@@ -1332,6 +1332,122 @@ def ibd_sort_segments(segments: np.ndarray) -> np.ndarray:
     return out
 
 
+# ---- LD clumping: genotype r^2 around index sites --------------------------------------------------------------------------------------------
+CLUMP_NONE = 0xFFFFFFFF
+GENO_LD_COUNTS = ("n", "sum_a", "sum_b", "sq_a", "sq_b", "cross")
+
+
+def clump_params(p1=1e-4, p2=1e-2, r2=0.5, window=250_000) -> "_abi.ClumpParams":
+    """fmh_clump_params with PLINK's --clump defaults (window in position units)."""
+    p = _abi.ClumpParams()
+    p.p1, p.p2, p.r2, p.window, p.reserved = float(p1), float(p2), float(r2), int(window), 0
+    return p
+
+
+@dataclass
+class ClumpResult:
+    index_of: np.ndarray     # uint32 [rows]: the index's row (relative to row_begin), CLUMP_NONE for a row in no clump
+    r2: Optional[np.ndarray]  # float64 [rows]: r^2 with the index, NaN for a row in no clump
+    n_clumps: int
+
+
+def clump(m: DeviceMatrix, p_values, params, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None,
+          keep=None, positions=None, want_r2: bool = True, stream=None) -> ClumpResult:
+    """fmh_clump over rows [row_begin, row_begin + row_count) and the samples `samples` (ascending sample numbers; None = the first n_samples,
+    default all).  `p_values` float64 [row_count]; `positions` [variants] uint32 (indexed by matrix row) or None.  The outputs are pre-filled
+    with junk."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    p_values = np.ascontiguousarray(p_values, dtype=np.float64)
+    if p_values.size != rows:
+        raise ValueError("p_values has one entry per row of the range")
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        if positions.size != m.variants:
+            raise ValueError("positions has one entry per row of the matrix")
+    index_of = np.full(max(rows, 1), 0xA5A5A5A5, dtype=np.uint32)
+    r2 = np.full(max(rows, 1), 12345.678, dtype=np.float64) if want_r2 else None
+    count = C.c_uint64(0xA5A5A5A5)
+    _abi.check(_abi.load().fmh_clump(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), _ptr(p_values),
+                                     C.byref(params), _ptr(index_of), _ptr(r2), C.byref(count), stream))
+    return ClumpResult(index_of[:rows], None if r2 is None else r2[:rows], int(count.value))
+
+
+def clump_host(dosage, p_values, params, x=None, want_r2: bool = True) -> ClumpResult:
+    """fmh_clump_host (host only): the same rule over `dosage` uint8 [K][n] (0, 1, 2; 3 = not called), `x` uint32 [K] or None."""
+    dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
+    K, n = dosage.shape
+    p_values = np.ascontiguousarray(p_values, dtype=np.float64)
+    if p_values.size != K:
+        raise ValueError("p_values has one entry per row")
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.size != K:
+            raise ValueError("x has one entry per row")
+    index_of = np.full(max(K, 1), 0xA5A5A5A5, dtype=np.uint32)
+    r2 = np.full(max(K, 1), 12345.678, dtype=np.float64) if want_r2 else None
+    count = C.c_uint64(0xA5A5A5A5)
+    _abi.check(_abi.load().fmh_clump_host(_ptr(dosage) if dosage.size else None, _ptr(x), _ptr(p_values) if K else None, K, n, C.byref(params),
+                                          _ptr(index_of), _ptr(r2), C.byref(count)))
+    return ClumpResult(index_of[:K], None if r2 is None else r2[:K], int(count.value))
+
+
+def _count_table(records: np.ndarray) -> np.ndarray:
+    return records.reshape(-1, 8)[:, :6].astype(np.int64)
+
+
+def geno_ld_pairs(m: DeviceMatrix, rows_a, rows_b, samples=None, n_samples: Optional[int] = None, stream=None) -> np.ndarray:
+    """fmh_geno_ld_pairs: int64 [P][6] (GENO_LD_COUNTS) of the pairs of matrix rows; the device records are pre-filled with junk."""
+    rows_a = np.ascontiguousarray(rows_a, dtype=np.uint32)
+    rows_b = np.ascontiguousarray(rows_b, dtype=np.uint32)
+    if rows_a.shape != rows_b.shape or rows_a.ndim != 1:
+        raise ValueError("rows_a and rows_b are one-dimensional and of one length")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    P = rows_a.size
+    buf = DeviceBuffer.from_numpy(m.device, np.full(max(P, 1) * 8, 0xA5A5A5A5, dtype=np.uint32))
+    _abi.check(_abi.load().fmh_geno_ld_pairs(m._h, _ptr(samples), n, _ptr(rows_a) if P else None, _ptr(rows_b) if P else None, P, buf.ptr if P else None, stream))
+    records = buf.to_numpy(np.uint32, max(P, 1) * 8)[: P * 8]
+    if P and records.reshape(-1, 8)[:, 6:].any():
+        raise AssertionError("the reserved words of a record are not 0")
+    return _count_table(records)
+
+
+def geno_ld_pairs_host(dosage, rows_a, rows_b) -> np.ndarray:
+    """fmh_geno_ld_pairs_host (host only): int64 [P][6] of pairs of rows of `dosage` uint8 [K][n]."""
+    dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
+    K, n = dosage.shape
+    rows_a = np.ascontiguousarray(rows_a, dtype=np.uint32)
+    rows_b = np.ascontiguousarray(rows_b, dtype=np.uint32)
+    P = rows_a.size
+    records = np.full(max(P, 1) * 8, 0xA5A5A5A5, dtype=np.uint32)
+    _abi.check(_abi.load().fmh_geno_ld_pairs_host(_ptr(dosage) if dosage.size else None, K, n, _ptr(rows_a) if P else None, _ptr(rows_b) if P else None, P,
+                                                  _ptr(records) if P else None))
+    return _count_table(records[: P * 8])
+
+
+def geno_ld_r2(counts) -> np.ndarray:
+    """fmh_geno_ld_r2 (host only): float64 [P] of int [P][6] counts (GENO_LD_COUNTS) by the definition's one formula."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 6)
+    P = counts.shape[0]
+    records = np.zeros((max(P, 1), 8), dtype=np.uint32)
+    records[:P, :6] = counts
+    out = np.full(max(P, 1), 12345.678, dtype=np.float64)
+    _abi.check(_abi.load().fmh_geno_ld_r2(_ptr(records) if P else None, P, _ptr(out) if P else None))
+    return out[:P]
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

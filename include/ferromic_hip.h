@@ -1116,6 +1116,62 @@ int fmh_ibd_scan_host(const uint8_t* h_dosage /* [n_kept][n_samples]: 0, 1, 2, 3
                       fmh_ibd_segment* h_segments_or_null, size_t segment_capacity, uint64_t* h_segment_count);   /* host only, no device */
 int fmh_ibd_sort_segments(fmh_ibd_segment* h_segments, size_t count);   /* host only, no device */
 
+/* ---- LD clumping: genotype r^2 around index sites (an addition: the reference has none) ---------------------------------------------
+ * The step between an association scan and a polygenic score (PLINK --clump): sites are taken in order of ascending p; each one not yet
+ * claimed becomes an index site and claims every nearby site whose genotype r^2 with it reaches a threshold.  THE definition: the device
+ * (fmh_clump, fmh_geno_ld_pairs), the host twins and a plain Python loop agree on every integer and every bit of r^2.
+ * Matrix, samples, called, dosage: fmh_genotype_counts' / fmh_roh_scan's.  Ploidy 2, a packed image; sample s owns columns 2s and 2s + 1;
+ *   a genotype is called iff both entries are called and both alleles are <= 1; every plane is masked with the called plane (junk bits
+ *   under uncalled entries are legal); row_gap / row_hi are honoured.  n = n_samples; the dosage is g in {0, 1, 2}.
+ * Genotype LD of two rows a, b over the selected samples (fmh_geno_ld_counts, eight u32, the last two reserved and written 0):
+ *   n = samples called at both rows; sum_a = sum g_a, sum_b, sq_a = sum g_a^2, sq_b, cross = sum g_a g_b, each over those n samples.
+ *   In int64: cov = n cross - sum_a sum_b, va = n sq_a - sum_a^2, vb likewise.
+ *   r2 = ((double)cov * (double)cov) / ((double)va * (double)vb), built with -ffp-contract=off.  va == 0 || vb == 0 (this includes
+ *   n == 0) gives a quiet NaN.  The squared Pearson correlation of the two dosage vectors over the jointly called samples (PLINK --r2's
+ *   default statistic); every integer stays below 2^53 for rows of at most 600 000 columns.  a == b is allowed and gives 1.0 or NaN.
+ *   From the bit planes, with A the alt-allele bits of a row masked to its called genotypes and swap() exchanging the two bits of every
+ *   sample: cross = popc(A_a & A_b) + popc(swap(A_a) & A_b), sum g^2 = popc(A) + 2 popc(hom-alt).
+ * Clumping, parameters fmh_clump_params { p1, p2, r2, window }:
+ *   1. Kept rows and positions x are fmh_roh_scan's: the h_keep_or_null bytes; h_positions_or_null [variants] u32, indexed by matrix row
+ *      and non-decreasing over the range; NULL = x is the row number.
+ *   2. h_p is f64 [row_count].  A row is a PARTICIPANT iff it is kept, its p is not NaN and p <= p2; a participant is a CANDIDATE iff
+ *      p <= p1.
+ *   3. Candidates are visited by ascending (p, row), compared as f64.  A candidate that is already claimed is skipped.  Otherwise it
+ *      becomes an INDEX and owns itself; it then claims every participant j != i that is not yet owned (neither an index nor a member)
+ *      with |x(j) - x(i)| <= window and r2(i, j) >= r2.  NaN never qualifies.
+ *   4. A participant that no index claims stays unassigned.  There is no overlap option: a site belongs to the first index that reaches it.
+ * Outputs are host arrays (rule 3 runs on the host, as fmh_ld_prune's does): h_index_of u32 [row_count]: the index's row relative to
+ *   row_begin (an index names itself), UINT32_MAX for a row in no clump; h_r2_or_null f64 [row_count]: r2 of the row with its index by the
+ *   formula above (an index with itself), NaN where index_of is UINT32_MAX; *h_n_clumps_or_null: the number of clumps.
+ * fmh_clump enqueues on `stream` and synchronises it.  With no participant or no candidate it is FMH_OK with UINT32_MAX / NaN / 0 and no
+ *   launch.  fmh_geno_ld_pairs gives the counts of P arbitrary row pairs (matrix rows) into a device array; fmh_clump calls it once at the
+ *   end for the (index, member) pairs behind h_r2.
+ * Refused before any launch, in this order.  FMH_ERR_INVALID: a NULL matrix, params, h_p or h_index_of; n_samples == 0; a bad sample
+ *   list; a row range past the matrix; params that are NaN or do not satisfy 0 <= p1 <= p2 <= 1 and 0 <= r2 <= 1; a p of a kept row that
+ *   is neither NaN nor within [0, 1]; positions that descend in the range.  For the pairs call also: a NULL list or output with P > 0; a
+ *   row outside the matrix.  FMH_ERR_UNSUPPORTED, each with a message: ploidy != 2; no packed image; a range of 2^32 - 1 rows or more;
+ *   threshold words above the budgets (FMH_CLUMP_HOST_BYTES for all candidates' bit rows on the host, FMH_CLUMP_BUDGET_BYTES when one tile
+ *   row of candidates alone exceeds a launch's scratch; the message names the bytes needed and the option); more than 2^31 work items.
+ * Host only, no device: fmh_geno_ld_r2 (the formula alone, P count records), fmh_geno_ld_pairs_host (counts of P row pairs of h_dosage u8
+ *   [K][n]: 0, 1, 2; 3 = not called) and fmh_clump_host (the same rule over h_dosage, h_x u32 [K] or NULL = k, h_p f64 [K]; every given
+ *   row counts as kept and rows are 0 .. K - 1).
+ * Options (neither changes a result): FMH_CLUMP_BUDGET_BYTES (default 1 GiB), FMH_CLUMP_HOST_BYTES (default 8 GiB).
+ */
+typedef struct { uint32_t n, sum_a, sum_b, sq_a, sq_b, cross, reserved[2]; } fmh_geno_ld_counts;
+typedef struct { double p1, p2, r2; uint32_t window; uint32_t reserved; } fmh_clump_params;
+int fmh_clump(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+              size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count] */,
+              const uint32_t* h_positions_or_null /* [variants] */, const double* h_p /* [row_count] */, const fmh_clump_params* params,
+              uint32_t* h_index_of /* [row_count] */, double* h_r2_or_null /* [row_count] */, uint64_t* h_n_clumps_or_null, void* stream);
+int fmh_geno_ld_pairs(const fmh_matrix* m, const uint32_t* h_samples_or_null, size_t n_samples, const uint32_t* h_rows_a /* [P], matrix rows */,
+                      const uint32_t* h_rows_b /* [P] */, size_t P, fmh_geno_ld_counts* d_counts /* [P], device, written */, void* stream);
+int fmh_geno_ld_r2(const fmh_geno_ld_counts* h_counts, size_t P, double* h_r2);   /* host only, no device */
+int fmh_geno_ld_pairs_host(const uint8_t* h_dosage /* [K][n]: 0, 1, 2, 3 = not called */, size_t K, size_t n, const uint32_t* h_rows_a,
+                           const uint32_t* h_rows_b, size_t P, fmh_geno_ld_counts* h_counts);   /* host only, no device */
+int fmh_clump_host(const uint8_t* h_dosage /* [K][n] */, const uint32_t* h_x_or_null /* [K] */, const double* h_p /* [K] */, size_t K, size_t n,
+                   const fmh_clump_params* params, uint32_t* h_index_of /* [K] */, double* h_r2_or_null /* [K] */,
+                   uint64_t* h_n_clumps_or_null);   /* host only, no device */
+
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
  * A group is a 0/1 column mask with n >= 1 members (fmh_groups); members are ranked 0 .. n-1 by ascending column.  A window is a row range
