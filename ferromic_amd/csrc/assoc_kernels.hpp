@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "plane_rows.hpp"
+#include "plane_rows.hpp"  // kEvenBits
 
 namespace fmh {
 
@@ -39,7 +39,6 @@ constexpr uint32_t kAssocPassRows = 128;          // 4 waves x 2 tiles x 16 rows
 constexpr uint32_t kAssocGroupSamples = 256;      // samples of one staged B chunk: 64 bytes of a plane row
 constexpr uint32_t kAssocChunkVecs = 16 * 64;     // 16-byte vectors of one (group, value group) of B: [4 t][4 digits][64 lanes] = 16 KiB
 constexpr uint32_t kAssocMaxColumns = 64;
-constexpr uint32_t kAssocEven = 0x55555555u;
 
 typedef int assoc_v4i __attribute__((ext_vector_type(4)));
 
@@ -165,8 +164,8 @@ __global__ __launch_bounds__(kAssocThreads) void assoc_sums_kernel(const AssocAr
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
               const uint32_t b = assoc_word(w0[m], t), pc = assoc_word(wc[m], t), hi = assoc_word(wh[m], t);
-              const uint32_t called = pc & (pc >> 1) & ~(hi | (hi >> 1)) & kAssocEven;
-              const uint32_t dosage = ((b & kAssocEven) + ((b >> 1) & kAssocEven)) & (called * 3u);
+              const uint32_t called = pc & (pc >> 1) & ~(hi | (hi >> 1)) & kEvenBits;
+              const uint32_t dosage = ((b & kEvenBits) + ((b >> 1) & kEvenBits)) & (called * 3u);
               a_s[m] = assoc_operand(dosage);
               if constexpr (CALLED) a_c[m] = assoc_operand(called);
             }

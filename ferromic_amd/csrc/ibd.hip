@@ -1,8 +1,8 @@
 // ibd.hip — IBD segments: fmh_ibd_scan (per pair of diploid samples the qualifying runs of kept rows without a discordant genotype, exact
 // integers from the bit planes: a states kernel that builds a sample-major bit image, a pair kernel over (row block, 32 x 32 pair tile)
 // items that leaves one record per (block, pair), and a stitch kernel that joins the blocks and writes the [n][n] tables), its host twin
-// fmh_ibd_scan_host, and the host-only fmh_ibd_sort_segments.  Kernels in ibd_kernels.hpp, host arithmetic in ibd_host.hpp; definition in
-// include/ferromic_hip.h, scheme in DESIGN.md section 3.22.
+// fmh_ibd_scan_host, and the host-only fmh_ibd_sort_segments.  Kernels in ibd_kernels.hpp, host arithmetic in ibd_host.hpp, what it shares
+// with the runs of homozygosity in segment_*.hpp; definition in include/ferromic_hip.h, scheme in DESIGN.md section 3.22.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,7 +11,7 @@
 #include "abi_internal.hpp"
 #include "ibd_host.hpp"
 #include "ibd_kernels.hpp"
-#include "stat_call.hpp"
+#include "segment_call.hpp"
 
 using namespace fmh;
 using namespace fmhi;
@@ -23,13 +23,8 @@ const fmh_ibd_out kIbdNoTables{nullptr, nullptr, nullptr, nullptr};
 
 bool any_table(const fmh_ibd_out& o) { return o.d_n_segments || o.d_sum_sites || o.d_sum_length || o.d_longest_length; }
 
-// what the two entry points refuse alike, in the header's order, from the mode on
-int check_ibd_request(const fmh_ibd_params& p, const uint32_t* x, size_t x_count, const fmh_ibd_out& out, const void* segments, const uint64_t* count) {
+int check_ibd_params(const fmh_ibd_params& p) {
   if (const char* refused = ibd_check_params(p)) return fail(FMH_ERR_INVALID, "%s (mode %u)", refused, p.mode);
-  for (size_t k = 1; x && k < x_count; ++k)
-    if (x[k] < x[k - 1]) return fail(FMH_ERR_INVALID, "the positions descend at row entry %zu of the range", k);
-  if (!any_table(out) && !segments && !count) return fail(FMH_ERR_INVALID, "every output is NULL");
-  if (segments && !count) return fail(FMH_ERR_INVALID, "a segment buffer is given but h_segment_count is NULL");
   return FMH_OK;
 }
 
@@ -57,32 +52,20 @@ extern "C" int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_nu
                             const fmh_ibd_out* out_or_null, fmh_ibd_segment* d_segments_or_null, size_t segment_capacity, uint64_t* h_segment_count,
                             void* stream) {
   // ---- every refusal, before any launch ----
-  if (!m) return fail(FMH_ERR_INVALID, "NULL matrix");
-  if (!params) return fail(FMH_ERR_INVALID, "NULL params");
-  if (n_samples == 0) return fail(FMH_ERR_INVALID, "n_samples is 0");
-  FMH_TRY(check_samples(h_samples_or_null, n_samples, m->samples));
-  FMH_TRY(check_rows(row_begin, row_count, m->variants));
-  const fmh_ibd_params& P = *params;
   const fmh_ibd_out out = out_or_null ? *out_or_null : kIbdNoTables;
-  FMH_TRY(check_ibd_request(P, h_positions_or_null ? h_positions_or_null + row_begin : nullptr, row_count, out, d_segments_or_null, h_segment_count));
-  if (m->ploidy != 2) return fail(FMH_ERR_UNSUPPORTED, "IBD segments take diploid genotypes (ploidy 2), got ploidy %zu", m->ploidy);
-  FMH_TRY(check_packed(m, "IBD segments read"));
-  if (row_count >= 0xFFFFFFFFull) return fail(FMH_ERR_UNSUPPORTED, "a range of %zu rows: fewer than 2^32 - 1 are taken (split the rows)", row_count);
+  FMH_TRY(check_segment_scan(m, params, h_samples_or_null, n_samples, row_begin, row_count, h_positions_or_null, any_table(out), d_segments_or_null,
+                             h_segment_count, "IBD segments", [&] { return check_ibd_params(*params); }));
+  const fmh_ibd_params& P = *params;
 
-  // ---- the kept rows, their positions and breaks ----
+  // ---- the kept rows and their positions ----
   const size_t n = n_samples;
-  std::vector<uint32_t> rows, x;
-  rows.reserve(row_count);
-  for (size_t r = 0; r < row_count; ++r)
-    if (!h_keep_or_null || h_keep_or_null[r]) rows.push_back((uint32_t)r);
-  const size_t K = rows.size(), words = (K + 63) / 64;
-  x.resize(K);
-  for (size_t k = 0; k < K; ++k) x[k] = h_positions_or_null ? h_positions_or_null[row_begin + rows[k]] : rows[k];
+  SegmentFrame frame(h_keep_or_null, h_positions_or_null, row_begin, row_count, h_samples_or_null, n);
+  const size_t K = frame.kept.rows.size(), words = (K + 63) / 64;
   const bool segments = d_segments_or_null || h_segment_count;
   const size_t capacity = d_segments_or_null ? segment_capacity : 0;
 
   // ---- the scratch and the work items: refused before anything is enqueued ----
-  const bool called = m->pc || m->p1 || m->p2;
+  const bool called = SegmentFrame::has_flags(m);
   const size_t n_planes = called ? 3 : 2;
   const size_t tiles_1d = (n + kIbdTile - 1) / kIbdTile, spad = tiles_1d * kIbdTile;
   const size_t n_tiles = tiles_1d * (tiles_1d + 1) / 2, slots = n_tiles * kIbdTileSlots;
@@ -119,42 +102,26 @@ extern "C" int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_nu
   FMH_TRY(check_item_count(n_blocks * n_tiles, "FMH_IBD_ITEM_ROWS"));
   const size_t grid = std::min(full_grid, n_blocks * n_tiles);
 
-  std::vector<unsigned long long> brk(words, 0ull);
-  if (P.max_gap > 0)
-    for (size_t k = 1; k < K; ++k)
-      if (x[k] - x[k - 1] > P.max_gap) brk[k >> 6] |= 1ull << (k & 63);
-
-  const uint32_t last = h_samples_or_null ? h_samples_or_null[n - 1] : (uint32_t)(n - 1);
-  const uint32_t nvec = last / 64 + 1;  // 64 samples per 16 bytes of a row; within the row: sample `last` exists
-  const uint32_t groups = (nvec + 3) / 4;
-  std::vector<uint32_t> rank((size_t)groups * kIbdGroupSamples, kIbdNone);
-  for (size_t i = 0; i < n; ++i) rank[h_samples_or_null ? h_samples_or_null[i] : i] = (uint32_t)i;
-
-  uint32_t *d_rows = nullptr, *d_x = nullptr, *d_rank = nullptr, *rec32 = nullptr;
-  unsigned long long *d_brk = nullptr, *rec64 = nullptr, *d_counter = nullptr, *d_t = nullptr;
-  uint8_t* d_flags = nullptr;
-  FMH_TRY(call.upload(rows.data(), K, &d_rows));
-  FMH_TRY(call.upload(x.data(), K, &d_x));
-  FMH_TRY(call.upload(brk.data(), words, &d_brk));
-  FMH_TRY(call.upload(rank.data(), rank.size(), &d_rank));
+  uint32_t* rec32 = nullptr;
+  unsigned long long *rec64 = nullptr, *d_t = nullptr;
+  const std::vector<unsigned long long> brk = break_bitmap(frame.kept.x, P.max_gap, 0, words);  // break(k) at bit k; read until the call ends
+  FMH_TRY(frame.upload(call, m, brk, segments));
   FMH_TRY(call.scratch.get(&d_t, n_planes * words * spad));
-  FMH_TRY(call.scratch.get(&rec32, n_blocks * kIbdRec32 * slots));
-  FMH_TRY(call.scratch.get(&rec64, n_blocks * kIbdRec64 * slots));
-  if (segments) FMH_TRY(call.zeroed(1, &d_counter));
-  if (called) FMH_TRY(call.scratch.get(&d_flags, K));
+  FMH_TRY(call.scratch.get(&rec32, n_blocks * IbdRec::n32 * slots));
+  FMH_TRY(call.scratch.get(&rec64, n_blocks * kSegRec64 * slots));
 
   IbdStateArgs s{};
   set_plane_rows(s, m);
-  s.nvec = nvec;
-  s.groups = groups;
+  s.nvec = frame.nvec;
+  s.groups = frame.groups;
   s.row_begin = row_begin;
-  s.rows = d_rows;
-  s.flags = d_flags;
-  s.rank = d_rank;
+  s.rows = frame.d_rows;
+  s.flags = frame.d_flags;
+  s.rank = frame.d_rank;
   s.K = (uint32_t)K;
   s.words = (uint32_t)words;
   s.n_planes = (uint32_t)n_planes;
-  s.n_items = (uint64_t)words * groups;
+  s.n_items = (uint64_t)words * frame.groups;
   s.spad = spad;
   s.T = d_t;
 
@@ -162,9 +129,9 @@ extern "C" int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_nu
   a.T = d_t;
   a.spad = spad;
   a.words = (uint32_t)words;
-  a.rows = d_rows;
-  a.x = d_x;
-  a.brk = d_brk;
+  a.rows = frame.d_rows;
+  a.x = frame.d_x;
+  a.brk = frame.d_brk;
   a.n = (uint32_t)n;
   a.K = (uint32_t)K;
   a.item_rows = (uint32_t)item_rows;
@@ -176,17 +143,12 @@ extern "C" int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_nu
   a.rec64 = rec64;
   a.segments = d_segments_or_null;
   a.capacity = capacity;
-  a.counter = d_counter;
+  a.counter = frame.d_counter;
   a.out = out;
 
   FMH_TRY(call.start());
   HIP_TRY(hipMemsetAsync(d_t, 0, t_bytes, st));  // the padding samples' words; the states kernel writes the selected samples'
-  if (called) {
-    PlaneRows planes{};
-    set_plane_rows(planes, m);
-    hipLaunchKernelGGL(ibd_flags_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, planes, row_begin, d_rows, (uint32_t)K, d_flags);
-    HIP_TRY(hipGetLastError());
-  }
+  FMH_TRY(frame.launch_flags(call, m, row_begin));
   {
     size_t state_grid = 0;
     FMH_TRY(persistent_grid(reinterpret_cast<const void*>(ibd_states_kernel), kIbdThreads, 0, (size_t)std::min<uint64_t>(s.n_items, (uint64_t)1 << 31),
@@ -197,12 +159,7 @@ extern "C" int fmh_ibd_scan(const fmh_matrix* m, const uint32_t* h_samples_or_nu
   FMH_TRY(launch_pair_kernel(P.mode, called, a, grid, st));
   hipLaunchKernelGGL(ibd_stitch_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
-  FMH_TRY(call.stop());
-  unsigned long long count = 0;
-  if (segments) HIP_TRY(hipMemcpyAsync(&count, d_counter, sizeof count, hipMemcpyDeviceToHost, st));
-  FMH_TRY(call.finish());
-  if (h_segment_count) *h_segment_count = count;
-  return FMH_OK;
+  return frame.finish(call, h_segment_count);
 }
 
 // ---- host only (no device) -------------------------------------------------------------------------------------------------------------------
@@ -213,7 +170,8 @@ extern "C" int fmh_ibd_scan_host(const uint8_t* h_dosage, const uint32_t* h_x_or
   if (n_samples == 0) return fail(FMH_ERR_INVALID, "n_samples is 0");
   if (n_kept != 0 && !h_dosage) return fail(FMH_ERR_INVALID, "NULL dosage");
   const fmh_ibd_out out = out_or_null ? *out_or_null : kIbdNoTables;
-  FMH_TRY(check_ibd_request(*params, h_x_or_null, n_kept, out, h_segments_or_null, h_segment_count));
+  FMH_TRY(check_ibd_params(*params));
+  FMH_TRY(check_segment_request(h_x_or_null, n_kept, any_table(out), h_segments_or_null, h_segment_count));
   if (n_kept >= 0xFFFFFFFFull) return fail(FMH_ERR_UNSUPPORTED, "%zu kept rows: fewer than 2^32 - 1 are taken", n_kept);
   for (size_t i = 0; i < n_kept * n_samples; ++i)
     if (h_dosage[i] > 3) return fail(FMH_ERR_INVALID, "dosage %u (kept row %zu, sample %zu) is not 0, 1, 2 or 3", h_dosage[i], i / n_samples, i % n_samples);

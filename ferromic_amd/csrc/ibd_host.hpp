@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "../../include/ferromic_hip.h"
+#include "segment_host.hpp"
 
 namespace fmh_host {
 
@@ -38,11 +39,6 @@ inline bool ibd_segment_less(const fmh_ibd_segment& s, const fmh_ibd_segment& t)
   return s.first_row < t.first_row;
 }
 
-inline bool ibd_qualifies(const fmh_ibd_params& p, uint64_t n_sites, uint64_t length, uint64_t n_missing) {
-  return n_sites >= p.min_sites && length >= p.min_length && n_missing <= p.max_missing &&
-         (p.max_bp_per_site == 0 || length <= (uint64_t)p.max_bp_per_site * n_sites);
-}
-
 // 0 CONC, 1 MISS, 2 DISC of two dosages (3 = not called)
 inline int ibd_state(uint32_t mode, uint8_t di, uint8_t dj) {
   if (di > 2 || dj > 2) return 1;
@@ -66,7 +62,7 @@ inline void ibd_scan_host(const uint8_t* dosage, const uint32_t* x_or_null, size
       size_t first = 0;
       auto close = [&](size_t last) {
         const uint64_t sites = last - first + 1, length = (uint64_t)x(last) - x(first) + 1;
-        if (ibd_qualifies(p, sites, length, n_missing)) {
+        if (run_qualifies(p, sites, length, n_missing)) {
           ++n_segments; sum_sites += sites; sum_length += length; longest = std::max(longest, length);
           if (count < capacity && segments) segments[count] = fmh_ibd_segment{(uint32_t)i, (uint32_t)j, (uint32_t)sites, (uint32_t)n_missing, first, last};
           ++count;

@@ -2,7 +2,8 @@
 // cohort with planted sharing, held in exact-size heap blocks, so that a read or write one element past the dosage table, the positions, a
 // table or the segment buffer is an ASan report.  The cohort comes from a splitmix64 stream that tests/test_ibd_cpu.py restates, the scan
 // runs twice (once to count, once into a buffer of exactly that many segments) and the program prints an order-free checksum of the tables
-// and segments, which the test compares with the oracle's (tests/ibd_ref.py: checksum).
+// and segments, which the test compares with the oracle's (tests/ibd_ref.py: checksum).  Before that, silently, the kept rows and the
+// break bitmap the device entry point builds (segment_host_check.hpp): break(k) at bit k of ceil(K / 64) words, and at bit k + 64.
 // Built by `make asan` with -fsanitize=address,undefined -fno-sanitize-recover=all.
 //   ibd_host_check.asan seed K n mode min_sites min_length max_gap max_bp_per_site max_missing
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "ibd_host.hpp"
+#include "segment_host_check.hpp"
 
 static uint64_t g_state = 0;
 static uint64_t rnd() {  // splitmix64
@@ -22,6 +24,8 @@ static uint64_t rnd() {  // splitmix64
 
 int main(int argc, char** argv) {
   if (argc != 10) { fprintf(stderr, "usage: %s seed K n mode min_sites min_length max_gap max_bp_per_site max_missing\n", argv[0]); return 2; }
+  for (size_t offset : {(size_t)0, (size_t)64})
+    if (!fmh_host::check_kept_rows_and_breaks(offset, [&](size_t K) { return (K + offset + 63) / 64; })) return 1;
   g_state = strtoull(argv[1], nullptr, 10);
   const size_t K = strtoull(argv[2], nullptr, 10), n = strtoull(argv[3], nullptr, 10);
   fmh_ibd_params p{};

@@ -5,10 +5,10 @@
 // States (ibd_states_kernel).  For the selected samples and the kept rows it builds the sample-major bit image T[plane][w][sample]: u64
 // words, the sample's LIST POSITION fastest and padded to the pair tile, word w = kept rows 64 w .. 64 w + 63; planes R (called, dosage 0),
 // A (called, dosage 2) and - for a matrix with a called or an upper plane - C (called).  Bits of rows >= K are zero in every plane, and so
-// are the words of the padding samples (the host zeroes T first).  The fetch is the ROH scan's, written out again (roh_kernels.hpp stays
-// as it is): an item = (word w, group of 256 matrix samples); through the kept-row list, 16 bytes per thread and plane (thread = row of the
-// word x 16-byte part of the group's 64 bytes), 2-bit fields as assoc_kernels.hpp makes them (upper planes, row_gap / row_hi honoured
-// through the per-kept-row flags of ibd_flags_kernel), parked in LDS; a lane then gathers ITS sample's bit of the 64 rows.
+// are the words of the padding samples (the host zeroes T first).  The fetch is the ROH scan's (segment_kernels.hpp: plane_fetch): an
+// item = (word w, group of 256 matrix samples); through the kept-row list, 16 bytes per thread and plane (thread = row of the word x
+// 16-byte part of the group's 64 bytes; upper planes, row_gap / row_hi honoured through the per-kept-row flags of plane_flags_kernel),
+// 2-bit fields parked in LDS; a lane then gathers ITS sample's bit of the 64 rows.
 // Pairs (ibd_pair_kernel<MODE, CALLED>).  An item on the persistent grid = (block of item_rows kept rows [b0, b1), b0 a multiple of 64;
 // tile pair ti <= tj of 32 x 32 samples).  256 threads; thread (ty, tx) owns the 2 x 2 pairs i = 32 ti + 2 ty + {0, 1},
 // j = 32 tj + 2 tx + {0, 1}: every loaded sample word serves two pairs and every per-pair array is indexed by constants after unrolling.
@@ -16,21 +16,20 @@
 // current one.  Per pair and word: D (discordant rows) = (Ri & Aj) | (Ai & Rj) for IBD1, Ci & Cj & ((Ri ^ Rj) | (Ai ^ Aj)) for IBD2;
 // M (missing rows) = valid & ~(Ci & Cj); B (break bits) is the same for all pairs.  A word with D | B == 0 extends (or opens) the pair's
 // run and adds popcount(M); otherwise the events are walked lowest first.  Runs strictly inside the block are judged, tallied and (when
-// asked for) appended by the lane itself; per (block, pair) the item leaves ROH's fixed record: the partial run that touches the block's
-// first row (head), the one that touches its last row (tail; tail_first == b0 = the whole block is one run, no head then) and the interior
-// tallies.  A record field is [block][field][slot], slot = 1024 tile + 256 sub-pair + thread: a wave's stores are contiguous.
-// Stitch (ibd_stitch_kernel).  One thread per slot walks the blocks in order, joins the tail of block r to the head of block r + 1 iff
-// both exist and there is no break at the boundary, judges the joined runs, adds the interior tallies and writes BOTH triangles of the
+// asked for) appended by the lane itself; per (block, pair) the item leaves the record of segment_kernels.hpp (SegRec<1>: head, tail and
+// the interior tallies).  A record field is [block][field][slot], slot = 1024 tile + 256 sub-pair + thread: a wave's stores are contiguous.
+// Stitch (ibd_stitch_kernel).  One thread per slot joins the blocks by the shared rule (seg_stitch), judges the joined runs, adds the
+// interior tallies and writes BOTH triangles of the
 // tables (the threads of the slots with i == j write the diagonal's zeros): one writer per entry, nothing is zeroed, no atomics touch the
-// tables.  Segments are appended with a vector atomicAdd on a device counter, stored below the capacity.
+// tables.  Segments are appended with a vector atomicAdd on a device counter, stored below the capacity (seg_append).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ferromic_hip.h"
-#include "assoc_kernels.hpp"  // kAssocEven
 #include "plane_rows.hpp"
+#include "segment_kernels.hpp"
 
 namespace fmh {
 
@@ -38,11 +37,8 @@ constexpr uint32_t kIbdThreads = 256;
 constexpr uint32_t kIbdTile = 32;            // samples of a pair tile's side
 constexpr uint32_t kIbdTileSlots = 1024;     // pairs of a tile pair: 256 threads x (2 x 2)
 constexpr uint32_t kIbdBatch = 8;            // words of a sample staged in LDS at a time
-constexpr uint32_t kIbdGroupSamples = 256;   // matrix samples of a states item: 64 bytes of a plane row
-constexpr uint32_t kIbdNone = 0xFFFFFFFFu;
-constexpr uint32_t kIbdRec32 = 6;            // head_last, head_miss, tail_first, tail_miss, runs, sites
-constexpr uint32_t kIbdRec64 = 2;            // length, longest
-constexpr size_t kIbdRecBytes = kIbdRec32 * sizeof(uint32_t) + kIbdRec64 * sizeof(unsigned long long);  // per (block, slot)
+using IbdRec = SegRec<1>;                    // a run carries (miss)
+constexpr size_t kIbdRecBytes = IbdRec::n32 * sizeof(uint32_t) + kSegRec64 * sizeof(unsigned long long);  // per (block, slot)
 
 struct IbdStateArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   uint32_t nvec;    // 16-byte vectors of a row through the last selected sample (<= plane_pitch / 16)
@@ -50,7 +46,7 @@ struct IbdStateArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   size_t row_begin;
   const uint32_t* rows;   // [K] kept rows, relative to row_begin
   const uint8_t* flags;   // [K] bit 0: the called plane of the row is read, bit 1: the upper planes are; null = neither exists
-  const uint32_t* rank;   // [groups * 256] list position of a matrix sample, kIbdNone where it is not selected
+  const uint32_t* rank;   // [groups * 256] list position of a matrix sample, kSegNone where it is not selected
   uint32_t K, words;      // words = ceil(K / 64)
   uint32_t n_planes;      // 2 (R, A) or 3 (R, A, C)
   uint64_t n_items;       // words * groups
@@ -69,22 +65,16 @@ struct IbdArgs {
   uint32_t n_tiles;                // tile pairs ti <= tj: t (t + 1) / 2 for t = spad / 32
   uint32_t n_items;                // n_blocks * n_tiles
   fmh_ibd_params P;
-  uint32_t* rec32;                 // [n_blocks][kIbdRec32][n_tiles * 1024]
-  unsigned long long* rec64;       // [n_blocks][kIbdRec64][n_tiles * 1024]
+  uint32_t* rec32;                 // [n_blocks][IbdRec::n32][n_tiles * 1024]
+  unsigned long long* rec64;       // [n_blocks][kSegRec64][n_tiles * 1024]
   fmh_ibd_segment* segments;       // device, `capacity` elements, or null
   unsigned long long capacity;
   unsigned long long* counter;     // null = segments are neither counted nor stored
   fmh_ibd_out out;
 };
 
-__device__ __forceinline__ bool ibd_qualifies(const fmh_ibd_params& P, uint64_t sites, uint64_t length, uint64_t n_missing) {
-  return sites >= P.min_sites && length >= P.min_length && n_missing <= P.max_missing &&
-         (P.max_bp_per_site == 0 || length <= (uint64_t)P.max_bp_per_site * sites);
-}
 __device__ __forceinline__ void ibd_append(const IbdArgs& A, uint32_t a, uint32_t b, uint32_t first, uint32_t last, uint32_t n_missing) {
-  if (!A.counter) return;
-  const unsigned long long at = atomicAdd(A.counter, 1ull);
-  if (A.segments && at < A.capacity) A.segments[at] = fmh_ibd_segment{a, b, last - first + 1, n_missing, A.rows[first], A.rows[last]};
+  seg_append(A, [&] { return fmh_ibd_segment{a, b, last - first + 1, n_missing, A.rows[first], A.rows[last]}; });
 }
 // tile pair t = tj (tj + 1) / 2 + ti, ti <= tj
 __device__ __forceinline__ void ibd_tile_of(uint32_t t, uint32_t& ti, uint32_t& tj) {
@@ -93,23 +83,6 @@ __device__ __forceinline__ void ibd_tile_of(uint32_t t, uint32_t& ti, uint32_t& 
   while ((c + 1) * (c + 2) / 2 <= t) ++c;
   tj = (uint32_t)c;
   ti = t - (uint32_t)(c * (c + 1) / 2);
-}
-
-// per kept row: which planes the states kernel has to read of it (the matrix's per-row tables are skip hints; without a table the plane is read)
-static __global__ __launch_bounds__(256) void ibd_flags_kernel(const PlaneRows R, size_t row_begin, const uint32_t* __restrict__ rows, uint32_t K,
-                                                               uint8_t* __restrict__ flags) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  const size_t row = row_begin + rows[k];
-  const uint32_t gap = R.pc ? (R.row_gap ? (R.row_gap[row] != 0) : 1u) : 0u;
-  const uint32_t high = (R.p1 || R.p2) ? (R.row_hi ? (R.row_hi[row] != 0) : 1u) : 0u;
-  flags[k] = (uint8_t)(gap | (high << 1));
-}
-
-__device__ __forceinline__ uint4 ibd_load(const uint8_t* plane, size_t off, bool on, uint32_t fill) {
-  uint4 v = make_uint4(fill, fill, fill, fill);
-  if (on) v = *reinterpret_cast<const uint4*>(plane + off);
-  return v;
 }
 
 // Launched with kIbdThreads threads; static LDS: 3 x 4 KiB of fields.
@@ -133,26 +106,21 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_states_kernel(const Ib
     const bool inside = vec < A.nvec;  // a vector past the covered samples is zero
     const bool ok = inside && k < A.K;
     const size_t off = (A.row_begin + row) * A.plane_pitch + (size_t)(inside ? vec : 0) * 16;
-    const uint4 w0 = ibd_load(A.p0, off, ok, 0u);
-    const uint4 wc = ibd_load(A.pc, off, ok && (fl & 1u), ok ? ~0u : 0u);
-    const uint4 w1 = ibd_load(A.p1, off, ok && (fl & 2u) && A.p1, 0u);
-    const uint4 w2 = ibd_load(A.p2, off, ok && (fl & 2u) && A.p2, 0u);
-    const uint32_t b[4] = {w0.x, w0.y, w0.z, w0.w}, pc[4] = {wc.x, wc.y, wc.z, wc.w};
-    const uint32_t hi[4] = {w1.x | w2.x, w1.y | w2.y, w1.z | w2.z, w1.w | w2.w};
+    const PlaneFields f(plane_fetch(A, off, ok, fl));
     uint32_t cal[4], ref[4], alt[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      cal[q] = pc[q] & (pc[q] >> 1) & ~(hi[q] | (hi[q] >> 1)) & kAssocEven;
-      ref[q] = cal[q] & ~(b[q] | (b[q] >> 1));
-      alt[q] = cal[q] & b[q] & (b[q] >> 1);
+      cal[q] = f.called(q);
+      ref[q] = cal[q] & ~(f.b[q] | (f.b[q] >> 1));
+      alt[q] = cal[q] & f.b[q] & (f.b[q] >> 1);
     }
     __syncthreads();  // every lane has gathered the item before this one
     s_ref4[tid] = make_uint4(ref[0], ref[1], ref[2], ref[3]);  // tid = srow * 4 + spart
     s_alt4[tid] = make_uint4(alt[0], alt[1], alt[2], alt[3]);
     s_cal4[tid] = make_uint4(cal[0], cal[1], cal[2], cal[3]);
     __syncthreads();
-    const uint32_t rank = A.rank[(size_t)sg * kIbdGroupSamples + tid];
-    if (rank == kIbdNone) continue;
+    const uint32_t rank = A.rank[(size_t)sg * kSegGroupSamples + tid];
+    if (rank == kSegNone) continue;
     uint64_t rm = 0, am = 0, cm = 0;
 #pragma unroll
     for (uint32_t i = 0; i < 64; ++i) {
@@ -207,7 +175,7 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_pair_kernel(const IbdA
     uint64_t length_sum[4], longest[4];
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
-      first[q] = head_last[q] = kIbdNone;
+      first[q] = head_last[q] = kSegNone;
       miss[q] = head_miss[q] = runs[q] = sites[q] = 0;
       length_sum[q] = longest[q] = 0;
     }
@@ -246,7 +214,7 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_pair_kernel(const IbdA
           // a run [f, last] has ended: the block's head goes to the stitch, an interior run is judged here
           auto close = [&](uint32_t last) {
             const uint32_t f = first[q];
-            first[q] = kIbdNone;
+            first[q] = kSegNone;
             if (f == b0) {
               head_last[q] = last; head_miss[q] = miss[q];
               return;
@@ -254,13 +222,13 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_pair_kernel(const IbdA
             const uint32_t n_sites = last - f + 1;
             if (n_sites < A.P.min_sites || miss[q] > A.P.max_missing) return;  // before the positions are fetched
             const uint64_t length = (uint64_t)A.x[last] - A.x[f] + 1;
-            if (!ibd_qualifies(A.P, n_sites, length, miss[q])) return;
+            if (!run_qualifies(A.P, n_sites, length, miss[q])) return;
             ++runs[q]; sites[q] += n_sites; length_sum[q] += length; longest[q] = length > longest[q] ? length : longest[q];
             ibd_append(A, i0 + qi, j0 + qj, f, last, miss[q]);
           };
           uint64_t events = D | B;  // rows >= K hold neither a D nor a B bit
           if (events == 0) {
-            if (first[q] == kIbdNone) { first[q] = base; miss[q] = 0; }
+            if (first[q] == kSegNone) { first[q] = base; miss[q] = 0; }
             miss[q] += (uint32_t)__popcll(M);
             continue;
           }
@@ -268,8 +236,8 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_pair_kernel(const IbdA
           do {
             const uint32_t e = (uint32_t)__builtin_ctzll(events);
             events &= events - 1;
-            if (e > pos && first[q] == kIbdNone) { first[q] = base + pos; miss[q] = 0; }
-            if (first[q] != kIbdNone) {
+            if (e > pos && first[q] == kSegNone) { first[q] = base + pos; miss[q] = 0; }
+            if (first[q] != kSegNone) {
               miss[q] += (uint32_t)__popcll(M & ((1ull << e) - 1ull) & ~((1ull << pos) - 1ull));
               close(base + e - 1);
             }
@@ -283,11 +251,11 @@ static __global__ __launch_bounds__(kIbdThreads) void ibd_pair_kernel(const IbdA
     for (uint32_t q = 0; q < 4; ++q) {
       if (!active[q]) continue;
       const size_t slot = (size_t)tp * kIbdTileSlots + q * kIbdThreads + tid;
-      uint32_t* r32 = A.rec32 + (size_t)rb * kIbdRec32 * slots + slot;
-      unsigned long long* r64 = A.rec64 + (size_t)rb * kIbdRec64 * slots + slot;
-      r32[0 * slots] = head_last[q]; r32[1 * slots] = head_miss[q];
-      r32[2 * slots] = first[q]; r32[3 * slots] = miss[q];
-      r32[4 * slots] = runs[q]; r32[5 * slots] = sites[q];
+      uint32_t* r32 = A.rec32 + (size_t)rb * IbdRec::n32 * slots + slot;
+      unsigned long long* r64 = A.rec64 + (size_t)rb * kSegRec64 * slots + slot;
+      r32[IbdRec::head_last * slots] = head_last[q]; r32[IbdRec::head_c * slots] = head_miss[q];
+      r32[IbdRec::tail_first * slots] = first[q]; r32[IbdRec::tail_c * slots] = miss[q];
+      r32[IbdRec::runs * slots] = runs[q]; r32[IbdRec::sites * slots] = sites[q];
       r64[0 * slots] = length_sum[q]; r64[1 * slots] = longest[q];
     }
   }
@@ -310,43 +278,19 @@ static __global__ __launch_bounds__(256) void ibd_stitch_kernel(const IbdArgs A)
     if (A.out.d_longest_length) A.out.d_longest_length[i * n + i] = 0;
   }
   if (!(i < j && j < n)) return;
-  const uint32_t K = A.K;
   uint64_t runs = 0, sites = 0, length_sum = 0, longest = 0;
-  auto judge = [&](uint32_t first, uint32_t last, uint32_t n_miss) {
+  auto judge = [&](uint32_t first, uint32_t last, const uint32_t (&c)[1]) {  // c = (miss)
     const uint64_t n_sites = last - first + 1, length = (uint64_t)A.x[last] - A.x[first] + 1;
-    if (!ibd_qualifies(A.P, n_sites, length, n_miss)) return;
+    if (!run_qualifies(A.P, n_sites, length, c[0])) return;
     ++runs; sites += n_sites; length_sum += length; longest = length > longest ? length : longest;
-    ibd_append(A, i, j, first, last, n_miss);
+    ibd_append(A, i, j, first, last, c[0]);
   };
-  bool carry = false;  // a run that touches the last row of the block before
-  uint32_t c_first = 0, c_miss = 0;
-  for (uint32_t rb = 0; rb < A.n_blocks; ++rb) {
-    const uint32_t b0 = rb * A.item_rows;
-    const uint32_t* r32 = A.rec32 + (size_t)rb * kIbdRec32 * slots + slot;
-    const unsigned long long* r64 = A.rec64 + (size_t)rb * kIbdRec64 * slots + slot;
-    const uint32_t head_last = r32[0], tail_first = r32[2 * slots];
-    const bool joined = carry && !((A.brk[b0 >> 6] >> (b0 & 63u)) & 1ull);
-    if (tail_first == b0) {  // the whole block is one run
-      if (joined) c_miss += r32[3 * slots];
-      else {
-        if (carry) judge(c_first, b0 - 1, c_miss);
-        carry = true; c_first = b0; c_miss = r32[3 * slots];
-      }
-      continue;  // no interior run
-    }
-    if (head_last != kIbdNone) {
-      if (joined) judge(c_first, head_last, c_miss + r32[1 * slots]);
-      else {
-        if (carry) judge(c_first, b0 - 1, c_miss);
-        judge(b0, head_last, r32[1 * slots]);
-      }
-    } else if (carry) judge(c_first, b0 - 1, c_miss);
-    carry = false;
-    runs += r32[4 * slots]; sites += r32[5 * slots]; length_sum += r64[0];
+  auto interior = [&](uint32_t rb, const uint32_t* r32) {
+    const unsigned long long* r64 = A.rec64 + (size_t)rb * kSegRec64 * slots + slot;
+    runs += r32[IbdRec::runs * slots]; sites += r32[IbdRec::sites * slots]; length_sum += r64[0];
     longest = r64[1 * slots] > longest ? r64[1 * slots] : longest;
-    if (tail_first != kIbdNone) { carry = true; c_first = tail_first; c_miss = r32[3 * slots]; }
-  }
-  if (carry) judge(c_first, K - 1, c_miss);
+  };
+  seg_stitch<1>(A.rec32 + slot, slots, A.n_blocks, A.item_rows, A.K, A.brk, 0, judge, interior);
   const size_t ij = (size_t)i * n + j, ji = (size_t)j * n + i;
   if (A.out.d_n_segments) A.out.d_n_segments[ij] = A.out.d_n_segments[ji] = runs;
   if (A.out.d_sum_sites) A.out.d_sum_sites[ij] = A.out.d_sum_sites[ji] = sites;

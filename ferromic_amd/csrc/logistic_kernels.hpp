@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kAssocThreads) void assoc_homalt_kernel(const Assoc
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
               const uint32_t b = assoc_word(w0[m], t), pc = assoc_word(wc[m], t), hi = assoc_word(wh[m], t);
-              const uint32_t called = pc & (pc >> 1) & ~(hi | (hi >> 1)) & kAssocEven;
+              const uint32_t called = pc & (pc >> 1) & ~(hi | (hi >> 1)) & kEvenBits;
               a[m] = assoc_operand(b & (b >> 1) & called);  // both alleles 1, the genotype called: 0 or 1 per 2-bit field
             }
 #pragma unroll

@@ -1,5 +1,5 @@
 // pymodule_clump.inc — ferromic.ld_clump, Population.ld_clump, ferromic.genotype_ld and the Clumps result (included inside
-// pymodule_stats.inc's namespace, after pymodule_rows.inc whose rows, sample and sites rules it uses).  An addition to the reference's
+// pymodule_stats.inc's namespace, after pymodule_rows.inc whose rows, sample and sites rules it uses, and pymodule_segments.inc for the positions in play).  An addition to the reference's
 // surface: it has no clumping; the definition is include/ferromic_hip.h's (fmh_clump, fmh_geno_ld_pairs, fmh_geno_ld_r2).  Every assignment
 // and every r^2 comes from the library; the GIL is released around the C calls.  Positions go to the library relative to the first row in
 // play.  A request without a participant or without a candidate, and a genotype_ld of no pair, is answered without a device.
@@ -69,11 +69,7 @@ Clumps clump_over_rows(const RowsInPlay& in_play, vector<uint32_t> samples, cons
   out.r2.assign(rc, std::numeric_limits<double>::quiet_NaN());
   if (rc == 0) return out;
   // positions relative to the first row in play and the p values, checked before any device use
-  const vector<int64_t>& pos = out.positions;
-  for (size_t r = 1; r < rc; ++r)
-    if (pos[r] < pos[r - 1]) value_error("the positions descend at variant " + std::to_string(r) + ": clumping needs them in order");
-  if ((uint64_t)(pos[rc - 1] - pos[0]) > 0xFFFFFFFFull)
-    value_error("the positions span " + std::to_string(pos[rc - 1] - pos[0]) + ", more than 2^32 - 1: clump one chromosome (or a region of it) at a time");
+  check_positions_in_play(out.positions, "clumping needs", "clump");
   size_t participants = 0, candidates = 0;
   for (size_t r = 0; r < rc; ++r) {
     if (masked && !keep[r]) continue;
@@ -88,8 +84,7 @@ Clumps clump_over_rows(const RowsInPlay& in_play, vector<uint32_t> samples, cons
   const shared_ptr<DevMatrix>& dm = rows.dm;
   const size_t r0 = rows.r0;
   if (!dm || rows.rc < rc) throw std::runtime_error("the resident matrix holds fewer rows than are in play");
-  vector<uint32_t> device_x(dm->variants, 0);  // [variants] of the matrix: only the rows of the range are read
-  for (size_t r = 0; r < rc; ++r) device_x[r0 + r] = (uint32_t)(pos[r] - pos[0]);
+  const vector<uint32_t> device_x = device_positions(out.positions, dm->variants, r0);
   vector<uint32_t> index_of(rc);
   uint64_t n_clumps = 0;
   int status;

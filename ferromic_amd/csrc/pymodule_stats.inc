@@ -918,6 +918,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_assoc.inc"
 #include "pymodule_logistic.inc"
 #include "pymodule_score.inc"
+#include "pymodule_segments.inc"
 #include "pymodule_roh.inc"
 #include "pymodule_ibd.inc"
 #include "pymodule_clump.inc"

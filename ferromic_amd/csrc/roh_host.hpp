@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ferromic_hip.h"
+#include "segment_host.hpp"
 
 namespace fmh_host {
 
@@ -24,6 +25,11 @@ inline size_t roh_item_rows(long long option) {
   const size_t rows = option <= 0 ? kRohDefaultItemRows : std::min<size_t>((size_t)option, (size_t)1 << 30);
   return (rows + 63) / 64 * 64;
 }
+
+// The break bitmap of the scan kernel (break_bitmap): break(k) at bit k + 64, so that 64 zero bits stand in front, and zero words behind:
+// the 64 bits a step of any window reads are two whole words
+constexpr size_t kRohBreakOffset = 64;
+inline size_t roh_break_words(size_t K, size_t window) { return (K + kRohBreakOffset + 2 * window + 63) / 64 + 2; }
 
 // window and bins of the parameters, in the header's order
 inline const char* roh_check_params(const fmh_roh_params& p) {
@@ -54,9 +60,8 @@ inline bool roh_segment_less(const fmh_roh_segment& a, const fmh_roh_segment& b)
 
 // a run's length, whether it qualifies (rule 8) and its bin
 inline uint64_t roh_length(uint32_t x_first, uint32_t x_last) { return (uint64_t)x_last - x_first + 1; }
-inline bool roh_qualifies(const fmh_roh_params& p, uint64_t n_sites, uint64_t length, uint64_t n_het, uint64_t n_missing) {
-  return n_sites >= p.min_sites && length >= p.min_length && n_het <= p.max_het && n_missing <= p.max_missing &&
-         (p.max_bp_per_site == 0 || length <= (uint64_t)p.max_bp_per_site * n_sites);
+FMH_HOST_DEVICE bool roh_qualifies(const fmh_roh_params& p, uint64_t n_sites, uint64_t length, uint64_t n_het, uint64_t n_missing) {
+  return run_qualifies(p, n_sites, length, n_missing, n_het, p.max_het);
 }
 inline uint32_t roh_bin(const fmh_roh_params& p, uint64_t length) {
   uint32_t b = 0;

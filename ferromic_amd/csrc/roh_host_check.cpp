@@ -2,7 +2,9 @@
 // roh_segment_less) on a seeded planted cohort held in exact-size heap blocks, so that a read or write one element past the state table,
 // the positions, a table or the segment buffer is an ASan report.  The cohort comes from a splitmix64 stream that tests/test_roh_cpu.py
 // restates, the scan runs twice (once to count, once into a buffer of exactly that many segments) and the program prints an order-free
-// checksum of the tables and segments, which the test compares with the oracle's (tests/roh_ref.py: checksum).
+// checksum of the tables and segments, which the test compares with the oracle's (tests/roh_ref.py: checksum).  Before that, silently,
+// the kept rows and the break bitmap the device entry point builds (segment_host_check.hpp), in the scan kernel's layout as well: 64 zero
+// bits in front and zero words behind, for the smallest and the largest window.
 // Built by `make asan` with -fsanitize=address,undefined -fno-sanitize-recover=all.
 //   roh_host_check.asan seed K n window window_het window_missing threshold min_sites min_length max_gap max_bp_per_site max_het max_missing [edge ...]
 #include <algorithm>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "roh_host.hpp"
+#include "segment_host_check.hpp"
 
 static uint64_t g_state = 0;
 static uint64_t rnd() {  // splitmix64
@@ -22,6 +25,11 @@ static uint64_t rnd() {  // splitmix64
 
 int main(int argc, char** argv) {
   if (argc < 14) { fprintf(stderr, "usage: %s seed K n window window_het window_missing threshold min_sites min_length max_gap max_bp_per_site max_het max_missing [edge ...]\n", argv[0]); return 2; }
+  using namespace fmh_host;
+  for (size_t offset : {(size_t)0, kRohBreakOffset})
+    if (!check_kept_rows_and_breaks(offset, [&](size_t K) { return (K + offset + 63) / 64; })) return 1;
+  for (size_t window : {(size_t)1, (size_t)kRohMaxWindow})
+    if (!check_kept_rows_and_breaks(kRohBreakOffset, [&](size_t K) { return roh_break_words(K, window); })) return 1;
   g_state = strtoull(argv[1], nullptr, 10);
   const size_t K = strtoull(argv[2], nullptr, 10), n = strtoull(argv[3], nullptr, 10);
   fmh_roh_params p{};

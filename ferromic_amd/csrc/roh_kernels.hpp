@@ -5,36 +5,34 @@
 // persistent grid; thread t owns sample 256 g + t.  The item walks the VIRTUAL kept rows [s, b1 + W - 1), s = max(0, b0 - (W - 1)): the W - 1
 // rows before the block fill the window history, the W - 1 past it complete the windows that cover the block's last rows (rows at or past K
 // are fed as zeros and complete no window).  A step of 64 kept rows is fetched through the kept-row list, 16 bytes per thread and plane
-// (thread = row of the step x 16-byte part of the group's 64 bytes), turned into `called` and `het` 2-bit fields as score_kernels.hpp does
-// (upper planes, row_gap / row_hi honoured through the per-kept-row flags of roh_flags_kernel) and parked in LDS; the next step's loads are
-// issued before the walk.  A lane gathers ITS bit of the 64 rows into two 64-bit masks and walks them with everything in registers:
+// (thread = row of the step x 16-byte part of the group's 64 bytes; segment_kernels.hpp: plane_fetch, upper planes, row_gap / row_hi
+// honoured through the per-kept-row flags of plane_flags_kernel), turned into `called` and `het` 2-bit fields and parked in LDS; the next
+// step's loads are issued before the walk.  A lane gathers ITS bit of the 64 rows into two 64-bit masks and walks them with everything in registers:
 //   hist_het / hist_miss: bit j = the state of row k - j;   hist_hom: bit j = whether window t = k - (W - 1) - j is homozygous
 //   at virtual row k the window t = k - (W - 1) is complete (iff k - s >= W - 1 and k < K) and row d = k - (W - 1) is decided:
 //   n_hom(d) = popcount(hist_hom & low W bits), n_cov(d) = min(d, K - W) - max(0, d - W + 1) + 1, its own state = bit W - 1 of the histories.
 // k, d, n_cov, need[n_cov] and break(d) are the same for every lane: scalar work.  Runs strictly inside the block are judged, tallied and
-// (when asked for) appended by the lane itself; per (block, sample) the item leaves a fixed record: the partial run that touches the block's
-// first row (head), the one that touches its last row (tail; tail_first == b0 = the whole block is one run, no head then) and the interior
-// tallies.
-// Stitch (roh_stitch_kernel).  One thread per selected sample walks the blocks in order, joins the tail of block j to the head of block
-// j + 1 iff both exist and there is no break at the boundary, judges the joined runs, adds the interior tallies in block order and writes
-// the sample's tables: one writer per entry.  Segments are appended with a vector atomicAdd on a device counter, stored below the capacity.
+// (when asked for) appended by the lane itself; per (block, sample) the item leaves the record of segment_kernels.hpp (SegRec<2>: head,
+// tail and the interior tallies) and, behind its two u64 fields, the block's bins.
+// Stitch (roh_stitch_kernel).  One thread per selected sample joins the blocks by the shared rule (seg_stitch), judges the joined runs,
+// adds the interior tallies and bins in block order and writes the sample's tables: one writer per entry.  Segments are appended with a
+// vector atomicAdd on a device counter, stored below the capacity (seg_append).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ferromic_hip.h"
-#include "assoc_kernels.hpp"  // kAssocEven
 #include "plane_rows.hpp"
+#include "roh_host.hpp"  // roh_qualifies
+#include "segment_kernels.hpp"
 
 namespace fmh {
 
 constexpr uint32_t kRohThreads = 256;
 constexpr uint32_t kRohStepRows = 64;
-constexpr uint32_t kRohGroupSamples = 256;  // 64 bytes of a plane row
-constexpr uint32_t kRohNone = 0xFFFFFFFFu;
-constexpr uint32_t kRohRec32 = 8;           // head_last, head_het, head_miss, tail_first, tail_het, tail_miss, runs, sites
-constexpr uint32_t kRohRec64 = 2;           // length, longest; then bin_runs[n_bins], bin_length[n_bins]
+using RohRec = SegRec<2>;                  // a run carries (het, miss)
+constexpr uint32_t kRohRec64 = kSegRec64;  // length, longest; then bin_runs[n_bins], bin_length[n_bins]
 
 struct RohArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   uint32_t nvec;    // 16-byte vectors of a row through the last selected sample (<= plane_pitch / 16)
@@ -44,11 +42,11 @@ struct RohArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   const uint8_t* flags;            // [K] bit 0: the called plane of the row is read, bit 1: the upper planes are; null = neither exists
   const uint32_t* x;               // [K] positions of the kept rows
   const unsigned long long* brk;   // break(k) at bit k + 64 (64 zero bits in front, zero words behind: any step's window is two whole words)
-  const uint32_t* rank;            // [groups * 256] list position of a matrix sample, kRohNone where it is not selected
+  const uint32_t* rank;            // [groups * 256] list position of a matrix sample, kSegNone where it is not selected
   const uint32_t* samples;         // [n] or null (entry i is sample i)
   uint32_t n, K, item_rows, n_blocks, n_items;
   fmh_roh_params P;
-  uint32_t* rec32;                 // [n_blocks][kRohRec32][groups * 256]
+  uint32_t* rec32;                 // [n_blocks][RohRec::n32][groups * 256]
   unsigned long long* rec64;       // [n_blocks][kRohRec64 + 2 n_bins][groups * 256]
   fmh_roh_segment* segments;       // device, `capacity` elements, or null
   unsigned long long capacity;
@@ -56,10 +54,7 @@ struct RohArgs : PlaneRows {  // the packed image first (plane_rows.hpp)
   fmh_roh_out out;
 };
 
-__device__ __forceinline__ bool roh_qualifies(const fmh_roh_params& P, uint64_t sites, uint64_t length, uint64_t n_het, uint64_t n_missing) {
-  return sites >= P.min_sites && length >= P.min_length && n_het <= P.max_het && n_missing <= P.max_missing &&
-         (P.max_bp_per_site == 0 || length <= (uint64_t)P.max_bp_per_site * sites);
-}
+using fmh_host::roh_qualifies;  // the host twin's rule
 __device__ __forceinline__ uint32_t roh_bin(const fmh_roh_params& P, uint64_t length) {
   uint32_t b = 0;
 #pragma unroll
@@ -67,30 +62,7 @@ __device__ __forceinline__ uint32_t roh_bin(const fmh_roh_params& P, uint64_t le
   return b;
 }
 __device__ __forceinline__ void roh_append(const RohArgs& A, uint32_t rank, uint32_t first, uint32_t last, uint32_t n_het, uint32_t n_missing) {
-  if (!A.counter) return;
-  const unsigned long long at = atomicAdd(A.counter, 1ull);
-  if (A.segments && at < A.capacity) A.segments[at] = fmh_roh_segment{rank, last - first + 1, n_het, n_missing, A.rows[first], A.rows[last]};
-}
-
-// per kept row: which planes the scan has to read of it (the matrix's per-row tables are skip hints; without a table the plane is read)
-static __global__ __launch_bounds__(256) void roh_flags_kernel(const PlaneRows R, size_t row_begin, const uint32_t* __restrict__ rows, uint32_t K,
-                                                               uint8_t* __restrict__ flags) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  const size_t row = row_begin + rows[k];
-  const uint32_t gap = R.pc ? (R.row_gap ? (R.row_gap[row] != 0) : 1u) : 0u;
-  const uint32_t high = (R.p1 || R.p2) ? (R.row_hi ? (R.row_hi[row] != 0) : 1u) : 0u;
-  flags[k] = (uint8_t)(gap | (high << 1));
-}
-
-struct RohStage {
-  uint4 w0, wc, w1, w2;
-};
-
-__device__ __forceinline__ uint4 roh_load(const uint8_t* plane, size_t off, bool on, uint32_t fill) {
-  uint4 v = make_uint4(fill, fill, fill, fill);
-  if (on) v = *reinterpret_cast<const uint4*>(plane + off);
-  return v;
+  seg_append(A, [&] { return fmh_roh_segment{rank, last - first + 1, n_het, n_missing, A.rows[first], A.rows[last]}; });
 }
 
 // Launched with kRohThreads threads; static LDS: 2 x 4 KiB of fields + the need table.
@@ -106,7 +78,7 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
   const uint32_t W = A.P.window, K = A.K, nb = A.P.n_bins;
   const uint64_t mask_w = W == 64 ? ~0ull : ((1ull << W) - 1ull);
   const uint32_t need_full = A.P.need[W];
-  const size_t spad = (size_t)A.groups * kRohGroupSamples;
+  const size_t spad = (size_t)A.groups * kSegGroupSamples;
   if (tid < 65) s_need[tid] = A.P.need[tid];  // read after the first step's barriers
 
   for (uint32_t it = blockIdx.x; it < A.n_items; it += gridDim.x) {
@@ -117,10 +89,10 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
     const uint32_t steps = (uint32_t)((end - s + kRohStepRows - 1) / kRohStepRows);
     const uint32_t vec = 4u * sg + spart;
     const bool inside = vec < A.nvec;  // a vector past the covered samples is zero
-    const size_t slot = (size_t)sg * kRohGroupSamples + tid;
+    const size_t slot = (size_t)sg * kSegGroupSamples + tid;
     const uint32_t rank = A.rank[slot];
-    const bool active = rank != kRohNone;
-    uint32_t* r32 = A.rec32 + (size_t)rb * kRohRec32 * spad + slot;
+    const bool active = rank != kSegNone;
+    uint32_t* r32 = A.rec32 + (size_t)rb * RohRec::n32 * spad + slot;
     unsigned long long* r64 = A.rec64 + (size_t)rb * (kRohRec64 + 2 * nb) * spad + slot;
     if (active)
       for (uint32_t b = 0; b < 2 * nb; ++b) r64[(kRohRec64 + b) * spad] = 0;  // the bins are added to in place: one writer, this lane
@@ -136,19 +108,14 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
       const uint64_t k = (uint64_t)s + (uint64_t)j * kRohStepRows + srow;
       const bool ok = inside && k < K;
       const size_t off = (A.row_begin + row) * A.plane_pitch + (size_t)(inside ? vec : 0) * 16;
-      RohStage g;
-      g.w0 = roh_load(A.p0, off, ok, 0u);
-      g.wc = roh_load(A.pc, off, ok && (fl & 1u), ok ? ~0u : 0u);
-      g.w1 = roh_load(A.p1, off, ok && (fl & 2u) && A.p1, 0u);
-      g.w2 = roh_load(A.p2, off, ok && (fl & 2u) && A.p2, 0u);
-      return g;
+      return plane_fetch(A, off, ok, fl);
     };
 
     // the lane's scan state
     uint64_t hist_het = 0, hist_miss = 0, hist_hom = 0;
     bool open = false;
     uint32_t first = 0, n_het = 0, n_miss = 0;
-    uint32_t head_last = kRohNone, head_het = 0, head_miss = 0;
+    uint32_t head_last = kSegNone, head_het = 0, head_miss = 0;
     uint32_t runs = 0, sites = 0;
     uint64_t length_sum = 0, longest = 0;
 
@@ -171,16 +138,15 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
 
     uint32_t row = 0, fl = 0;
     meta(0, row, fl);
-    RohStage g = fetch(0, row, fl);
+    PlaneStage g = fetch(0, row, fl);
     meta(1, row, fl);
     for (uint32_t j = 0; j < steps; ++j) {
       uint32_t cal[4], het[4];
-      const uint32_t b[4] = {g.w0.x, g.w0.y, g.w0.z, g.w0.w}, pc[4] = {g.wc.x, g.wc.y, g.wc.z, g.wc.w};
-      const uint32_t hi[4] = {g.w1.x | g.w2.x, g.w1.y | g.w2.y, g.w1.z | g.w2.z, g.w1.w | g.w2.w};
+      const PlaneFields f(g);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        cal[q] = pc[q] & (pc[q] >> 1) & ~(hi[q] | (hi[q] >> 1)) & kAssocEven;
-        het[q] = (b[q] ^ (b[q] >> 1)) & cal[q];
+        cal[q] = f.called(q);
+        het[q] = (f.b[q] ^ (f.b[q] >> 1)) & cal[q];
       }
       __syncthreads();  // every lane has gathered the step before this one
       s_cal4[tid] = make_uint4(cal[0], cal[1], cal[2], cal[3]);  // tid = srow * 4 + spart
@@ -229,9 +195,9 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
       }
     }
     if (active) {
-      r32[0 * spad] = head_last; r32[1 * spad] = head_het; r32[2 * spad] = head_miss;
-      r32[3 * spad] = open ? first : kRohNone; r32[4 * spad] = n_het; r32[5 * spad] = n_miss;
-      r32[6 * spad] = runs; r32[7 * spad] = sites;
+      r32[RohRec::head_last * spad] = head_last; r32[RohRec::head_c * spad] = head_het; r32[(RohRec::head_c + 1) * spad] = head_miss;
+      r32[RohRec::tail_first * spad] = open ? first : kSegNone; r32[RohRec::tail_c * spad] = n_het; r32[(RohRec::tail_c + 1) * spad] = n_miss;
+      r32[RohRec::runs * spad] = runs; r32[RohRec::sites * spad] = sites;
       r64[0 * spad] = length_sum; r64[1 * spad] = longest;
     }
   }
@@ -241,8 +207,8 @@ static __global__ __launch_bounds__(kRohThreads) void roh_scan_kernel(const RohA
 static __global__ __launch_bounds__(256) void roh_stitch_kernel(const RohArgs A) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n) return;
-  const uint32_t K = A.K, nb = A.P.n_bins;
-  const size_t spad = (size_t)A.groups * kRohGroupSamples;
+  const uint32_t nb = A.P.n_bins;
+  const size_t spad = (size_t)A.groups * kSegGroupSamples;
   const size_t slot = A.samples ? A.samples[i] : i;
   uint64_t runs = 0, sites = 0, length_sum = 0, longest = 0;
   unsigned long long* bin_runs = A.out.d_bin_runs ? A.out.d_bin_runs + (size_t)i * nb : nullptr;
@@ -251,52 +217,27 @@ static __global__ __launch_bounds__(256) void roh_stitch_kernel(const RohArgs A)
     if (bin_runs) bin_runs[b] = 0;
     if (bin_length) bin_length[b] = 0;
   }
-  auto judge = [&](uint32_t first, uint32_t last, uint32_t n_het, uint32_t n_miss) {
+  auto judge = [&](uint32_t first, uint32_t last, const uint32_t (&c)[2]) {  // c = (het, miss)
     const uint64_t n_sites = last - first + 1, length = (uint64_t)A.x[last] - A.x[first] + 1;
-    if (!roh_qualifies(A.P, n_sites, length, n_het, n_miss)) return;
+    if (!roh_qualifies(A.P, n_sites, length, c[0], c[1])) return;
     ++runs; sites += n_sites; length_sum += length; longest = length > longest ? length : longest;
     if (nb) {
       const uint32_t b = roh_bin(A.P, length);
       if (bin_runs) bin_runs[b] += 1;
       if (bin_length) bin_length[b] += length;
     }
-    roh_append(A, i, first, last, n_het, n_miss);
+    roh_append(A, i, first, last, c[0], c[1]);
   };
-  bool carry = false;  // a run that touches the last row of the block before
-  uint32_t c_first = 0, c_het = 0, c_miss = 0;
-  for (uint32_t rb = 0; rb < A.n_blocks; ++rb) {
-    const uint32_t b0 = rb * A.item_rows, b1 = K - b0 < A.item_rows ? K : b0 + A.item_rows;
-    const uint32_t* r32 = A.rec32 + (size_t)rb * kRohRec32 * spad + slot;
+  auto interior = [&](uint32_t rb, const uint32_t* r32) {
     const unsigned long long* r64 = A.rec64 + (size_t)rb * (kRohRec64 + 2 * nb) * spad + slot;
-    const uint32_t head_last = r32[0], tail_first = r32[3 * spad];
-    const uint64_t at = (uint64_t)b0 + 64;
-    const bool joined = carry && !((A.brk[at >> 6] >> (at & 63)) & 1ull);
-    if (tail_first == b0) {  // the whole block is one run
-      if (joined) { c_het += r32[4 * spad]; c_miss += r32[5 * spad]; }
-      else {
-        if (carry) judge(c_first, b0 - 1, c_het, c_miss);
-        carry = true; c_first = b0; c_het = r32[4 * spad]; c_miss = r32[5 * spad];
-      }
-      continue;  // no interior run
-    }
-    if (head_last != kRohNone) {
-      if (joined) judge(c_first, head_last, c_het + r32[1 * spad], c_miss + r32[2 * spad]);
-      else {
-        if (carry) judge(c_first, b0 - 1, c_het, c_miss);
-        judge(b0, head_last, r32[1 * spad], r32[2 * spad]);
-      }
-    } else if (carry) judge(c_first, b0 - 1, c_het, c_miss);
-    carry = false;
-    runs += r32[6 * spad]; sites += r32[7 * spad]; length_sum += r64[0];
+    runs += r32[RohRec::runs * spad]; sites += r32[RohRec::sites * spad]; length_sum += r64[0];
     longest = r64[1 * spad] > longest ? r64[1 * spad] : longest;
     for (uint32_t b = 0; b < nb; ++b) {
       if (bin_runs) bin_runs[b] += r64[(kRohRec64 + b) * spad];
       if (bin_length) bin_length[b] += r64[(kRohRec64 + nb + b) * spad];
     }
-    if (tail_first != kRohNone) { carry = true; c_first = tail_first; c_het = r32[4 * spad]; c_miss = r32[5 * spad]; }
-    (void)b1;
-  }
-  if (carry) judge(c_first, K - 1, c_het, c_miss);
+  };
+  seg_stitch<2>(A.rec32 + slot, spad, A.n_blocks, A.item_rows, A.K, A.brk, 64, judge, interior);
   if (A.out.d_n_runs) A.out.d_n_runs[i] = runs;
   if (A.out.d_sum_sites) A.out.d_sum_sites[i] = sites;
   if (A.out.d_sum_length) A.out.d_sum_length[i] = length_sum;

@@ -30,8 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "assoc_kernels.hpp"  // assoc_digit, assoc_v4i, kAssocEven
-#include "plane_rows.hpp"
+#include "assoc_kernels.hpp"  // assoc_digit, assoc_v4i
+#include "plane_rows.hpp"  // plane_load, kEvenBits
 
 namespace fmh {
 
@@ -98,13 +98,6 @@ struct ScoreStage {
   uint4 w0, wc, w1, w2, dv, du;
 };
 
-// 16 bytes of a plane row, or `fill` in every word where the plane is not read
-__device__ __forceinline__ uint4 score_load(const uint8_t* plane, size_t off, bool on, uint32_t fill) {
-  uint4 v = make_uint4(fill, fill, fill, fill);
-  if (on) v = *reinterpret_cast<const uint4*>(plane + off);
-  return v;
-}
-
 __device__ __forceinline__ uint32_t score_field(uint32_t word, uint32_t shift, uint32_t width) { return __builtin_amdgcn_ubfe(word, shift, width); }
 
 // Launched with kScoreThreads threads; static LDS: fields 4 160 B (x 2 when CALLED) + digits 4 KiB (x 2).
@@ -148,10 +141,10 @@ __global__ __launch_bounds__(kScoreThreads, 2) void score_sums_kernel(const Scor
         const bool ok = inside && r < rows;
         const size_t off = (A.row_begin + first + (r < rows ? r : rows - 1)) * A.plane_pitch + (size_t)(inside ? vec : 0) * 16;
         ScoreStage g;
-        g.w0 = score_load(A.p0, off, ok, 0u);
-        g.wc = score_load(A.pc, off, ok && gap != 0, ok ? ~0u : 0u);
-        g.w1 = score_load(A.p1, off, ok && high != 0 && A.p1, 0u);
-        g.w2 = score_load(A.p2, off, ok && high != 0 && A.p2, 0u);
+        g.w0 = plane_load(A.p0, off, ok, 0u);
+        g.wc = plane_load(A.pc, off, ok && gap != 0, ok ? ~0u : 0u);
+        g.w1 = plane_load(A.p1, off, ok && high != 0 && A.p1, 0u);
+        g.w2 = plane_load(A.p2, off, ok && high != 0 && A.p2, 0u);
         const size_t d = ((step0 + s) * A.vgroups + vg) * kScoreStepVecs + tid;
         g.dv = A.digits_v[d];
         g.du = CALLED ? A.digits_u[d] : g.dv;
@@ -170,8 +163,8 @@ __global__ __launch_bounds__(kScoreThreads, 2) void score_sums_kernel(const Scor
         const uint32_t hi[4] = {g.w1.x | g.w2.x, g.w1.y | g.w2.y, g.w1.z | g.w2.z, g.w1.w | g.w2.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          cal[q] = pc[q] & (pc[q] >> 1) & ~(hi[q] | (hi[q] >> 1)) & kAssocEven;
-          dos[q] = ((b[q] & kAssocEven) + ((b[q] >> 1) & kAssocEven)) & (cal[q] * 3u);
+          cal[q] = pc[q] & (pc[q] >> 1) & ~(hi[q] | (hi[q] >> 1)) & kEvenBits;
+          dos[q] = ((b[q] & kEvenBits) + ((b[q] >> 1) & kEvenBits)) & (cal[q] * 3u);
         }
         __syncthreads();  // every wave has read the step before this one
         const uint32_t at = srow * 4u + spart + (srow >> 4);

@@ -1140,6 +1140,61 @@ def logistic_stats(score, variance, outputs=LOGISTIC_STATS) -> Dict[str, np.ndar
     return out
 
 
+# ---- what the segment statistics (runs of homozygosity, IBD segments) share --------------------------------------------------------------------
+def _scan_range(m, samples, n_samples, row_begin, row_count, keep, positions):
+    """The arguments of a device scan as the library takes them: (samples, n, rows of the range, keep, positions)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        if positions.size != m.variants:
+            raise ValueError("positions has one entry per row of the matrix")
+    return samples, n, rows, keep, positions
+
+
+def _kept_positions(x, K):
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.size != K:
+            raise ValueError("x has one entry per kept row")
+    return x
+
+
+def _segment_scan(call, sizes: Dict[str, int], dtype: np.dtype, capacity: Optional[int], device: Optional[int] = None):
+    """One fmh_*_scan (device None: fmh_*_scan_host, on host arrays).  call(pointers, segments, capacity, count) gets {table: pointer} for
+    uint64 tables of `sizes` elements, pre-filled with junk, a buffer of `capacity` segments (0: they are counted only, None: not even that)
+    and the count's reference.  Returns ({table: flat array}, segments [min(count, capacity)] or None, count or None)."""
+    host = device is None
+    bufs = {name: np.full(max(size, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) for name, size in sizes.items()}
+    seg = np.zeros(capacity, dtype=dtype) if capacity else None
+    if not host:
+        bufs = {name: DeviceBuffer.from_numpy(device, junk) for name, junk in bufs.items()}
+        seg = DeviceBuffer(device, capacity * dtype.itemsize) if capacity else None
+    count = C.c_uint64(0)
+    call({name: b.ctypes.data if host else b.ptr for name, b in bufs.items()}, None if seg is None else _ptr(seg) if host else seg.ptr, capacity or 0,
+         C.byref(count) if capacity is not None else None)
+    tables = {name: bufs[name][:size].copy() if host else bufs[name].to_numpy(np.uint64, size) for name, size in sizes.items()}
+    if capacity is None:
+        return tables, None, None
+    stored = min(int(count.value), capacity)
+    segments = np.zeros(0, dtype=dtype) if seg is None else seg[:stored].copy() if host else seg.to_numpy(dtype, stored)
+    return tables, segments, int(count.value)
+
+
+def _sort_segments(sort, segments, dtype: np.dtype) -> np.ndarray:
+    out = np.ascontiguousarray(segments, dtype=dtype).copy()
+    _abi.check(sort(_ptr(out) if out.size else None, out.size))
+    return out
+
+
 # ---- runs of homozygosity: per-sample sliding-window scan along the kept rows ---------------------------------------------------------------
 ROH_DEFAULT_ITEM_ROWS = 4096   # FMH_ROH_ITEM_ROWS unset
 ROH_TABLES = ("n_runs", "sum_sites", "sum_length", "longest_length")
@@ -1181,10 +1236,13 @@ class RohResult:
     count: Optional[int]                 # the exact number of qualifying runs, or None when segments were not asked for
 
 
-def _roh_result(n, n_bins, get, segments, count):
-    tables = {name: get(name, n) for name in ROH_TABLES}
+def _roh_scan(call, n, n_bins, capacity, device=None) -> RohResult:
+    sizes = {name: n for name in ROH_TABLES}
+    sizes.update(bin_runs=n * n_bins, bin_length=n * n_bins)
+    tables, segments, count = _segment_scan(lambda ptrs, *rest: call(_abi.RohOut(*[ptrs[name] for name in sizes]), *rest), sizes,
+                                            ROH_SEGMENT_DTYPE, capacity, device)
     for name in ("bin_runs", "bin_length"):
-        tables[name] = get(name, n * n_bins).reshape(n, n_bins)
+        tables[name] = tables[name].reshape(n, n_bins)
     return RohResult(tables, segments, count)
 
 
@@ -1193,60 +1251,24 @@ def roh_scan(m: DeviceMatrix, params, samples=None, n_samples: Optional[int] = N
     """fmh_roh_scan over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
     n_samples, default all).  `positions` [variants] uint32 (indexed by matrix row) or None.  `capacity`: None = no segments, else the
     elements of the segment buffer (0: the runs are counted only)."""
-    rows = m.variants - row_begin if row_count is None else row_count
-    if samples is not None:
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        n = samples.size
-    else:
-        n = m.samples if n_samples is None else int(n_samples)
-    if keep is not None:
-        keep = np.ascontiguousarray(keep, dtype=np.uint8)
-        if keep.size != rows:
-            raise ValueError("keep has one entry per row of the range")
-    if positions is not None:
-        positions = np.ascontiguousarray(positions, dtype=np.uint32)
-        if positions.size != m.variants:
-            raise ValueError("positions has one entry per row of the matrix")
-    nb = int(params.n_bins)
-    names = ROH_TABLES + ("bin_runs", "bin_length")
-    sizes = {name: n * (nb if name.startswith("bin_") else 1) for name in names}
-    bufs = {name: DeviceBuffer.from_numpy(m.device, np.full(max(sizes[name], 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)) for name in names}
-    out = _abi.RohOut(*[bufs[name].ptr for name in names])
-    d_seg = DeviceBuffer(m.device, max(capacity, 1) * ROH_SEGMENT_DTYPE.itemsize) if capacity else None
-    count = C.c_uint64(0)
-    _abi.check(_abi.load().fmh_roh_scan(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params), C.byref(out),
-                                        d_seg.ptr if d_seg else None, capacity or 0, C.byref(count) if capacity is not None else None, stream))
-    segments = None
-    if capacity is not None:
-        segments = d_seg.to_numpy(ROH_SEGMENT_DTYPE, min(int(count.value), capacity)) if d_seg else np.zeros(0, dtype=ROH_SEGMENT_DTYPE)
-    return _roh_result(n, nb, lambda name, size: bufs[name].to_numpy(np.uint64, size), segments, int(count.value) if capacity is not None else None)
+    samples, n, rows, keep, positions = _scan_range(m, samples, n_samples, row_begin, row_count, keep, positions)
+    return _roh_scan(lambda out, seg, cap, count: _abi.check(_abi.load().fmh_roh_scan(
+        m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params), C.byref(out), seg, cap, count, stream)),
+        n, int(params.n_bins), capacity, m.device)
 
 
 def roh_scan_host(state, params, x=None, capacity: Optional[int] = None) -> RohResult:
     """fmh_roh_scan_host (host only): the same scan over `state` uint8 [K][n] (0 HOM, 1 HET, 2 MISS) and `x` uint32 [K] or None."""
     state = np.ascontiguousarray(state, dtype=np.uint8)
     K, n = state.shape
-    if x is not None:
-        x = np.ascontiguousarray(x, dtype=np.uint32)
-        if x.size != K:
-            raise ValueError("x has one entry per kept row")
-    nb = int(params.n_bins)
-    names = ROH_TABLES + ("bin_runs", "bin_length")
-    host = {name: np.full(max(n * (nb if name.startswith("bin_") else 1), 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) for name in names}
-    out = _abi.RohOut(*[host[name].ctypes.data for name in names])
-    seg = np.zeros(max(capacity or 0, 1), dtype=ROH_SEGMENT_DTYPE)
-    count = C.c_uint64(0)
-    _abi.check(_abi.load().fmh_roh_scan_host(_ptr(state) if state.size else None, _ptr(x), K, n, C.byref(params), C.byref(out),
-                                             _ptr(seg) if capacity else None, capacity or 0, C.byref(count) if capacity is not None else None))
-    segments = seg[: min(int(count.value), capacity)].copy() if capacity is not None else None
-    return _roh_result(n, nb, lambda name, size: host[name][:size].copy(), segments, int(count.value) if capacity is not None else None)
+    x = _kept_positions(x, K)
+    return _roh_scan(lambda out, seg, cap, count: _abi.check(_abi.load().fmh_roh_scan_host(
+        _ptr(state) if state.size else None, _ptr(x), K, n, C.byref(params), C.byref(out), seg, cap, count)), n, int(params.n_bins), capacity)
 
 
 def roh_sort_segments(segments: np.ndarray) -> np.ndarray:
     """fmh_roh_sort_segments (host only): a copy ordered by (sample, first_row)."""
-    out = np.ascontiguousarray(segments, dtype=ROH_SEGMENT_DTYPE).copy()
-    _abi.check(_abi.load().fmh_roh_sort_segments(_ptr(out) if out.size else None, out.size))
-    return out
+    return _sort_segments(_abi.load().fmh_roh_sort_segments, segments, ROH_SEGMENT_DTYPE)
 
 
 # ---- IBD segments: pairwise shared-segment scan along the kept rows ----------------------------------------------------------------------------
@@ -1273,63 +1295,36 @@ class IbdResult:
     count: Optional[int]                 # the exact number of qualifying runs, or None when segments were not asked for
 
 
+def _ibd_scan(call, n, names, capacity, device=None) -> IbdResult:
+    """`names`: the tables asked for; the others go to the library as NULL."""
+    tables, segments, count = _segment_scan(lambda ptrs, *rest: call(_abi.IbdOut(*[ptrs.get(name) for name in IBD_TABLES]), *rest),
+                                            {name: n * n for name in names}, IBD_SEGMENT_DTYPE, capacity, device)
+    return IbdResult({name: t.reshape(n, n) for name, t in tables.items()}, segments, count)
+
+
 def ibd_scan(m: DeviceMatrix, params, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
              positions=None, capacity: Optional[int] = None, stream=None, tables=IBD_TABLES) -> IbdResult:
     """fmh_ibd_scan over rows [row_begin, row_begin + row_count) for all pairs of the samples `samples` (ascending sample numbers; None = the
     first n_samples, default all).  `positions` [variants] uint32 (indexed by matrix row) or None.  `capacity`: None = no segments, else the
     elements of the segment buffer (0: the runs are counted only).  `tables`: the tables asked for; they are pre-filled with junk."""
-    rows = m.variants - row_begin if row_count is None else row_count
-    if samples is not None:
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        n = samples.size
-    else:
-        n = m.samples if n_samples is None else int(n_samples)
-    if keep is not None:
-        keep = np.ascontiguousarray(keep, dtype=np.uint8)
-        if keep.size != rows:
-            raise ValueError("keep has one entry per row of the range")
-    if positions is not None:
-        positions = np.ascontiguousarray(positions, dtype=np.uint32)
-        if positions.size != m.variants:
-            raise ValueError("positions has one entry per row of the matrix")
-    bufs = {name: DeviceBuffer.from_numpy(m.device, np.full(max(n * n, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)) for name in tables}
-    out = _abi.IbdOut(*[bufs[name].ptr if name in bufs else None for name in IBD_TABLES])
-    d_seg = DeviceBuffer(m.device, max(capacity, 1) * IBD_SEGMENT_DTYPE.itemsize) if capacity else None
-    count = C.c_uint64(0)
-    _abi.check(_abi.load().fmh_ibd_scan(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params),
-                                        C.byref(out) if tables else None, d_seg.ptr if d_seg else None, capacity or 0,
-                                        C.byref(count) if capacity is not None else None, stream))
-    segments = None
-    if capacity is not None:
-        segments = d_seg.to_numpy(IBD_SEGMENT_DTYPE, min(int(count.value), capacity)) if d_seg else np.zeros(0, dtype=IBD_SEGMENT_DTYPE)
-    return IbdResult({name: bufs[name].to_numpy(np.uint64, n * n).reshape(n, n) for name in tables}, segments,
-                     int(count.value) if capacity is not None else None)
+    samples, n, rows, keep, positions = _scan_range(m, samples, n_samples, row_begin, row_count, keep, positions)
+    return _ibd_scan(lambda out, seg, cap, count: _abi.check(_abi.load().fmh_ibd_scan(
+        m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params), C.byref(out) if tables else None, seg, cap, count, stream)),
+        n, tables, capacity, m.device)
 
 
 def ibd_scan_host(dosage, params, x=None, capacity: Optional[int] = None) -> IbdResult:
     """fmh_ibd_scan_host (host only): the same scan over `dosage` uint8 [K][n] (0, 1, 2; 3 = not called) and `x` uint32 [K] or None."""
     dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
     K, n = dosage.shape
-    if x is not None:
-        x = np.ascontiguousarray(x, dtype=np.uint32)
-        if x.size != K:
-            raise ValueError("x has one entry per kept row")
-    host = {name: np.full(max(n * n, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) for name in IBD_TABLES}
-    out = _abi.IbdOut(*[host[name].ctypes.data for name in IBD_TABLES])
-    seg = np.zeros(max(capacity or 0, 1), dtype=IBD_SEGMENT_DTYPE)
-    count = C.c_uint64(0)
-    _abi.check(_abi.load().fmh_ibd_scan_host(_ptr(dosage) if dosage.size else None, _ptr(x), K, n, C.byref(params), C.byref(out),
-                                             _ptr(seg) if capacity else None, capacity or 0, C.byref(count) if capacity is not None else None))
-    segments = seg[: min(int(count.value), capacity)].copy() if capacity is not None else None
-    return IbdResult({name: host[name][: n * n].copy().reshape(n, n) for name in IBD_TABLES}, segments,
-                     int(count.value) if capacity is not None else None)
+    x = _kept_positions(x, K)
+    return _ibd_scan(lambda out, seg, cap, count: _abi.check(_abi.load().fmh_ibd_scan_host(
+        _ptr(dosage) if dosage.size else None, _ptr(x), K, n, C.byref(params), C.byref(out), seg, cap, count)), n, IBD_TABLES, capacity)
 
 
 def ibd_sort_segments(segments: np.ndarray) -> np.ndarray:
     """fmh_ibd_sort_segments (host only): a copy ordered by (a, b, first_row)."""
-    out = np.ascontiguousarray(segments, dtype=IBD_SEGMENT_DTYPE).copy()
-    _abi.check(_abi.load().fmh_ibd_sort_segments(_ptr(out) if out.size else None, out.size))
-    return out
+    return _sort_segments(_abi.load().fmh_ibd_sort_segments, segments, IBD_SEGMENT_DTYPE)
 
 
 # ---- LD clumping: genotype r^2 around index sites --------------------------------------------------------------------------------------------
