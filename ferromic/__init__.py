@@ -16,6 +16,8 @@ from ._core import (  # noqa: E402,F401
     FStatEstimate,
     FStatistics,
     FstEstimate,
+    GeneticRelationship,
+    GenotypePCA,
     GenotypeQC,
     HaplotypeScan,
     HaplotypeWindows,
@@ -43,6 +45,7 @@ from ._core import (  # noqa: E402,F401
     genotype_ld,
     genotype_qc,
     global_pca,
+    grm,
     hudson_dxy,
     hudson_fst,
     hudson_fst_sites,

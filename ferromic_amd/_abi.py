@@ -177,6 +177,15 @@ class ClumpParams(C.Structure):
     _fields_ = [("p1", C.c_double), ("p2", C.c_double), ("r2", C.c_double), ("window", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GrmParams(C.Structure):
+    _fields_ = [("method", C.c_uint32), ("denominator", C.c_uint32)]
+
+
+class GrmOut(C.Structure):
+    _fields_ = [("d_products", C.c_void_p), ("d_pair_sites", C.c_void_p), ("h_called", C.c_void_p), ("h_allele_count", C.c_void_p),
+                ("h_usable", C.c_void_p), ("h_usable_rows", C.POINTER(C.c_uint64)), ("h_scale", C.POINTER(C.c_double))]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -304,6 +313,11 @@ SYMBOLS = {
     "fmh_geno_ld_r2": (_i, [_vp, _sz, _vp]),
     "fmh_geno_ld_pairs_host": (_i, [_vp, _sz, _sz, _vp, _vp, _sz, _vp]),
     "fmh_clump_host": (_i, [_vp, _vp, _vp, _sz, _sz, _P(ClumpParams), _vp, _vp, _P(_u64)]),
+    "fmh_grm": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _P(GrmParams), _P(GrmOut), _P(_u64), _vp]),
+    "fmh_grm_values": (_i, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _P(_d), _P(_u64)]),
+    "fmh_grm_finish": (_i, [_vp, _vp, _sz, _P(GrmParams), _u64, _d, _vp]),
+    "fmh_grm_host": (_i, [_vp, _sz, _sz, _u32, _vp, _vp, _P(_u64), _P(_d)]),
+    "fmh_grm_eigen": (_i, [_i, _vp, _sz, _sz, _vp, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),
@@ -343,6 +357,7 @@ SYMBOLS = {
     "fmh_timing_reset_reduce": (_i, []),
     "fmh_timing_read_pca": (_i, [_P(_d)]),
     "fmh_timing_read_gram": (_i, [_P(_d)]),
+    "fmh_timing_read_grm": (_i, [_P(_d)]),
     "fmh_timing_enable": (_i, [_i]),
     "fmh_timing_reset": (_i, []),
     "fmh_timing_read": (_i, [_P(_d), _P(_u64)]),

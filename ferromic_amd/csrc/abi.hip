@@ -96,6 +96,7 @@ const OptionRow kOptionRows[] = {
     {"FMH_PCA_EIGEN", &Options::pca_eigen, 0, "host=1,rocsolver=2,auto=0"},
     {"FMH_PCA_SPLITS", &Options::pca_splits, 0, nullptr},
     {"FMH_PCA_BUDGET_BYTES", &Options::pca_budget_bytes, (long long)16 << 30, nullptr},
+    {"FMH_GRM_SPLITS", &Options::grm_splits, 0, nullptr},
     {"FMH_SFS_ITEM_ROWS", &Options::sfs_item_rows, 0, nullptr},
     {"FMH_SFS_LDS_BINS", &Options::sfs_lds_bins, 0, nullptr},
     {"FMH_HAP_THREADS", &Options::hap_threads, 0, nullptr},

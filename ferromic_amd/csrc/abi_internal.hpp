@@ -85,6 +85,7 @@ struct Options {
   std::atomic<long long> pca_eigen{0};           // FMH_PCA_EIGEN = host | rocsolver: the PCA's symmetric eigen solver; 0 = rocSOLVER, the host solver when it cannot be loaded
   std::atomic<long long> pca_splits{0};          // FMH_PCA_SPLITS: K splits of the PCA Gram (1 = none); 0 = by the tile count
   std::atomic<long long> pca_budget_bytes{(long long)16 << 30};  // FMH_PCA_BUDGET_BYTES: device memory one fmh_pca_gram call may use (Gram + bit words + slabs)
+  std::atomic<long long> grm_splits{0};          // FMH_GRM_SPLITS: K splits of the relationship matrix's Gram (1 = none); 0 = by the tile count
   std::atomic<long long> sfs_item_rows{0};       // FMH_SFS_ITEM_ROWS: rows per work item of the site frequency spectrum kernel; 0 = 4 096
   std::atomic<long long> sfs_lds_bins{0};        // FMH_SFS_LDS_BINS: cap on that kernel's LDS tile in bins (tests: tiny shapes take the global path and the corner mapping); 0 = 5 116, an eighth of a CU's LDS (at most 40 956, all of it)
   std::atomic<long long> hap_threads{0};         // FMH_HAP_THREADS = 64 | 256 | 512 | 1024: threads per workgroup of the haplotype window kernel (raised where a group needs more); 0 = by the group size
@@ -247,6 +248,9 @@ int pca_gram_check(const fmh_matrix* m, const uint64_t* h_kept_rows, size_t n_ke
                    double* d_gram, size_t extra_bytes);
 int pca_pack_triangle(const double* d_full, size_t n, double* d_tri, hipStream_t st);
 int pca_unpack_triangle(const double* d_tri, size_t n, double* d_full, hipStream_t st);
+// the top eigenpairs of a symmetric device matrix (overwritten) through the solver FMH_PCA_EIGEN names (pca.hip): lambda[k] descending,
+// row k of `top` the unit eigenvector; arguments already checked
+int pca_eigen_top(int device, double* d_matrix, size_t n, size_t n_components, std::vector<double>& lambda, std::vector<double>& top);
 
 // One function per (mask route, lanes per row): dispatches on (P, mode, missing, general) to the instantiation, sizes the
 // persistent grid and launches.  FMH_ERR_UNSUPPORTED for a combination the route does not build.

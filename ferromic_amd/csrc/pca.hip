@@ -393,11 +393,10 @@ int pca_unpack_triangle(const double* d_tri, size_t n, double* d_full, hipStream
 
 }  // namespace fmhi
 
-extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t n_components, double* h_eigenvalues, double* h_scores) {
-  if (!d_gram || !h_eigenvalues || !h_scores) return fail(FMH_ERR_INVALID, "NULL argument");
-  if (n < 2) return fail(FMH_ERR_INVALID, "haplotype PCA needs at least two haplotypes");
-  if (n_components == 0 || n_components > n) return fail(FMH_ERR_INVALID, "n_components %zu outside 1..%zu", n_components, n);
-  if (n > 46340) return fail(FMH_ERR_UNSUPPORTED, "the eigen solver takes at most 46 340 haplotypes (n * n must fit a 32-bit index), got %zu", n);
+// The top n_components eigenpairs of the symmetric d_gram[n][n] (OVERWRITTEN) through the solver FMH_PCA_EIGEN names: lambda[k] = the k-th
+// largest eigenvalue, row k of `top` its unit eigenvector.  The arguments have been checked; fmh_pca_eigen_scores and fmh_grm_eigen (grm.hip)
+// share it.
+int fmhi::pca_eigen_top(int device, double* d_gram, size_t n, size_t n_components, std::vector<double>& lambda, std::vector<double>& top) {
   FMH_TRY(use_device(device));
   const long long mode = options().pca_eigen.load();  // 0 = rocSOLVER, host when it cannot be loaded; 1 = host; 2 = rocSOLVER or an error
   SolverApi* api = nullptr;
@@ -413,8 +412,8 @@ extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t
       });
     }
   }
-  // `top`: row k = the unit eigenvector of the k-th largest eigenvalue lambda[k]
-  std::vector<double> top(n_components * n), lambda(n_components);
+  top.assign(n_components * n, 0.0);
+  lambda.assign(n_components, 0.0);
   if (api) {
     std::lock_guard<std::mutex> one_at_a_time(g_solver_device_mutex[device & 63]);
     KernelTimer<> timer;
@@ -457,6 +456,17 @@ extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t
       for (size_t i = 0; i < n; ++i) top[k * n + i] = a[i * n + (n - 1 - k)];
     }
   }
+  return FMH_OK;
+}
+
+extern "C" int fmh_pca_eigen_scores(int device, double* d_gram, size_t n, size_t n_components, double* h_eigenvalues, double* h_scores) {
+  if (!d_gram || !h_eigenvalues || !h_scores) return fail(FMH_ERR_INVALID, "NULL argument");
+  if (n < 2) return fail(FMH_ERR_INVALID, "haplotype PCA needs at least two haplotypes");
+  if (n_components == 0 || n_components > n) return fail(FMH_ERR_INVALID, "n_components %zu outside 1..%zu", n_components, n);
+  if (n > 46340) return fail(FMH_ERR_UNSUPPORTED, "the eigen solver takes at most 46 340 haplotypes (n * n must fit a 32-bit index), got %zu", n);
+  // `top`: row k = the unit eigenvector of the k-th largest eigenvalue lambda[k]
+  std::vector<double> top, lambda;
+  FMH_TRY(pca_eigen_top(device, d_gram, n, n_components, lambda, top));
   // pca.rs:771-797: a column stays zero when its eigenvalue (or sigma) is not above the threshold
   for (size_t k = 0; k < n_components; ++k) {
     h_eigenvalues[k] = lambda[k];

@@ -10,6 +10,8 @@
 // 4 x 4 v_mfma_f64_16x16x4_f64 accumulators (128 VGPRs).  Per 4 sites a wave expands 4 A and 4 B operands (a bit test and a two-register
 // select each) and issues 16 MFMAs, so the expansion hides under the matrix pipe.  The f64 MFMA's register map (NOT that of the other shapes):
 // A: lane l holds A[row l & 15][k = l >> 4]; B: lane l holds B[k = l >> 4][col l & 15]; C/D: col = l & 15, row = (l >> 4) + 4 * reg.
+// (The kernels are static: grm_kernels.hpp takes the tile geometry, the mirror store and pca_slab_reduce_kernel from here, so two units
+// include this header.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,7 +41,7 @@ __device__ inline unsigned pca_wave_or(unsigned v) {
 // One wave per row.  alt = called entries whose allele is exactly 1; flags: kPcaFlagUncalled when a column is not called,
 // kPcaFlagHighAllele when a called entry is above 1.  row_gap / row_hi (one byte per row, may be null) spare the called / high planes
 // of the rows that have nothing there.
-__global__ __launch_bounds__(256) void pca_scan_packed_kernel(const uint8_t* __restrict__ p0, const uint8_t* __restrict__ p1, const uint8_t* __restrict__ p2,
+static __global__ __launch_bounds__(256) void pca_scan_packed_kernel(const uint8_t* __restrict__ p0, const uint8_t* __restrict__ p1, const uint8_t* __restrict__ p2,
                                                               const uint8_t* __restrict__ pc, const uint8_t* __restrict__ row_gap,
                                                               const uint8_t* __restrict__ row_hi, size_t plane_pitch, uint32_t columns, size_t row_begin,
                                                               size_t row_count, uint32_t* __restrict__ alt, uint8_t* __restrict__ flags) {
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(256) void pca_scan_packed_kernel(const uint8_t* __r
   if (lane == 0) { alt[r] = (uint32_t)count; flags[r] = (uint8_t)f; }
 }
 
-__global__ __launch_bounds__(256) void pca_scan_bytes_kernel(const uint8_t* __restrict__ data, size_t pitch, const uint8_t* __restrict__ bits,
+static __global__ __launch_bounds__(256) void pca_scan_bytes_kernel(const uint8_t* __restrict__ data, size_t pitch, const uint8_t* __restrict__ bits,
                                                              size_t bits_pitch, uint32_t columns, size_t row_begin, size_t row_count,
                                                              uint32_t* __restrict__ alt, uint8_t* __restrict__ flags) {
   const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -108,7 +110,7 @@ __device__ inline void pca_transpose_store(unsigned long long word, unsigned lan
   *dst = out;
 }
 
-__global__ __launch_bounds__(256) void pca_transpose_packed_kernel(const uint8_t* __restrict__ p0, size_t plane_pitch, const unsigned long long* __restrict__ kept,
+static __global__ __launch_bounds__(256) void pca_transpose_packed_kernel(const uint8_t* __restrict__ p0, size_t plane_pitch, const unsigned long long* __restrict__ kept,
                                                                    size_t n_kept, uint32_t n_pad, unsigned long long* __restrict__ bitsT) {
   const unsigned lane = threadIdx.x & 63;
   const uint32_t hb = blockIdx.y * 4 + (threadIdx.x >> 6);  // n_pad is a multiple of 128: whole waves are in or out
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(256) void pca_transpose_packed_kernel(const uint8_t
   pca_transpose_store(word, lane, bitsT + w * n_pad + (size_t)hb * 64 + lane);
 }
 
-__global__ __launch_bounds__(256) void pca_transpose_bytes_kernel(const uint8_t* __restrict__ data, size_t pitch, uint32_t columns,
+static __global__ __launch_bounds__(256) void pca_transpose_bytes_kernel(const uint8_t* __restrict__ data, size_t pitch, uint32_t columns,
                                                                   const unsigned long long* __restrict__ kept, size_t n_kept, uint32_t n_pad,
                                                                   unsigned long long* __restrict__ bitsT) {
   const unsigned lane = threadIdx.x & 63;
@@ -156,7 +158,7 @@ __device__ inline void pca_store_entry(double* __restrict__ gram, uint32_t n, ui
 
 // grid (tiles, splits); words [split * words_per_split, ...) of the K range, words_per_split a multiple of kPcaStageWords.
 // splits == 1: the tile goes straight to `gram` (divided by `denom`); otherwise to slabs[split][tile][128][128] for pca_slab_reduce_kernel.
-__global__ __launch_bounds__(256, 2) void pca_gram_kernel(const unsigned long long* __restrict__ bitsT, const double2* __restrict__ vals, uint32_t n_pad,
+static __global__ __launch_bounds__(256, 2) void pca_gram_kernel(const unsigned long long* __restrict__ bitsT, const double2* __restrict__ vals, uint32_t n_pad,
                                                        uint32_t kwords, uint32_t nt, uint32_t words_per_split, uint32_t n, double denom,
                                                        double* __restrict__ gram, double* __restrict__ slabs) {
   __shared__ double2 s_vals[2][kPcaStageSites];
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void pca_gram_kernel(const unsigned long lo
 
 // One thread per entry of every upper-triangular tile: the splits' partials summed in split order (a fixed order: two runs give the
 // same bits), divided, written with the mirror.
-__global__ __launch_bounds__(256) void pca_slab_reduce_kernel(const double* __restrict__ slabs, uint32_t tiles, uint32_t splits, uint32_t nt, uint32_t n,
+static __global__ __launch_bounds__(256) void pca_slab_reduce_kernel(const double* __restrict__ slabs, uint32_t tiles, uint32_t splits, uint32_t nt, uint32_t n,
                                                               double denom, double* __restrict__ gram) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   const size_t per_tile = (size_t)kPcaTile * kPcaTile;
@@ -272,7 +274,7 @@ constexpr int kPcaTriRows = 16, kPcaTriCols = 32;
 __device__ inline size_t pca_tri_offset(size_t i, size_t n) { return i * n - i * (i - 1) / 2 - i; }  // + column = index of (i, column)
 
 // full[n][n] -> tri: tiles wholly below the diagonal have nothing to write
-__global__ __launch_bounds__(256) void pca_pack_triangle_kernel(const double* __restrict__ full, uint32_t n, uint32_t tiles_x, double* __restrict__ tri) {
+static __global__ __launch_bounds__(256) void pca_pack_triangle_kernel(const double* __restrict__ full, uint32_t n, uint32_t tiles_x, double* __restrict__ tri) {
   const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
   const uint32_t r = ty * kPcaTriRows + (threadIdx.x >> 4), c = tx * kPcaTriCols + 2 * (threadIdx.x & 15);
   if (r >= n || c >= n || c + 1 < r) return;
@@ -289,7 +291,7 @@ __global__ __launch_bounds__(256) void pca_pack_triangle_kernel(const double* __
 // tri -> full[n][n]: entry (r, c) reads the packed (min, max) element, so (r, c) and (c, r) carry the same bits whatever order the
 // transport added in.  The writes are whole row segments; below the diagonal the reads of a tile walk down packed rows, 16
 // neighbouring rows of one column = one 128-byte line.
-__global__ __launch_bounds__(256) void pca_unpack_triangle_kernel(const double* __restrict__ tri, uint32_t n, uint32_t tiles_x, double* __restrict__ full) {
+static __global__ __launch_bounds__(256) void pca_unpack_triangle_kernel(const double* __restrict__ tri, uint32_t n, uint32_t tiles_x, double* __restrict__ full) {
   const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
   const uint32_t r = ty * kPcaTriRows + (threadIdx.x >> 4), c = tx * kPcaTriCols + 2 * (threadIdx.x & 15);
   if (r >= n || c >= n) return;

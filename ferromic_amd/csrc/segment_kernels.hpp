@@ -1,7 +1,8 @@
 // segment_kernels.hpp — the device side the segment statistics share (runs of homozygosity: roh_kernels.hpp, IBD segments:
 // ibd_kernels.hpp): a thread's 16 bytes of the four planes of a kept row and the `called` fields derived from them, the per-kept-row plane
 // flags, the record a (row block, owner) leaves, the rule that joins the blocks' records, and the append of a segment through the device
-// counter.  One rule in one place: a third segment statistic includes this header and writes its own walk.  (A kernel declared here is
+// counter.  One rule in one place: a third segment statistic includes this header and writes its own walk; grm_kernels.hpp takes the fetch
+// and the plane flags for its code image.  (A kernel declared here is
 // emitted into every unit that includes the header: what score_kernels.hpp shares with these, the plane load, is in plane_rows.hpp.)
 #pragma once
 

@@ -692,6 +692,113 @@ def kinship_unrelated(kinship, threshold: float) -> np.ndarray:
     return keep.astype(bool)
 
 
+# ---- genomic relationship matrix and its eigenpairs ---------------------------------------------------------------------------------------
+GRM_METHODS = ("standardized", "centered")   # FMH_GRM_STANDARDIZED, FMH_GRM_CENTERED
+GRM_DENOMINATORS = ("sites", "pairs")        # FMH_GRM_SITES, FMH_GRM_PAIRS
+
+
+def grm_params(method: str = "standardized", denominator: str = "sites") -> "_abi.GrmParams":
+    return _abi.GrmParams(GRM_METHODS.index(method), GRM_DENOMINATORS.index(denominator))
+
+
+@dataclass
+class GrmResult:
+    products: np.ndarray               # S [n][n] float64
+    pair_sites: Optional[np.ndarray]   # N [n][n] uint64, or None
+    called: np.ndarray                 # c, a and the usable flag of the kept rows
+    allele_count: np.ndarray
+    usable: np.ndarray
+    n_usable: int
+    scale: float
+    kept_rows: int
+
+
+class GrmBuffers:
+    """The [n][n] device matrices fmh_grm ADDS into: S (f64) and, with pairs=True, N (u64); zero (or `fill` / `fill_pairs`) on creation."""
+
+    def __init__(self, device: int, n: int, pairs: bool = False, fill: Optional[np.ndarray] = None, fill_pairs: Optional[np.ndarray] = None):
+        self.device, self.n = device, int(n)
+        fill = np.zeros(self.n * self.n, dtype=np.float64) if fill is None else np.ascontiguousarray(fill, dtype=np.float64)
+        self.products = DeviceBuffer.from_numpy(device, fill)
+        self.pair_sites = None
+        if pairs:
+            fill_pairs = np.zeros(self.n * self.n, dtype=np.uint64) if fill_pairs is None else np.ascontiguousarray(fill_pairs, dtype=np.uint64)
+            self.pair_sites = DeviceBuffer.from_numpy(device, fill_pairs)
+
+
+def grm(m: DeviceMatrix, params=None, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+        pairs: bool = False, into: Optional[GrmBuffers] = None, stream=None) -> GrmResult:
+    """fmh_grm: the products S (and with `pairs` the pair counts N) of the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all) over the usable rows among those of [row_begin, row_begin + row_count) that `keep` keeps.  `into`: accumulate."""
+    params = grm_params() if params is None else params
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    bufs = into if into is not None else GrmBuffers(m.device, n, pairs or params.denominator == 1)
+    called, allele_count, usable = np.zeros(max(rows, 1), np.uint32), np.zeros(max(rows, 1), np.uint32), np.zeros(max(rows, 1), np.uint8)
+    n_usable, scale, kept = C.c_uint64(0), C.c_double(0.0), C.c_uint64(0)
+    out = _abi.GrmOut(bufs.products.ptr, None if bufs.pair_sites is None else bufs.pair_sites.ptr, _ptr(called), _ptr(allele_count), _ptr(usable),
+                      C.pointer(n_usable), C.pointer(scale))
+    _abi.check(_abi.load().fmh_grm(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), C.byref(params), C.byref(out), C.byref(kept), stream))
+    k = int(kept.value)
+    S = bufs.products.to_numpy(np.float64, n * n).reshape(n, n)
+    N = None if bufs.pair_sites is None else bufs.pair_sites.to_numpy(np.uint64, n * n).reshape(n, n)
+    return GrmResult(S, N, called[:k], allele_count[:k], usable[:k].astype(bool), int(n_usable.value), float(scale.value), k)
+
+
+def grm_values(called, allele_count, method: str = "standardized"):
+    """fmh_grm_values (host only): (usable bool [rows], p [rows], z [rows][3], scale, n_usable) from the exact counts."""
+    c, a = np.ascontiguousarray(called, dtype=np.uint32), np.ascontiguousarray(allele_count, dtype=np.uint32)
+    if c.shape != a.shape or c.ndim != 1:
+        raise ValueError("called and allele_count are one-dimensional and of one length")
+    rows = c.size
+    usable, p, z = np.zeros(rows, np.uint8), np.zeros(rows, np.float64), np.zeros((rows, 3), np.float64)
+    scale, n_usable = C.c_double(0.0), C.c_uint64(0)
+    _abi.check(_abi.load().fmh_grm_values(_ptr(c), _ptr(a), rows, GRM_METHODS.index(method), _ptr(usable), _ptr(p), _ptr(z), C.byref(scale), C.byref(n_usable)))
+    return usable.astype(bool), p, z, float(scale.value), int(n_usable.value)
+
+
+def grm_finish(products, pair_sites, n_usable: int, scale: float, params=None) -> np.ndarray:
+    """fmh_grm_finish (host only): A [n][n] from S (and N for denominator "pairs")."""
+    params = grm_params() if params is None else params
+    S = np.ascontiguousarray(products, dtype=np.float64)
+    n = S.shape[0]
+    N = None if pair_sites is None else np.ascontiguousarray(pair_sites, dtype=np.uint64)
+    if S.shape != (n, n) or (N is not None and N.shape != (n, n)):
+        raise ValueError("products and pair_sites are [n][n]")
+    A = np.empty((n, n), dtype=np.float64)
+    _abi.check(_abi.load().fmh_grm_finish(_ptr(S), _ptr(N), n, C.byref(params), int(n_usable), float(scale), _ptr(A)))
+    return A
+
+
+def grm_host(dosage, method: str = "standardized"):
+    """fmh_grm_host (host only): (S, N, n_usable, scale) from a [K][n] dosage table (0, 1, 2; above 2 = not called)."""
+    d = np.ascontiguousarray(dosage, dtype=np.uint8)
+    K, n = d.shape
+    S, N = np.empty((n, n), dtype=np.float64), np.empty((n, n), dtype=np.uint64)
+    n_usable, scale = C.c_uint64(0), C.c_double(0.0)
+    _abi.check(_abi.load().fmh_grm_host(_ptr(d), K, n, GRM_METHODS.index(method), _ptr(S), _ptr(N), C.byref(n_usable), C.byref(scale)))
+    return S, N, int(n_usable.value), float(scale.value)
+
+
+def grm_eigen(device: int, matrix, n_components: int):
+    """fmh_grm_eigen of a symmetric (n, n) array: (eigenvalues descending [n_components], unit eigenvectors [n][n_components], the component
+    of the largest magnitude positive)."""
+    a = np.ascontiguousarray(matrix, dtype=np.float64)
+    n = a.shape[0]
+    buf = DeviceBuffer.from_numpy(device, a)
+    values, vectors = np.empty(n_components, dtype=np.float64), np.empty((n, n_components), dtype=np.float64)
+    _abi.check(_abi.load().fmh_grm_eigen(device, buf.ptr, n, n_components, _ptr(values), _ptr(vectors)))
+    return values, vectors
+
+
 # ---- genotype QC: class counts per site and per sample, HWE exact test -----------------------------------------------------------------
 QC_DEFAULT_ITEM_ROWS = 4096   # FMH_QC_ITEM_ROWS unset
 QC_CLASSES = ("hom_ref", "het", "hom_alt")

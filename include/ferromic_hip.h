@@ -1172,6 +1172,80 @@ int fmh_clump_host(const uint8_t* h_dosage /* [K][n] */, const uint32_t* h_x_or_
                    const fmh_clump_params* params, uint32_t* h_index_of /* [K] */, double* h_r2_or_null /* [K] */,
                    uint64_t* h_n_clumps_or_null);   /* host only, no device */
 
+/* ---- genomic relationship matrix and genotype PCA (an addition: the reference's PCA is the haplotype PCA above) ---------------------------
+ * The per-sample link of the cohort chain QC -> fmh_ld_prune -> fmh_kinship_counts -> PCA -> association: the matrix GCTA --make-grm and
+ * PLINK --make-rel compute, and its top eigenvectors (PLINK --pca), the covariates of the association scans.
+ * Matrix, samples, `called` and dosage are fmh_genotype_counts': ploidy 2, a packed image, sample s owns columns 2s and 2s + 1; the genotype
+ * of s at row r is called iff both entries are called and both alleles are <= 1 (classes hom-ref, het, hom-alt, not called); the dosage is
+ * g in {0, 1, 2}.  Sample lists, row ranges and keep masks are fmh_kinship_counts', under the same rules.
+ *
+ * Over the kept rows k (in ascending row order) and the selected samples:
+ *   c_k = the number of called genotypes, a_k = the sum of their dosages (exact u32);  p_k = (double)a_k / (double)(2 * c_k), NaN where c_k = 0.
+ *   A kept row is USABLE iff c_k >= 1 and 0 < a_k < 2 c_k.  A row that is not usable contributes nothing; it is reported, never refused.
+ *   MAF and call-rate filters are the caller's (the keep mask).
+ *   Values of a usable row, the operation order fixed (the library is built with -ffp-contract=off; numpy reproduces the bits):
+ *     mean = 2.0 * p;  var = mean * (1.0 - p);  z(g) = (double)g - mean for g = 0, 1, 2
+ *     FMH_GRM_STANDARDIZED (GCTA, PLINK): z(g) = ((double)g - mean) / sqrt(var)
+ *     FMH_GRM_CENTERED (VanRaden 1): z(g) as above;  scale = the sum of var over the usable rows, ascending, from 0.0
+ *   A genotype that is not called has z = 0 (mean imputation), in both methods; a row that is not usable has z = (0, 0, 0).
+ *   S[i][j] = sum over the usable rows of z_k(g_ik) z_k(g_jk): with mean imputation this is GCTA's sum over the rows called in both.
+ *   N[i][j] = the number of usable rows called in both samples (u64).
+ *   A = S / (double)m_usable (standardized) or S / scale (centered) with denominator FMH_GRM_SITES; S[i][j] / (double)N[i][j], NaN where
+ *   N[i][j] = 0, with FMH_GRM_PAIRS (GCTA's), which takes FMH_GRM_STANDARDIZED only.  diag(A) - 1 is the per-sample inbreeding estimate.
+ *
+ * fmh_grm: out->d_products (f64 [n][n], device) is ADDED into - chromosomes held as separate matrices accumulate, as in kinship; the caller
+ *   zeroes it first and adds up *h_usable_rows and *h_scale, which are WRITTEN with this call's.  Both triangles are filled; what one call adds
+ *   is symmetric bit for bit and two runs give the same bits.  out->d_pair_sites (u64 [n][n], device, may be NULL; required with FMH_GRM_PAIRS)
+ *   is ADDED into: it is fmh_kinship_counts' `both` over the usable rows.  out->h_called, h_allele_count (u32) and h_usable (u8) are host arrays
+ *   of row_count entries (each may be NULL) whose first *h_kept_rows entries are written: c, a and the usable flag of the kept rows in row
+ *   order; they come from fmh_genotype_counts' site tracks.  No kept row or no usable row: FMH_OK, nothing is added.
+ *   How: the usable rows' 2-bit genotype codes go into a sample-major bit image (two planes, one u64 per 64 rows and sample), and S is a
+ *   Gram on v_mfma_f64_16x16x4_f64 whose operand is {z(0), z(1), z(2), 0}[code]; K is split over workgroups while there are few tiles
+ *   (FMH_GRM_SPLITS forces a count; 1 = none, 0 = by the tile count) and the partial tiles are added in split order.  Device memory from the
+ *   pool: n^2 * 8 (the call's products) + the image (2 planes * 8 bytes per 64 rows and padded sample) + 32 bytes per row + 128 KiB per
+ *   (tile, split) when K is split + 4 n^2 * 8 with d_pair_sites; the sum must stay within FMH_PCA_BUDGET_BYTES.  Neither option changes a
+ *   result beyond the order of the sum.  Enqueues on `stream` and synchronises it.
+ *   Refusals, all before any launch, in this order.  FMH_ERR_INVALID: NULL matrix; NULL params or out; d_products NULL; a method or
+ *   denominator that is not listed, or FMH_GRM_PAIRS with FMH_GRM_CENTERED or without d_pair_sites; n_samples == 0.  FMH_ERR_UNSUPPORTED:
+ *   ploidy != 2.  FMH_ERR_INVALID: a sample out of range or the list not strictly ascending; a row range past the matrix.
+ *   FMH_ERR_UNSUPPORTED, with a message: a matrix without a packed image (u8 rows only: call fmh_matrix_pack first); 2^32 - 1 rows or more
+ *   in the range, more than 2^24 samples; over budget.
+ * Host only (no device), bit for bit what the definition says:
+ *   fmh_grm_values: c, a of `rows` rows -> usable flags, p, z [rows][3], *scale, *n_usable (each output may be NULL).
+ *   fmh_grm_finish: S, N (NULL unless FMH_GRM_PAIRS), m_usable, scale -> A.
+ *   fmh_grm_host: the twin for CPU tests.  S [n][n] WRITTEN from a dosage table [K][n] (0, 1, 2; above 2 = not called): the counts, the
+ *     values, then every entry summed over ascending k in plain f64; N, *n_usable and *scale as well (each may be NULL).
+ * fmh_grm_eigen: the top n_components eigenpairs of the symmetric d_matrix [n][n] (device, OVERWRITTEN) through the solver of
+ *   fmh_pca_eigen_scores (FMH_PCA_EIGEN): h_eigenvalues descending, h_eigenvectors [n][n_components], column k the unit eigenvector of
+ *   h_eigenvalues[k], its component of the largest magnitude positive (on a tie the one of the lowest index).  FMH_ERR_INVALID: NULL argument,
+ *   n == 0, n_components outside 1..n; FMH_ERR_UNSUPPORTED: n > 46 340.
+ * Not built: sharding over devices (S is a plain sum over rows), run_vcf wiring, GCTA .grm.bin writers, dominance matrices, leave-one-
+ *   chromosome-out sets, the mixed-model scan itself, u8 rows.
+ */
+#define FMH_GRM_STANDARDIZED 0
+#define FMH_GRM_CENTERED 1
+#define FMH_GRM_SITES 0
+#define FMH_GRM_PAIRS 1
+typedef struct { uint32_t method, denominator; } fmh_grm_params;
+typedef struct {
+  double* d_products;                 /* [n][n], device, ADDED into */
+  unsigned long long* d_pair_sites;   /* [n][n], device, ADDED into; may be NULL unless FMH_GRM_PAIRS */
+  uint32_t *h_called, *h_allele_count; /* [row_count] host, the first *h_kept_rows written; may be NULL */
+  uint8_t* h_usable;                  /* likewise */
+  uint64_t* h_usable_rows;            /* written; may be NULL */
+  double* h_scale;                    /* written; may be NULL */
+} fmh_grm_out;
+int fmh_grm(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+            size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count], as fmh_ld_prune writes it */,
+            const fmh_grm_params* params, const fmh_grm_out* out, uint64_t* h_kept_rows /* may be NULL */, void* stream);
+int fmh_grm_values(const uint32_t* h_called, const uint32_t* h_allele_count, size_t rows, uint32_t method, uint8_t* h_usable, double* h_p,
+                   double* h_z /* [rows][3] */, double* h_scale, uint64_t* h_n_usable);   /* host only, no device */
+int fmh_grm_finish(const double* h_products, const uint64_t* h_pair_sites_or_null, size_t n, const fmh_grm_params* params, uint64_t n_usable,
+                   double scale, double* h_matrix);   /* host only, no device */
+int fmh_grm_host(const uint8_t* h_dosage /* [K][n] */, size_t K, size_t n, uint32_t method, double* h_products, uint64_t* h_pair_sites_or_null,
+                 uint64_t* h_n_usable, double* h_scale);   /* host only, no device */
+int fmh_grm_eigen(int device, double* d_matrix, size_t n, size_t n_components, double* h_eigenvalues, double* h_eigenvectors);
+
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
  * A group is a 0/1 column mask with n >= 1 members (fmh_groups); members are ranked 0 .. n-1 by ascending column.  A window is a row range
@@ -1450,6 +1524,9 @@ int fmh_timing_read_pca(double* h_stage_ms /*[6]*/);
  * summed over the call's row slabs: [0] the planes kernels, [1] the first Gram of a slab with its slab reduce (pairwise: all its Grams;
  * kinship: the stacked [H; V] or H operand), [2] the second Gram (kinship: W), [3] the finish kernel. */
 int fmh_timing_read_gram(double* h_stage_ms /*[4]*/);
+/* Stage times of the calling thread's last fmh_grm while timing was enabled, ms by HIP events: [0] the codes kernel (with the plane flags),
+ * [1] the Gram, [2] the slab reduce and the addition into the caller's matrix.  (Its eigen solver is fmh_timing_read_pca's [4].) */
+int fmh_timing_read_grm(double* h_stage_ms /*[3]*/);
 
 #ifdef __cplusplus
 }
