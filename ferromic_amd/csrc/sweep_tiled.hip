@@ -42,15 +42,33 @@ int launch_counted(const SweepArgs& a, hipStream_t st, const LaunchCtx& ctx, int
 }
 
 // the table form: every counted group from the prefix counts and its edge vectors (at least one group is counted)
+template <int P, int MODE, int C, int F, int HF>
+int launch_prefix_pair(const SweepArgs& args, hipStream_t st, const LaunchCtx& ctx, int* grid_out) {
+  auto kern = sweep_kernel_tiled_prefix<P, MODE, C, F, HF>;
+  static thread_local OccupancyCache cache;
+  int occ = 0;
+  FMH_TRY(cached_occupancy(kern, kBlock, 0, 8, false, cache, 0, &occ));
+  return timed_launch(kern, persistent_grid(occ, args.row_count, kWavesPerBlock, ctx), kBlock, 0, st, ctx, args, grid_out);
+}
+// The formula pair of the launch picks the instantiation: one per formula where the population totals and the Hudson part share it (every
+// sweep but the fused region sweep; only the Hudson part reads the second one), the region driver's two distinct pairs (dense or summary
+// totals over the sparse Hudson set), and one that reads any other distinct pair from the arguments.
 template <int P, int MODE, int C>
 int launch_prefix(const SweepArgs& args, hipStream_t st, const LaunchCtx& ctx, int* grid_out) {
   if constexpr (C < 1) return fail(FMH_ERR_INVALID, "the table form of the tiled route counts at least one group");
   else {
-    auto kern = sweep_kernel_tiled_prefix<P, MODE, C>;
-    static thread_local OccupancyCache cache;
-    int occ = 0;
-    FMH_TRY(cached_occupancy(kern, kBlock, 0, 8, false, cache, 0, &occ));
-    return timed_launch(kern, persistent_grid(occ, args.row_count, kWavesPerBlock, ctx), kBlock, 0, st, ctx, args, grid_out);
+    const int f = args.formula, hf = args.hudson_formula_p1 ? args.hudson_formula_p1 - 1 : args.formula;
+    if ((MODE & kModeHudson) == 0 || hf == f) {
+      if (f == kFormulaSparse) return launch_prefix_pair<P, MODE, C, kFormulaSparse, kFormulaSparse>(args, st, ctx, grid_out);
+      if (f == kFormulaDense) return launch_prefix_pair<P, MODE, C, kFormulaDense, kFormulaDense>(args, st, ctx, grid_out);
+      if (f == kFormulaSummary) return launch_prefix_pair<P, MODE, C, kFormulaSummary, kFormulaSummary>(args, st, ctx, grid_out);
+      return fail(FMH_ERR_INVALID, "unknown formula %d", f);
+    }
+    if constexpr ((MODE & kModeHudson) != 0 && (MODE & kModeDiversity) != 0) {
+      if (f == kFormulaDense && hf == kFormulaSparse) return launch_prefix_pair<P, MODE, C, kFormulaDense, kFormulaSparse>(args, st, ctx, grid_out);
+      if (f == kFormulaSummary && hf == kFormulaSparse) return launch_prefix_pair<P, MODE, C, kFormulaSummary, kFormulaSparse>(args, st, ctx, grid_out);
+      return launch_prefix_pair<P, MODE, C, kFormulaRuntime, kFormulaRuntime>(args, st, ctx, grid_out);
+    } else return fail(FMH_ERR_INVALID, "only the fused region sweep takes a Hudson formula of its own");
   }
 }
 template <int P, int MODE>
@@ -67,6 +85,11 @@ int launch_sweep_tiled(int P, int mode, const SweepArgs& a, hipStream_t st, cons
   if (a.prefix) {  // a.mv.data = the whole image, a.prefix_group = the counted group(s): enqueue_sweep filled them from the plan
     const uint32_t pvec = (uint32_t)(a.mv.pitch / 16);
     if (a.derived_group >= P || (a.derived_group >= 0 && !a.row_alt)) return fail(FMH_ERR_INVALID, "the tiled route takes a derived group with its row totals");
+    // the epilogue of the table form works in 32 bits (site_const_epilogue.hpp): n^2 and n1 n2 below 2^32.  The table's own eligibility (u16 entries)
+    // already implies it, so no plan reaches this refusal.
+    if (a.mv.columns > kConstEpilogueMaxColumns) return fail(FMH_ERR_INVALID, "the table form of the tiled route takes at most %u columns", kConstEpilogueMaxColumns);
+    for (int p = 0; p < P; ++p)
+      if (a.group_size[p] > kConstEpilogueMaxColumns) return fail(FMH_ERR_INVALID, "the table form of the tiled route takes groups of at most %u columns", kConstEpilogueMaxColumns);
     for (int q = 0; q < P - (a.derived_group >= 0 ? 1 : 0); ++q) {
       const PrefixGroup& g = a.prefix_group[q];
       if (g.b_lo > g.b_hi || g.b_hi > pvec || g.n_edges > 2 || (g.n_edges > 0 && g.edge_vec[0] >= pvec) || (g.n_edges > 1 && g.edge_vec[1] >= pvec))

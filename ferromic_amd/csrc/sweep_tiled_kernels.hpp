@@ -16,6 +16,7 @@
 //     order of every f64 sum is the four-lane route's at the same grid.
 #pragma once
 
+#include "site_const_epilogue.hpp"
 #include "sweep_kernels.hpp"
 
 namespace fmh {
@@ -159,16 +160,20 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel_tiled(const SweepArgs A) 
 // (A.prefix: for image tile T, boundary b and row slot s the u16 at ((T * (pvec + 1) + b) * 64 + s) - 128 contiguous bytes per wave
 // instruction) and only the at most two vectors the range shares with other columns are read from the image and counted, under masks that
 // arrive as kernel arguments.  A group with no whole vector loads no entry, one with no shared vector loads no vector (all wave-uniform).
-// Tile -> wave -> lane, the clamp of the rows past the end, derive_group, finish_biallelic_site, site_epilogue, the stores and
-// reduce_block_totals are sweep_kernel_tiled's: the same integers reach the same f64 operations in the same order.  The next tile's loads
+// Tile -> wave -> lane, the clamp of the rows past the end, derive_group, the stores and reduce_block_totals are sweep_kernel_tiled's.  The
+// epilogue is site_const_epilogue (site_const_epilogue.hpp): every called count of this form is a launch constant, so
+// the divisions of finish_biallelic_site + site_epilogue by them share their reciprocals - the same integers reach the same f64 operations in
+// the same order and give the same bits.  F / HF: the launch's formula pair, resolved by the launcher (kFormulaRuntime = read from the arguments
+// inside the loop), so a built pair has no branch on the formula in its tile loop and registers for its own arms only.  The next tile's loads
 // are issued before this tile's epilogue and land under it.
-template <int P, int MODE, int C>
+template <int P, int MODE, int C, int F, int HF>
 __global__ __launch_bounds__(kBlock) void sweep_kernel_tiled_prefix(const SweepArgs A) {
   static_assert(P <= 2 && C <= P && C >= P - 1 && C >= 1 && (MODE & kModeWc) == 0, "one or two groups, at most one of them derived, not W&C");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   LaneTotals<P, MODE> T;
   T.clear();
+  const double* K0 = const_epilogue_init<P, MODE>(A);  // the launch constants of the epilogue, in LDS (ends in a barrier)
   const size_t ntiles = (A.row_count + kTileRows - 1) / kTileRows;
   const size_t tile_stride = (size_t)gridDim.x * kWavesPerBlock;
   size_t tile = (size_t)blockIdx.x * kWavesPerBlock + (size_t)wave;
@@ -223,15 +228,13 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel_tiled_prefix(const SweepA
         for (int p = 0; p < P; ++p) alt_mine[p] = p == cg ? cnt[0] : 0u;
       }
       derive_group<P>(A.derived_group, row_alt, alt_mine);
-      SiteTally<P> mine;
-      WcSite<P> wc;
-      double hud_dot = 0.0;
-#pragma unroll
-      for (int p = 0; p < P; ++p) { mine.n[p] = A.group_size[p]; mine.alt[p] = alt_mine[p]; mine.distinct[p] = 0; mine.ssq[p] = 0; }
-      mine.n_all = A.mv.columns;
-      finish_biallelic_site<P, MODE>(mine, hud_dot);
+      // (an opaque zero offset per tile: the constants are read from LDS where a site uses them - ds_read_b64 of a wave-uniform address, no VALU
+      // slot - instead of being hoisted out of the tile loop into up to 44 VGPRs, which cost the Hudson kernels a wave per SIMD)
+      uint32_t ko = 0;
+      asm volatile("" : "+v"(ko));
+      const double* K = K0 + ko;
       const size_t my_rel = tile * kTileRows + (size_t)lane;
-      site_epilogue<P, MODE, false, false>(A, my_rel, my_rel < A.row_count, mine, hud_dot, wc, T);
+      site_const_epilogue<P, MODE, F, HF>(A, K, my_rel, my_rel < A.row_count, alt_mine, T);
     }
   }
   reduce_block_totals<P, MODE>(A, T);

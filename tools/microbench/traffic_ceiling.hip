@@ -10,6 +10,9 @@
 //   plus one 4-byte row total per site, the tracks as above; the row pitch is unchanged, so the reads are `count * 16` bytes at a stride of `pitch`.
 //   CEILING_TILED=first:count   the same window of a tile-transposed image: the 64 rows of a tile share the lines of one vector
 //   column, so per tile the reads are `count` contiguous KiB out of every `pitch / 16` KiB, one coalesced 16-byte-per-lane load each; row totals and tracks as above.
+//   CEILING_PREFIX=boundary:edge   the traffic of the table form (sweep_kernel_tiled_prefix, DESIGN.md sections 3.5d / 3.5e): per tile one 128-byte line
+//   of u16 prefix counts (boundary `boundary` of pitch / 16 + 1), the 1-KiB wave load of vector `edge` of the tile-transposed image and 256 B of row
+//   totals; the next tile's loads are issued before this tile's stores, as the kernel issues them; tracks as above.
 // Build: hipcc --offload-arch=gfx950 -O3 -o traffic_ceiling traffic_ceiling.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -130,6 +133,60 @@ void run_window(const uint8_t* data, size_t rows, size_t pitch, int v0, const ui
   }
 }
 
+// The table form's traffic: a u16 prefix count, one edge vector and a row total per lane and tile, loaded one tile ahead of the stores.
+__global__ __launch_bounds__(256) void prefix_kernel(const uint8_t* __restrict__ image, const uint16_t* __restrict__ prefix, const uint32_t* __restrict__ row_total, size_t rows,
+                                                     size_t pvec, int boundary, int edge, int n_f64, int n_u32, double* __restrict__ o64, uint32_t* __restrict__ o32,
+                                                     unsigned long long* __restrict__ sink) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t ntiles = rows / 64;
+  const size_t nwaves = (size_t)gridDim.x * 4;
+  size_t tile = (size_t)blockIdx.x * 4 + wave;
+  unsigned acc = 0;
+  if (tile < ntiles) {
+    uint32_t total, count;
+    uint4 x;
+    auto load = [&](size_t t) {
+      total = row_total[t * 64 + lane];
+      count = prefix[(t * (pvec + 1) + (size_t)boundary) * 64 + lane];
+      x = *reinterpret_cast<const uint4*>(image + (t * pvec + (size_t)edge) * 1024 + (size_t)lane * 16);
+    };
+    load(tile);
+    for (; tile < ntiles; tile += nwaves) {
+      acc += total + count + (x.x ^ x.y ^ x.z ^ x.w);
+      load(tile + nwaves < ntiles ? tile + nwaves : tile);  // the next tile's loads go out before this tile's stores
+      const size_t site = tile * 64 + lane;
+      for (int k = 0; k < n_u32; ++k) __builtin_nontemporal_store(acc, o32 + (size_t)k * rows + site);
+      for (int k = 0; k < n_f64; ++k) __builtin_nontemporal_store((double)acc, o64 + (size_t)k * rows + site);
+    }
+  }
+  if (acc == 0xFFFFFFFFu) sink[0] = acc;
+}
+
+void run_prefix(const uint8_t* image, const uint16_t* prefix, const uint32_t* row_total, size_t rows, size_t pvec, int boundary, int edge, int n_f64, int n_u32,
+                double* o64, uint32_t* o32, unsigned long long* sink, int cus, int argc, char** argv) {
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  const double bytes = (double)rows * (2 + 16 + 4 + 8.0 * n_f64 + 4.0 * n_u32);
+  for (int a = 6; a < argc || a == 6; ++a) {
+    const int per_cu = a < argc ? atoi(argv[a]) : 4;
+    float best = 1e9f, sum = 0.f;
+    for (int rep = 0; rep < 30; ++rep) {
+      CHECK(hipEventRecord(e0));
+      hipLaunchKernelGGL(prefix_kernel, dim3(cus * per_cu), dim3(256), 0, 0, image, prefix, row_total, rows, pvec, boundary, edge, n_f64, n_u32, o64, o32, sink);
+      CHECK(hipEventRecord(e1));
+      CHECK(hipEventSynchronize(e1));
+      float ms;
+      CHECK(hipEventElapsedTime(&ms, e0, e1));
+      if (rep >= 10) { sum += ms; if (ms < best) best = ms; }
+    }
+    printf("{\"mode\": \"prefix line+edge vector+total+tracks, loads one tile ahead\", \"rows\": %zu, \"pvec\": %zu, \"boundary\": %d, \"edge_vec\": %d, \"f64_tracks\": %d, "
+           "\"u32_tracks\": %d, \"workgroups_per_cu\": %d, \"best_ms\": %.4f, \"mean_ms\": %.4f, \"GBs\": %.0f, \"frac_of_8TBs\": %.3f}\n",
+           rows, pvec, boundary, edge, n_f64, n_u32, per_cu, best, sum / 20.f, bytes / best / 1e6, bytes / best / 1e6 / 8000.0);
+    fflush(stdout);
+  }
+}
+
 // Phase-aligned deferral: every wave of the chip looks at the same constant-rate clock (s_memrealtime, 100 MHz) and keeps reading tiles (parking
 // their results) until that clock enters the write window of the current period, then writes everything it has parked - so that, without any
 // barrier, most of the chip reads at the same time and writes at the same time.  period = 8 << shift ticks of 10 ns, write window = wnum / 8 of it.
@@ -237,6 +294,19 @@ int main(int argc, char** argv) {
   hipDeviceProp_t prop;
   CHECK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount;
+  if (const char* pf = getenv("CEILING_PREFIX")) {
+    const size_t pvec = pitch / 16;
+    int boundary = 0, edge = 0;
+    if (sscanf(pf, "%d:%d", &boundary, &edge) != 2 || boundary < 0 || (size_t)boundary > pvec || edge < 0 || (size_t)edge >= pvec) { printf("CEILING_PREFIX=boundary:edge must lie inside the row\n"); return 1; }
+    uint16_t* prefix;
+    uint32_t* row_total;
+    CHECK(hipMalloc(&prefix, rows * (pvec + 1) * 2));
+    CHECK(hipMemset(prefix, 0, rows * (pvec + 1) * 2));
+    CHECK(hipMalloc(&row_total, rows * 4));
+    CHECK(hipMemset(row_total, 0, rows * 4));
+    run_prefix(data, prefix, row_total, rows, pvec, boundary, edge, n_f64, n_u32, o64, o32, sink, cus, argc, argv);
+    return 0;
+  }
   const char* tiled = getenv("CEILING_TILED");
   if (const char* w = tiled ? tiled : getenv("CEILING_WINDOW")) {
     int v0 = 0, wv = 0;
