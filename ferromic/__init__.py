@@ -29,6 +29,7 @@ from ._core import (  # noqa: E402,F401
     JointSiteFrequencySpectrum,
     Kinship,
     LogisticScan,
+    MixedModelScan,
     PairwiseDifference,
     PolygenicScore,
     Population,
@@ -59,6 +60,7 @@ from ._core import (  # noqa: E402,F401
     ld_prune,
     ld_r2,
     logistic_scan,
+    mixed_model_scan,
     nsl,
     nucleotide_diversity,
     pairwise_differences,

@@ -186,6 +186,11 @@ class GrmOut(C.Structure):
                 ("h_usable", C.c_void_p), ("h_usable_rows", C.POINTER(C.c_uint64)), ("h_scale", C.POINTER(C.c_double))]
 
 
+class LmmNullOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("h_delta", "h_sigma_g2", "h_sigma_e2", "h_heritability", "h_log_likelihood", "h_at_boundary", "h_reason",
+                                                "h_weights", "h_linear", "h_m", "h_v", "h_r", "h_grid_log_likelihood_or_null")]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -318,6 +323,10 @@ SYMBOLS = {
     "fmh_grm_finish": (_i, [_vp, _vp, _sz, _P(GrmParams), _u64, _d, _vp]),
     "fmh_grm_host": (_i, [_vp, _sz, _sz, _u32, _vp, _vp, _P(_u64), _P(_d)]),
     "fmh_grm_eigen": (_i, [_i, _vp, _sz, _sz, _vp, _vp]),
+    "fmh_lmm_projections": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "fmh_lmm_projections_host": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmh_lmm_null": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _P(_sz), _vp, _P(LmmNullOut)]),
+    "fmh_lmm_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _u64, _sz, _sz, _vp, _vp, _vp, _vp]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),

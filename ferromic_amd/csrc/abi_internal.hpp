@@ -93,6 +93,7 @@ struct Options {
   std::atomic<long long> fstat_lds_mask_bytes{0};  // FMH_FSTAT_LDS_MASK_BYTES: LDS bytes that kernel's mask entries may take; 0 = 8 192 (eight workgroups per CU stay resident); entries that need more are read from global memory (1 forces that)
   std::atomic<long long> kin_budget_bytes{(long long)16 << 30};  // FMH_KIN_BUDGET_BYTES: the Gram scratch one fmh_kinship_counts call may take
   std::atomic<long long> qc_item_rows{0};        // FMH_QC_ITEM_ROWS: rows per work item of the genotype QC kernels; 0 = 4 096
+  std::atomic<long long> lmm_item_rows{0};       // FMH_LMM_ITEM_ROWS: the most rows per work item of the mixed-model projections; 0 = 4 096, fewer on short ranges
   std::atomic<long long> assoc_item_rows{0};     // FMH_ASSOC_ITEM_ROWS: rows per work item of the association scans' sums kernels; 0 = 4 096 (DESIGN.md sections 3.18, 3.19)
   std::atomic<long long> assoc_budget_bytes{(long long)1 << 30};  // FMH_ASSOC_BUDGET_BYTES: device bytes the sums of one row chunk of ferromic.association_scan / logistic_scan may take
   std::atomic<long long> score_item_rows{0};     // FMH_SCORE_ITEM_ROWS: rows per work item of the polygenic score's sums kernel, rounded up to a multiple of 64; 0 = 4 096

@@ -116,52 +116,6 @@ extern "C" int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_
 }
 
 // ---- host only (no device).  The operation order is the header's; the unit is built with -ffp-contract=off ----------------------------------
-namespace {
-
-// the continued fraction of the incomplete beta function (modified Lentz), to a relative change below 1e-15
-double beta_cf(double a, double b, double x) {
-  const double tiny = 1e-300;
-  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
-  double c = 1.0, d = 1.0 - qab * x / qap;
-  if (std::fabs(d) < tiny) d = tiny;
-  d = 1.0 / d;
-  double h = d;
-  for (int m = 1; m <= 10000; ++m) {
-    const double dm = (double)m, m2 = 2.0 * dm;
-    double aa = dm * (b - dm) * x / ((qam + m2) * (a + m2));
-    d = 1.0 + aa * d;
-    if (std::fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (std::fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    h = h * (d * c);
-    aa = -(a + dm) * (qab + dm) * x / ((a + m2) * (qap + m2));
-    d = 1.0 + aa * d;
-    if (std::fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (std::fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    const double del = d * c;
-    h = h * del;
-    if (std::fabs(del - 1.0) < 1e-15) break;
-  }
-  return h;
-}
-
-// two-sided tail of Student's t: I_x(df / 2, 1 / 2) at x = df / (df + t^2)
-double student_t_two_sided(double t, double df) {
-  const double t2 = t * t;
-  if (t2 == 0.0) return 1.0;
-  const double x = df / (df + t2), xc = t2 / (df + t2);  // xc = 1 - x without the cancellation
-  if (x == 0.0) return 0.0;
-  const double a = df / 2.0, b = 0.5;
-  const double front = std::exp(std::lgamma(a + b) - std::lgamma(a) - std::lgamma(b) + a * std::log(x) + b * std::log(xc));
-  if (x < (a + 1.0) / (a + b + 2.0)) return front * beta_cf(a, b, x) / a;
-  return 1.0 - front * beta_cf(b, a, xc) / b;
-}
-
-}  // namespace
-
 extern "C" int fmh_assoc_prepare(const double* h_phenotypes, const double* h_covariates_or_null, size_t n, size_t n_phenotypes, size_t n_covariates,
                                  int32_t* h_values, int32_t* h_exponent, long long* h_total, double* h_yy, size_t* h_n_basis,
                                  uint8_t* h_dropped_or_null) {

@@ -1,5 +1,6 @@
 // assoc_host.hpp — the host arithmetic fmh_assoc_prepare (assoc.hip) and fmh_logistic_null (logistic_host.hpp) share: sequential sums,
-// centring, the twice-over modified Gram-Schmidt, the covariate basis with its drop rule, and the fixed-point exponent.  The operation order
+// centring, the twice-over modified Gram-Schmidt, the covariate basis with its drop rule, the fixed-point exponent, and the Student-t tail
+// of fmh_assoc_stats, which the mixed-model scan (lmm_host.hpp) shares with the covariate basis.  The operation order
 // is include/ferromic_hip.h's (association scan, host preparation, steps 1, 2 and 4); every unit that includes this is built with
 // -ffp-contract=off.  Plain C++: no HIP, no library state, so that a stand-alone program can run it under a sanitizer.
 #pragma once
@@ -86,5 +87,49 @@ inline void quantise_column(const double* col, size_t n, int32_t* values, size_t
   *exponent = e;
   *total = t;
 }
+
+// ---- the two-sided tail of Student's t: fmh_assoc_stats' p, which the mixed-model statistics (lmm_host.hpp) report with the same bits ----
+// the continued fraction of the incomplete beta function (modified Lentz), to a relative change below 1e-15
+inline double beta_cf(double a, double b, double x) {
+  const double tiny = 1e-300;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (std::fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= 10000; ++m) {
+    const double dm = (double)m, m2 = 2.0 * dm;
+    double aa = dm * (b - dm) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h = h * (d * c);
+    aa = -(a + dm) * (qab + dm) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h = h * del;
+    if (std::fabs(del - 1.0) < 1e-15) break;
+  }
+  return h;
+}
+
+// two-sided tail of Student's t: I_x(df / 2, 1 / 2) at x = df / (df + t^2)
+inline double student_t_two_sided(double t, double df) {
+  const double t2 = t * t;
+  if (t2 == 0.0) return 1.0;
+  const double x = df / (df + t2), xc = t2 / (df + t2);  // xc = 1 - x without the cancellation
+  if (x == 0.0) return 0.0;
+  const double a = df / 2.0, b = 0.5;
+  const double front = std::exp(std::lgamma(a + b) - std::lgamma(a) - std::lgamma(b) + a * std::log(x) + b * std::log(xc));
+  if (x < (a + 1.0) / (a + b + 2.0)) return front * beta_cf(a, b, x) / a;
+  return 1.0 - front * beta_cf(b, a, xc) / b;
+}
+
 
 }  // namespace fmh_host

@@ -22,6 +22,7 @@ struct GeneticRelationship {
   uint64_t n_usable = 0;
   double scale = 0.0;
   int device = 0;
+  mutable vector<double> eigen_values, eigen_vectors;  // every eigenpair of A ([n], [n][n]), computed when first asked (eigen())
 
   size_t n() const { return samples.size(); }
   template <class T> py::array_t<T> square(const vector<T>& v) const {
@@ -55,6 +56,26 @@ struct GeneticRelationship {
     for (size_t i = 0; i < n(); ++i) trace += matrix[i * n() + i];
     for (double v : out.eigenvalues) out.explained.push_back(v / trace);
     return out;
+  }
+  // every eigenpair of A through fmh_grm_eigen, descending: what the mixed-model scan rotates by.  Computed once and kept.
+  void eigen_pairs(vector<double>& values, vector<double>& vectors) const {
+    if (eigen_values.empty()) {
+      for (double v : matrix)
+        if (v != v) value_error("the relationship matrix holds a NaN: with denominator=\"pairs\" a pair of samples without a jointly called usable site has no value");
+      vector<double> w(n(), 0.0), u(n() * n(), 0.0);
+      int status;
+      {
+        DevBuf d(device, matrix.size() * sizeof(double));
+        py::gil_scoped_release nogil;
+        status = fmh_copy_to_device(device, d.p, matrix.data(), matrix.size() * sizeof(double), nullptr);
+        if (status == FMH_OK) status = fmh_grm_eigen(device, (double*)d.p, n(), n(), w.data(), u.data());
+      }
+      fmh_check(status);
+      eigen_values = std::move(w);
+      eigen_vectors = std::move(u);
+    }
+    values = eigen_values;
+    vectors = eigen_vectors;
   }
   string repr() const {
     return "GeneticRelationship(samples=" + std::to_string(n()) + ", sites=" + std::to_string(sites.size()) + ", usable=" + std::to_string(n_usable) + ")";
@@ -178,6 +199,11 @@ template <class Class> void bind_grm(py::module_& m, Class& population) {
       .def_property_readonly("scale", [](const GeneticRelationship& g) { return g.scale; })
       .def("inbreeding", &GeneticRelationship::inbreeding)
       .def("pca", &GeneticRelationship::pca, py::arg("n_components") = 10)
+      .def("eigen", [](const GeneticRelationship& g) {
+        vector<double> values, vectors;
+        g.eigen_pairs(values, vectors);
+        return py::make_tuple(array_of(values), g.square(vectors));
+      })
       .def("__repr__", &GeneticRelationship::repr);
   m.def("grm", &grm, py::arg("variants"), py::arg("samples") = py::none(), py::arg("sites") = py::none(), py::arg("region") = py::none(),
         py::arg("method") = "standardized", py::arg("denominator") = "sites");

@@ -799,6 +799,119 @@ def grm_eigen(device: int, matrix, n_components: int):
     return values, vectors
 
 
+# ---- mixed-model association scan ----------------------------------------------------------------------------------------------------------
+LMM_DEFAULT_ITEM_ROWS = 4096   # FMH_LMM_ITEM_ROWS unset: at most
+LMM_GRID_POINTS = 101
+
+
+@dataclass
+class LmmProjections:
+    quad: np.ndarray           # [rows][P] float64
+    lin: np.ndarray            # [rows][L] float64
+    called: np.ndarray         # c, a per row, uint32
+    allele_count: np.ndarray
+
+
+def lmm_projections(m: DeviceMatrix, basis, weights, linear, samples=None, n_samples: Optional[int] = None, row_begin: int = 0,
+                    row_count: Optional[int] = None, stream=None, fill: Optional[float] = None) -> LmmProjections:
+    """fmh_lmm_projections over rows [row_begin, row_begin + row_count) for the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all).  basis [n][K], weights [P][K], linear [L][K] float64.  `fill` pre-fills the outputs (tests: every entry is written)."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    basis, weights, linear = (np.ascontiguousarray(a, dtype=np.float64) for a in (basis, weights, linear))
+    if basis.ndim != 2 or weights.ndim != 2 or linear.ndim != 2 or weights.shape[1] != basis.shape[1] or linear.shape[1] != basis.shape[1]:
+        raise ValueError("basis is [n][K], weights [P][K], linear [L][K]")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if basis.shape[0] != n:
+        raise ValueError("basis has one row per selected sample")
+    K, P, L = basis.shape[1], weights.shape[0], linear.shape[0]
+    bufs = [DeviceBuffer.from_numpy(m.device, a) for a in (basis, weights, linear)]
+    start = np.zeros(max(rows, 1) * (P + L), dtype=np.float64) if fill is None else np.full(max(rows, 1) * (P + L), fill, dtype=np.float64)
+    d_quad = DeviceBuffer.from_numpy(m.device, start[: max(rows, 1) * P])
+    d_lin = DeviceBuffer.from_numpy(m.device, start[: max(rows, 1) * L])
+    called, allele_count = np.zeros(max(rows, 1), np.uint32), np.zeros(max(rows, 1), np.uint32)
+    _abi.check(_abi.load().fmh_lmm_projections(m._h, _ptr(samples), n, row_begin, rows, bufs[0].ptr, K, bufs[1].ptr, P, bufs[2].ptr, L, d_quad.ptr, d_lin.ptr,
+                                               _ptr(called), _ptr(allele_count), stream))
+    return LmmProjections(d_quad.to_numpy(np.float64, rows * P).reshape(rows, P), d_lin.to_numpy(np.float64, rows * L).reshape(rows, L), called[:rows],
+                          allele_count[:rows])
+
+
+def lmm_projections_host(dosage, basis, weights, linear) -> LmmProjections:
+    """fmh_lmm_projections_host (host only): the twin over a [rows][n] dosage table (0, 1, 2; above 2 = not called)."""
+    d = np.ascontiguousarray(dosage, dtype=np.uint8)
+    basis, weights, linear = (np.ascontiguousarray(a, dtype=np.float64) for a in (basis, weights, linear))
+    rows, n = d.shape
+    K, P, L = basis.shape[1], weights.shape[0], linear.shape[0]
+    quad, lin = np.empty((rows, P), dtype=np.float64), np.empty((rows, L), dtype=np.float64)
+    called, allele_count = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32)
+    _abi.check(_abi.load().fmh_lmm_projections_host(_ptr(d), rows, n, _ptr(basis), K, _ptr(weights), P, _ptr(linear), L, _ptr(quad), _ptr(lin), _ptr(called),
+                                                    _ptr(allele_count)))
+    return LmmProjections(quad, lin, called, allele_count)
+
+
+@dataclass
+class LmmNull:
+    q: int
+    dropped: np.ndarray        # [c_in] bool
+    delta: np.ndarray          # [P]
+    sigma_g2: np.ndarray
+    sigma_e2: np.ndarray
+    heritability: np.ndarray
+    log_likelihood: np.ndarray
+    at_boundary: np.ndarray    # [P] bool
+    reason: np.ndarray         # [P] uint8
+    weights: np.ndarray        # [P][n]
+    linear: np.ndarray         # [P * (q + 1)][n]
+    M: np.ndarray              # [P][q][q]
+    v: np.ndarray              # [P][q]
+    R: np.ndarray              # [P]
+    grid_log_likelihood: np.ndarray  # [P][101]
+
+
+def lmm_null(eigenvalues, eigenvectors, phenotypes, covariates=None, fixed_delta=None) -> LmmNull:
+    """fmh_lmm_null (host only): the null fit per phenotype; `fixed_delta` [P] skips the search."""
+    lam = np.ascontiguousarray(eigenvalues, dtype=np.float64)
+    U = np.ascontiguousarray(eigenvectors, dtype=np.float64)
+    y = np.ascontiguousarray(phenotypes, dtype=np.float64)
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    n, P = y.shape
+    if lam.shape != (n,) or U.shape != (n, n):
+        raise ValueError("eigenvalues are [n], eigenvectors [n][n], phenotypes [n][P]")
+    cov = None if covariates is None else np.ascontiguousarray(covariates, dtype=np.float64).reshape(n, -1)
+    cin = 0 if cov is None else cov.shape[1]
+    fixed = None if fixed_delta is None else np.ascontiguousarray(fixed_delta, dtype=np.float64).reshape(P)
+    qmax = cin + 1
+    f = lambda *shape: np.zeros(shape, dtype=np.float64)
+    delta, sg, se, h2, ll, R = f(P), f(P), f(P), f(P), f(P), f(P)
+    boundary, reason, dropped = np.zeros(P, np.uint8), np.zeros(P, np.uint8), np.zeros(max(cin, 1), np.uint8)
+    weights, linear, M, v, grid = f(P * n), f(P * (qmax + 1) * n), f(P * qmax * qmax), f(P * qmax), f(P, LMM_GRID_POINTS)
+    out = _abi.LmmNullOut(*(a.ctypes.data for a in (delta, sg, se, h2, ll, boundary, reason, weights, linear, M, v, R, grid)))
+    q = C.c_size_t(0)
+    _abi.check(_abi.load().fmh_lmm_null(_ptr(lam), _ptr(U), _ptr(y), _ptr(cov), n, P, cin, _ptr(fixed), C.byref(q), _ptr(dropped), C.byref(out)))
+    q = int(q.value)
+    return LmmNull(q, dropped[:cin].astype(bool), delta, sg, se, h2, ll, boundary.astype(bool), reason, weights.reshape(P, n),
+                   linear[: P * (q + 1) * n].reshape(P * (q + 1), n), M[: P * q * q].reshape(P, q, q), v[: P * q].reshape(P, q), R, grid)
+
+
+def lmm_stats(quad, lin, called, allele_count, M, v, R, n_samples: int):
+    """fmh_lmm_stats (host only): dict(beta, se, t, p) [rows][P] from the projections and the null fit's M [P][q][q], v [P][q], R [P]."""
+    quad, lin = np.ascontiguousarray(quad, dtype=np.float64), np.ascontiguousarray(lin, dtype=np.float64)
+    M, v, R = (np.ascontiguousarray(a, dtype=np.float64) for a in (M, v, R))
+    c, a = np.ascontiguousarray(called, dtype=np.uint32), np.ascontiguousarray(allele_count, dtype=np.uint32)
+    rows, P = quad.shape
+    q = v.shape[1]
+    if lin.shape != (rows, P * (q + 1)) or M.shape != (P, q, q) or R.shape != (P,) or c.shape != (rows,) or a.shape != (rows,):
+        raise ValueError("quad is [rows][P], lin [rows][P (q + 1)], M [P][q][q], v [P][q], R [P]")
+    out = {k: np.empty((rows, P), dtype=np.float64) for k in ("beta", "se", "t", "p")}
+    _abi.check(_abi.load().fmh_lmm_stats(_ptr(quad), _ptr(lin), _ptr(c), _ptr(a), rows, _ptr(M), _ptr(v), _ptr(R), int(n_samples), q, P, _ptr(out["beta"]),
+                                         _ptr(out["se"]), _ptr(out["t"]), _ptr(out["p"])))
+    return out
+
+
 # ---- genotype QC: class counts per site and per sample, HWE exact test -----------------------------------------------------------------
 QC_DEFAULT_ITEM_ROWS = 4096   # FMH_QC_ITEM_ROWS unset
 QC_CLASSES = ("hom_ref", "het", "hom_alt")

@@ -82,7 +82,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
  *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES   FMH_SCORE_ITEM_ROWS   FMH_SCORE_BUDGET_BYTES
- *   FMH_ROH_ITEM_ROWS   FMH_IBD_ITEM_ROWS   FMH_IBD_BUDGET_BYTES
+ *   FMH_ROH_ITEM_ROWS   FMH_IBD_ITEM_ROWS   FMH_IBD_BUDGET_BYTES   FMH_LMM_ITEM_ROWS
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -787,7 +787,7 @@ int fmh_genotype_sample_stats(const uint64_t* h_hom_ref, const uint64_t* h_het, 
  *     cf the continued fraction by the modified Lentz method (floor 1e-300), iterated until a step changes it by less than 1e-15 relative.
  *   Outputs beta, se, t, p: f64 [rows][P]; each may be NULL.  Refusals (FMH_ERR_INVALID): P == 0; c + P > 64; n > 2^22 or n - c - 2 < 1; a
  *   NULL input with n_rows > 0.  n_rows == 0 is FMH_OK.
- * Not built: per-phenotype missing values (a NaN is refused), mixed models, dominant / recessive coding, sharding over devices (a caller
+ * Not built: per-phenotype missing values (a NaN is refused), dominant / recessive coding, sharding over devices (a caller
  *   splits rows), run_vcf wiring, u8 rows, more than 64 value columns per call.  Case / control phenotypes: the next section.
  */
 int fmh_assoc_sums(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
@@ -880,8 +880,9 @@ int fmh_assoc_stats(const long long* h_dosage_sum, const long long* h_called_sum
  *   p is the upper tail of chi-square with one degree of freedom.  beta and se are the ONE-STEP, score-based estimates of the log odds ratio
  *   per allele (the first Newton step from the null), not a Wald fit: they agree with it for small effects only.  All five are a quiet NaN
  *   where Vr is not > 0 or an input is NaN.  Each output pointer may be NULL; count == 0 is FMH_OK; a NULL input FMH_ERR_INVALID.
- * Not built: Wald and Firth estimates, the saddle-point correction for unbalanced case / control, per-phenotype missing values, mixed
- *   models, sharding over devices (a caller splits rows), run_vcf wiring, u8 rows.
+ * Not built: Wald and Firth estimates, the saddle-point correction for unbalanced case / control, per-phenotype missing values,
+ *   sharding over devices (a caller splits rows), run_vcf wiring, u8 rows.  (The random effect of the relationship matrix is for
+ *   quantitative phenotypes: the mixed-model scan below; a logistic mixed model is not built.)
  */
 #define FMH_LOGISTIC_FITTED 0
 #define FMH_LOGISTIC_ONE_CLASS 1      /* no case or no control */
@@ -1220,7 +1221,7 @@ int fmh_clump_host(const uint8_t* h_dosage /* [K][n] */, const uint32_t* h_x_or_
  *   h_eigenvalues[k], its component of the largest magnitude positive (on a tie the one of the lowest index).  FMH_ERR_INVALID: NULL argument,
  *   n == 0, n_components outside 1..n; FMH_ERR_UNSUPPORTED: n > 46 340.
  * Not built: sharding over devices (S is a plain sum over rows), run_vcf wiring, GCTA .grm.bin writers, dominance matrices, leave-one-
- *   chromosome-out sets, the mixed-model scan itself, u8 rows.
+ *   chromosome-out sets, u8 rows.
  */
 #define FMH_GRM_STANDARDIZED 0
 #define FMH_GRM_CENTERED 1
@@ -1245,6 +1246,86 @@ int fmh_grm_finish(const double* h_products, const uint64_t* h_pair_sites_or_nul
 int fmh_grm_host(const uint8_t* h_dosage /* [K][n] */, size_t K, size_t n, uint32_t method, double* h_products, uint64_t* h_pair_sites_or_null,
                  uint64_t* h_n_usable, double* h_scale);   /* host only, no device */
 int fmh_grm_eigen(int device, double* d_matrix, size_t n, size_t n_components, double* h_eigenvalues, double* h_eigenvectors);
+
+/* ---- mixed-model association scan (an addition: the reference has none) ----------------------------------------------------------------------
+ * The last link of the cohort chain: the single-variant test with the random effect of the relationship matrix A (EMMAX, GCTA --mlma,
+ * FaST-LMM), exact in the eigenbasis of A.  With A = U diag(lambda) U^T and V = A + delta I, the per-site term g^T V^-1 g is a weighted sum of
+ * squares of the rotated dosages U^T g: a K x n by n x rows product, which fmh_lmm_projections contracts on the f64 matrix cores straight from
+ * the bit planes, with the weights and the coefficient rows the statistics need.
+ * Matrix, samples, c_i(r), g_i(r), row ranges and row tables are fmh_assoc_sums'.  n = the number of selected samples, i = a position in the
+ * sample list, u = 2^-53.  The library is built with -ffp-contract=off.
+ *
+ * fmh_lmm_projections (device).  d_basis f64 [n][K], device, row-major by sample position, 1 <= K <= 32 768 (it need not be square or
+ *   orthogonal); d_weights f64 [P][K], 1 <= P <= 16; d_linear f64 [L][K], 1 <= L <= 64; outputs d_quad f64 [row_count][P] and d_lin f64
+ *   [row_count][L]; optional host tracks h_called, h_allele_count (u32 [row_count]).  Per row r: c = the number of called genotypes, a = the
+ *   number of alternate alleles among them - fmh_genotype_counts' site tracks, called from inside as fmh_grm does;
+ *   mu = (double)a / (double)c, computed ON THE HOST and uploaded at 8 bytes per row (0 when c = 0); x_i(r) = g_i(r) where the genotype is
+ *   called, else mu.
+ *     T[r][k]    = sum_i  basis[i][k] * x_i(r)
+ *     quad[r][p] = sum_k  weights[p][k] * T[r][k]^2
+ *     lin[r][j]  = sum_k  linear[j][k]  * T[r][k]
+ *   Both outputs are WRITTEN, every entry by one writer: nothing is zeroed, nothing is atomic.  The order of every sum is fixed by the kernel
+ *   alone and two runs give the same bits; FMH_LMM_ITEM_ROWS (the most rows of a work item; default 4 096, or fewer whole passes of 128 rows
+ *   where that many would leave compute units without an item), FMH_GRID_PER_CU and FMH_GRID_BLOCKS change no bit.  T is never stored.  Any
+ *   order of the sums keeps |T^ - T| <= E_k = (n + 2) u sum_i |basis[i][k] x_i|, |lin^ - lin| <= sum_k |linear[j][k]| E_k + (K + 2) u sum_k
+ *   |linear[j][k] T_k| and |quad^ - quad| <= sum_k |weights[p][k]| (2 |T_k| E_k + E_k^2) + (K + 3) u sum_k |weights[p][k]| T_k^2.
+ *   Device memory from the pool: the basis as a padded image indexed by MATRIX sample number (64-sample x 64-component stages, zero rows for
+ *   samples that are not selected), the coefficient image, 8 bytes per row and the tracks; the sum must stay within FMH_PCA_BUDGET_BYTES.
+ *   Enqueues on `stream` and synchronises it.
+ *   Refusals, all before any launch, in this order.  FMH_ERR_INVALID: a NULL matrix, input or output; n_samples == 0; a sample out of range
+ *   or the list not strictly ascending; a row range past the matrix; K, P or L outside their limits.  FMH_ERR_UNSUPPORTED, each with a
+ *   message: ploidy != 2; a matrix without a packed image; over budget.  row_count == 0 is FMH_OK.
+ * fmh_lmm_projections_host: the twin for CPU tests.  h_dosage u8 [rows][n] (0, 1, 2; above 2 = not called); the same three formulas, every
+ *   sum over ascending index in plain f64, the product with the weights as weights * (T * T).
+ *
+ * fmh_lmm_null (host only).  Eigenvalues lambda [n] (each taken as max(lambda_k, 0)), eigenvectors U [n][n] (column k belongs to
+ *   lambda_k), phenotypes [n][P], covariates [n][c_in].  The design matrix is X = [1/sqrt(n) 1, Q]: Q = fmh_assoc_prepare's centred,
+ *   twice-orthonormalised covariate basis with its drop rule and its `dropped` flags; q = c + 1 columns (*h_q).  Rotation X~ = U^T X,
+ *   y~ = U^T y by sequential sums.  For a delta > 0: w_k = 1 / (lambda_k + delta); XWX = X~^T diag(w) X~; b = XWX^-1 X~^T diag(w) y~ by
+ *   Cholesky; R = sum_k w_k (y~_k - X~_k b)^2;
+ *     l(delta) = -1/2 [ (n - q) log(2 pi R / (n - q)) + sum_k log(lambda_k + delta) + log det XWX + (n - q) ]
+ *   (-inf where XWX is not positive definite or R is not positive).  Search per phenotype: l at log10 delta = -5 + 0.1 i, i = 0 .. 100; the
+ *   argmax (the lowest index on a tie) `best`; 40 golden-section steps on [best - 0.1, best + 0.1] clipped to [-5, 5] (ratio
+ *   (sqrt(5) - 1) / 2, the inner points c < d, the interval moves to [lo, d] iff l(c) > l(d)); the best point evaluated is returned (an
+ *   earlier point wins a tie), delta = pow(10, that).  Outputs per phenotype: delta, sigma_g2 = R / (n - q), sigma_e2 = delta sigma_g2,
+ *   heritability = 1 / (1 + delta), l, at_boundary (log10 delta is -5 or 5), and what the device and the statistics take: weights[p] = w
+ *   [n]; q + 1 rows of linear per phenotype, w o X~_0 .. w o X~_(q-1) then w o y~ ([P][q + 1][n]); M = XWX^-1 [P][q][q] (by the factor,
+ *   column by column), v = M (X~^T W y~) [P][q], R [P].  The arrays are the caller's, sized for q = c_in + 1 and filled densely for the q that
+ *   results.  A phenotype of which the design matrix leaves nothing (its norm 0, or its residual after centring and Q at most 2^-26 of it)
+ *   gets reason 1, NaN in every scalar, in M and in v (so every statistic of it is NaN) and zero weights and linear rows.
+ *   h_fixed_delta_or_null [P]: these delta are used and the search is skipped (at_boundary 0, the grid values NaN).
+ *   FMH_ERR_INVALID: a NULL pointer; no phenotype, n == 0 or n > 32 768; a non-finite input, a fixed delta that is not positive;
+ *   n - q - 1 < 1; P > 16 or P (q + 1) > 64.
+ * fmh_lmm_stats (host only).  Per row and phenotype, a_j (j < q), b = the phenotype's q + 1 entries of lin (at p (q + 1)), d its entry of
+ *   quad, c and a the row's exact counts:  aMa = sum_i (sum_j M[i][j] a_j) a_i;  D = d - aMa;  num = b - sum_j a_j v_j;  beta = num / D;
+ *   rss = R - num num / D, 0 if negative;  df = n - q - 1;  se = sqrt(rss / df / D);  t = beta / se;  p = the two-sided Student-t tail of
+ *   fmh_assoc_stats, that very function.  NaN in all four outputs where c = 0, a = 0, a = 2 c (the integers catch the monomorphic rows, where
+ *   D would be rounding noise) or not D > 0; se == 0: t and p are NaN.  Each output may be NULL.
+ * Option: FMH_LMM_ITEM_ROWS.  It changes no result, nor do FMH_GRID_PER_CU and FMH_GRID_BLOCKS.
+ * Not built: leave-one-chromosome-out, low-rank relationship matrices, per-phenotype missing values, a re-fit of delta per site, logistic
+ *   mixed models, sharding over devices, run_vcf wiring, u8 rows.
+ */
+typedef struct {
+  double *h_delta, *h_sigma_g2, *h_sigma_e2, *h_heritability, *h_log_likelihood;   /* [P] */
+  uint8_t *h_at_boundary, *h_reason;          /* [P]; reason: 0 fitted, 1 the design matrix leaves nothing of the phenotype */
+  double *h_weights, *h_linear;               /* [P][n], [P][q + 1][n] */
+  double *h_m, *h_v, *h_r;                    /* [P][q][q], [P][q], [P] */
+  double* h_grid_log_likelihood_or_null;      /* [P][101]: l at the grid points; may be NULL */
+} fmh_lmm_null_out;
+int fmh_lmm_projections(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                        size_t row_begin, size_t row_count, const double* d_basis /* [n][K] */, size_t n_components, const double* d_weights /* [P][K] */,
+                        size_t n_weights, const double* d_linear /* [L][K] */, size_t n_linear, double* d_quad /* [row_count][P] */,
+                        double* d_lin /* [row_count][L] */, uint32_t* h_called_or_null, uint32_t* h_allele_count_or_null, void* stream);
+int fmh_lmm_projections_host(const uint8_t* h_dosage /* [rows][n] */, size_t rows, size_t n, const double* h_basis, size_t n_components,
+                             const double* h_weights, size_t n_weights, const double* h_linear, size_t n_linear, double* h_quad, double* h_lin,
+                             uint32_t* h_called_or_null, uint32_t* h_allele_count_or_null);   /* host only, no device */
+int fmh_lmm_null(const double* h_eigenvalues, const double* h_eigenvectors, const double* h_phenotypes, const double* h_covariates_or_null, size_t n,
+                 size_t n_phenotypes, size_t n_covariates, const double* h_fixed_delta_or_null /* [P] */, size_t* h_q,
+                 uint8_t* h_dropped_or_null /* [n_covariates] */,
+                 const fmh_lmm_null_out* out);   /* host only, no device */
+int fmh_lmm_stats(const double* h_quad, const double* h_lin, const uint32_t* h_called, const uint32_t* h_allele_count, size_t n_rows,
+                  const double* h_m, const double* h_v, const double* h_r, uint64_t n_samples, size_t q, size_t n_phenotypes, double* h_beta,
+                  double* h_se, double* h_t, double* h_p);   /* host only, no device */
 
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
