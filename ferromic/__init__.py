@@ -28,6 +28,8 @@ from ._core import (  # noqa: E402,F401
     HudsonFstSite,
     JointSiteFrequencySpectrum,
     Kinship,
+    LdScoreRegression,
+    LdScores,
     LogisticScan,
     MixedModelScan,
     PairwiseDifference,
@@ -58,6 +60,8 @@ from ._core import (  # noqa: E402,F401
     kinship,
     ld_clump,
     ld_prune,
+    ld_score_regression,
+    ld_scores,
     ld_r2,
     logistic_scan,
     mixed_model_scan,

@@ -177,6 +177,15 @@ class ClumpParams(C.Structure):
     _fields_ = [("p1", C.c_double), ("p2", C.c_double), ("r2", C.c_double), ("window", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LdScoreParams(C.Structure):
+    _fields_ = [("window", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LdscOut(C.Structure):
+    _fields_ = [("h2", C.c_double), ("h2_se", C.c_double), ("intercept", C.c_double), ("intercept_se", C.c_double), ("ratio", C.c_double),
+                ("mean_chi2", C.c_double), ("lambda_gc", C.c_double), ("n_used", C.c_uint64), ("blocks", C.c_uint64)]
+
+
 class GrmParams(C.Structure):
     _fields_ = [("method", C.c_uint32), ("denominator", C.c_uint32)]
 
@@ -318,6 +327,10 @@ SYMBOLS = {
     "fmh_geno_ld_r2": (_i, [_vp, _sz, _vp]),
     "fmh_geno_ld_pairs_host": (_i, [_vp, _sz, _sz, _vp, _vp, _sz, _vp]),
     "fmh_clump_host": (_i, [_vp, _vp, _vp, _sz, _sz, _P(ClumpParams), _vp, _vp, _P(_u64)]),
+    "fmh_ld_scores": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(LdScoreParams), _vp, _vp, _vp, _vp]),
+    "fmh_ld_scores_host": (_i, [_vp, _vp, _sz, _sz, _P(LdScoreParams), _vp, _vp, _vp]),
+    "fmh_ld_score_values": (_i, [_vp, _vp, _sz, _vp]),
+    "fmh_ldsc_regress": (_i, [_vp, _vp, _vp, _sz, _d, _d, _u64, _P(_d), _P(LdscOut)]),
     "fmh_grm": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _P(GrmParams), _P(GrmOut), _P(_u64), _vp]),
     "fmh_grm_values": (_i, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _P(_d), _P(_u64)]),
     "fmh_grm_finish": (_i, [_vp, _vp, _sz, _P(GrmParams), _u64, _d, _vp]),

@@ -103,6 +103,7 @@ struct Options {
   std::atomic<long long> ibd_budget_bytes{(long long)4 << 30};  // FMH_IBD_BUDGET_BYTES: device bytes the sample-major bit image and the block records of one fmh_ibd_scan call may take
   std::atomic<long long> clump_budget_bytes{(long long)1 << 30};  // FMH_CLUMP_BUDGET_BYTES: device bytes of threshold words one launch of fmh_clump's tile kernel may write; candidates are walked in chunks under it
   std::atomic<long long> clump_host_bytes{(long long)8 << 30};    // FMH_CLUMP_HOST_BYTES: host bytes of all candidates' threshold bit rows, kept for fmh_clump's greedy pass; more is refused
+  std::atomic<long long> ldscore_budget_bytes{(long long)1 << 30};  // FMH_LDSCORE_BUDGET_BYTES: device scratch of one launch of fmh_ld_scores (28 bytes per kept row + 8 per item); the items are walked in chunks under it
   std::atomic<long long> graph{0};               // FMH_GRAPH: 1 = replay a repeated pipelined sweep on a local communicator from a captured hipGraph
   std::atomic<unsigned long long> generation{0}; // bumped by every fmh_set_option: a captured launch is never replayed across an option change
 };

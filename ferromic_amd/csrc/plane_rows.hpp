@@ -1,5 +1,5 @@
 // plane_rows.hpp — what the kernels of the device statistics and their host frame (stat_call.hpp) both see: how a kernel is handed the packed
-// image of a matrix - the head of HapArgs, EhhArgs, FstatArgs, QcArgs, AssocArgs, ScoreArgs, RohArgs, IbdStateArgs, ClumpArgs, ClumpPairArgs, GrmCodeArgs and LmmArgs (SfsArgs holds the same fields with its masks between
+// image of a matrix - the head of HapArgs, EhhArgs, FstatArgs, QcArgs, AssocArgs, ScoreArgs, RohArgs, IbdStateArgs, ClumpArgs, ClumpPairArgs, LdScoreArgs, GrmCodeArgs and LmmArgs (SfsArgs holds the same fields with its masks between
 // them); the host fills it in one place, set_plane_rows - how a kernel reads 16 bytes of a plane row, and the LDS of a compute unit.
 #pragma once
 

@@ -922,6 +922,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_roh.inc"
 #include "pymodule_ibd.inc"
 #include "pymodule_clump.inc"
+#include "pymodule_ldscore.inc"
 #include "pymodule_grm.inc"
 #include "pymodule_lmm.inc"
 
@@ -1078,6 +1079,7 @@ PYBIND11_MODULE(_core, m) {
   bind_roh(m, population);
   bind_ibd(m, population);
   bind_clump(m, population);
+  bind_ldscore(m, population);
   bind_grm(m, population);
   bind_lmm(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {

@@ -1663,6 +1663,98 @@ def geno_ld_r2(counts) -> np.ndarray:
     return out[:P]
 
 
+# ---- LD scores and LD score regression ---------------------------------------------------------------------------------------------------------
+LDSCORE_ADJUST = 1
+LDSCORE_ROW_BYTES, LDSCORE_ITEM_BYTES, LDSCORE_TILE = 28, 8, 64   # FMH_LDSCORE_BUDGET_BYTES counts these; an item is a pair of 64-row tiles
+LDSC_OUT = ("h2", "h2_se", "intercept", "intercept_se", "ratio", "mean_chi2", "lambda_gc", "n_used", "blocks")
+
+
+def ldscore_params(window=1_000_000, adjust=True) -> "_abi.LdScoreParams":
+    """fmh_ldscore_params (window in position units; adjust = ldsc's bias correction of every r^2)."""
+    p = _abi.LdScoreParams()
+    p.window, p.flags = int(window), LDSCORE_ADJUST if adjust else 0
+    return p
+
+
+@dataclass
+class LdScoreSums:
+    q: np.ndarray          # int64 [rows]: the sum of the pair terms in units of 2^-40
+    partners: Optional[np.ndarray]  # uint32 [rows]: kept rows within the window
+    counted: np.ndarray    # uint32 [rows]: those whose term is defined
+
+
+def ld_scores(m: DeviceMatrix, params, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+              positions=None, want_partners: bool = True, stream=None) -> LdScoreSums:
+    """fmh_ld_scores over rows [row_begin, row_begin + row_count) and the samples `samples` (ascending sample numbers; None = the first
+    n_samples, default all).  `positions` [variants] uint32 (indexed by matrix row) or None.  The outputs are pre-filled with junk."""
+    rows = m.variants - row_begin if row_count is None else row_count
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = samples.size
+    else:
+        n = m.samples if n_samples is None else int(n_samples)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != rows:
+            raise ValueError("keep has one entry per row of the range")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        if positions.size != m.variants:
+            raise ValueError("positions has one entry per row of the matrix")
+    q = np.full(max(rows, 1), -0x5A5A5A5A5A5A5A5A, dtype=np.int64)
+    partners = np.full(max(rows, 1), 0xA5A5A5A5, dtype=np.uint32) if want_partners else None
+    counted = np.full(max(rows, 1), 0xA5A5A5A5, dtype=np.uint32)
+    _abi.check(_abi.load().fmh_ld_scores(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), _ptr(positions), C.byref(params), _ptr(q), _ptr(partners),
+                                         _ptr(counted), stream))
+    return LdScoreSums(q[:rows], None if partners is None else partners[:rows], counted[:rows])
+
+
+def ld_scores_host(dosage, params, x=None, want_partners: bool = True) -> LdScoreSums:
+    """fmh_ld_scores_host (host only): the same rule over `dosage` uint8 [K][n] (0, 1, 2; 3 = not called), `x` uint32 [K] or None."""
+    dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
+    K, n = dosage.shape
+    if x is not None:
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.size != K:
+            raise ValueError("x has one entry per row")
+    q = np.full(max(K, 1), -0x5A5A5A5A5A5A5A5A, dtype=np.int64)
+    partners = np.full(max(K, 1), 0xA5A5A5A5, dtype=np.uint32) if want_partners else None
+    counted = np.full(max(K, 1), 0xA5A5A5A5, dtype=np.uint32)
+    _abi.check(_abi.load().fmh_ld_scores_host(_ptr(dosage) if dosage.size else None, _ptr(x), K, n, C.byref(params), _ptr(q), _ptr(partners), _ptr(counted)))
+    return LdScoreSums(q[:K], None if partners is None else partners[:K], counted[:K])
+
+
+def ld_score_values(q, counted) -> np.ndarray:
+    """fmh_ld_score_values (host only): float64 [K] = q * 2^-40, NaN where counted is 0."""
+    q = np.ascontiguousarray(q, dtype=np.int64)
+    counted = np.ascontiguousarray(counted, dtype=np.uint32)
+    if q.shape != counted.shape or q.ndim != 1:
+        raise ValueError("q and counted are one-dimensional and of one length")
+    K = q.size
+    out = np.full(max(K, 1), 12345.678, dtype=np.float64)
+    _abi.check(_abi.load().fmh_ld_score_values(_ptr(q) if K else None, _ptr(counted) if K else None, K, _ptr(out) if K else None))
+    return out[:K]
+
+
+def ldsc_regress(chi2, score, n_samples, m_sites, blocks=200, intercept=None, weights=None) -> dict:
+    """fmh_ldsc_regress (host only): the LD score regression of chi2 on score; a dict of LDSC_OUT."""
+    chi2 = np.ascontiguousarray(chi2, dtype=np.float64)
+    score = np.ascontiguousarray(score, dtype=np.float64)
+    if chi2.shape != score.shape or chi2.ndim != 1:
+        raise ValueError("chi2 and score are one-dimensional and of one length")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != score.shape:
+            raise ValueError("weights has one entry per site")
+    out = _abi.LdscOut()
+    C.memset(C.byref(out), 0xA5, C.sizeof(out))
+    fixed = None if intercept is None else C.byref(C.c_double(float(intercept)))
+    K = chi2.size
+    _abi.check(_abi.load().fmh_ldsc_regress(_ptr(chi2) if K else None, _ptr(score) if K else None, _ptr(weights), K, float(n_samples), float(m_sites), int(blocks),
+                                            fixed, C.byref(out)))
+    return {name: getattr(out, name) for name in LDSC_OUT}
+
+
 # ---- haplotype homozygosity windows --------------------------------------------------------------------------------------------------
 HAP_WINDOW_DTYPE = np.dtype([("sum_sq", np.uint64), ("distinct", np.uint32), ("top", np.uint32, (3,))])
 HAP_STATS = ("h1", "h12", "h123", "h2_h1", "haplotype_diversity")

@@ -1173,6 +1173,63 @@ int fmh_clump_host(const uint8_t* h_dosage /* [K][n] */, const uint32_t* h_x_or_
                    const fmh_clump_params* params, uint32_t* h_index_of /* [K] */, double* h_r2_or_null /* [K] */,
                    uint64_t* h_n_clumps_or_null);   /* host only, no device */
 
+/* ---- LD scores and LD score regression (an addition: the reference has none) -----------------------------------------------------------
+ * What a study computes from an association scan's chi^2 column: the LD score of every site, l_i = the sum of genotype r^2 over the sites
+ * within a window of site i (ldsc --l2, GCTA --ld-score), and the regression of chi^2 on it, whose intercept separates confounding from
+ * polygenicity and whose slope is the SNP heritability.  THE definition: the device (fmh_ld_scores), the host twin (fmh_ld_scores_host)
+ * and a plain Python loop agree on every integer.
+ * Matrix, samples, called, dosage, kept rows and positions are fmh_clump's (rule 1 there): ploidy 2, a packed image, every plane masked
+ *   with the called plane, row_gap / row_hi honoured; h_keep_or_null; h_positions_or_null u32 [variants], non-decreasing over the range,
+ *   NULL = x is the row number.  Parameters fmh_ldscore_params { window, flags }; flags is 0 or FMH_LDSCORE_ADJUST.
+ * Pair term of two kept rows i, j (j = i included): the six integers are fmh_geno_ld_counts over the selected samples and r2 is the
+ *   fmh_geno_ld_r2 formula, bit for bit.  The pair is SKIPPED when r2 is NaN and, with FMH_LDSCORE_ADJUST, also when the joint called
+ *   count n < 3.  Otherwise t = r2 without FMH_LDSCORE_ADJUST and t = r2 - (1.0 - r2) / (double)(n - 2) with it (ldsc's bias correction,
+ *   in that operation order, built with -ffp-contract=off), and q = llrint(ldexp(t, 40)), round half to even.
+ * Per kept row i: partners[i] = the number of kept rows j with |x_j - x_i| <= window (i itself is one), counted[i] = the number of those
+ *   that are not skipped, Q[i] = the sum of q over them as int64.  Rows that are not kept get 0, 0, 0.  The sum of integers is the same in
+ *   every order, so tiles, the symmetry r2_ij = r2_ji and atomic adds change nothing; the quantisation is at most 2^-41 per term.
+ *   fmh_ld_score_values: score = (double)Q * 2^-40, NaN where counted == 0.
+ * fmh_ld_scores: host outputs h_q i64 [row_count], h_partners_or_null u32 [row_count], h_counted u32 [row_count], every entry written;
+ *   it enqueues on `stream` and synchronises it.  No kept row is FMH_OK with zeros and no launch.
+ * Refused before any launch, in this order.  FMH_ERR_INVALID: a NULL matrix, params, h_q or h_counted; n_samples == 0; a bad sample list; a
+ *   row range past the matrix; flags other than 0 or FMH_LDSCORE_ADJUST; positions that descend in the range.  FMH_ERR_UNSUPPORTED, each
+ *   with a message: ploidy != 2; no packed image (the message names fmh_matrix_pack); a range of 2^32 - 1 rows or more; a row with more than
+ *   2^22 partners (so that |Q| < 2^63); more than 2^31 work items; a launch's scratch above FMH_LDSCORE_BUDGET_BYTES (default 1 GiB): the
+ *   scratch is 28 bytes per kept row plus 8 bytes per work item (a pair of 64-row tiles of kept rows that holds a partner pair); the items
+ *   are walked in chunks under the budget, and a budget below 28 bytes per kept row plus one item is refused with the bytes needed.  The
+ *   option changes no result.
+ * Host only, no device: fmh_ld_scores_host (the same rule over h_dosage u8 [K][n]: 0, 1, 2; 3 = not called, h_x u32 [K] or NULL = k; every
+ *   given row counts as kept; refusals as fmh_clump_host's), fmh_ld_score_values and fmh_ldsc_regress.
+ * LD score regression, fmh_ldsc_regress(chi2 [K], score [K], w_score_or_null [K] (NULL = score), K, N, M, blocks, fixed_intercept_or_null):
+ *   a site is USED iff its chi2, score and w_score are finite; U used sites, in ascending order, B = min(blocks, U) blocks
+ *   [floor(bU/B), floor((b+1)U/B)).  x = N * l / M; the model is E[chi2] = a + h x.  Start a = 1.0 (or the fixed intercept) and
+ *   h = M * (mean chi2 - 1.0) / (N * mean l).  Weights of an estimate (a, h), hc = h clipped to [0, 1]:
+ *   c = a + ((hc * N) * max(l, 1.0)) / M,  w = 1.0 / (max(lw, 1.0) * (2.0 * (c * c))).
+ *   Three weighted least-squares fits, each with the weights of the previous estimate.  Sums in ascending site order:
+ *   Sw = sum w, Sx = sum w x, Sxx = sum (w x) x, Sy = sum w y, Sxy = sum (w x) y; det = Sw Sxx - Sx Sx, h = (Sw Sxy - Sx Sy) / det,
+ *   a = (Sxx Sy - Sx Sxy) / det; with a fixed intercept h = (Sxy - a Sx) / Sxx.  Standard errors: delete-one-block jackknife of the last
+ *   fit with its weights held; per-block sums, the sums without block b added in ascending block order, pseudo-values
+ *   (double)B * theta - (double)(B - 1) * theta_(-b), se = sqrt(var(pseudo, ddof 1) / B).  ratio = (a - 1) / (mean chi2 - 1);
+ *   lambda_gc = median chi2 / 0.4549364231195724 (an even U takes (lo + hi) / 2.0).  intercept_se is NaN with a fixed intercept.
+ *   Built with -ffp-contract=off: a plain loop over doubles reproduces every bit.
+ *   Refused (FMH_ERR_INVALID) before any arithmetic: a NULL chi2, score or out; N or M not finite or <= 0; a fixed intercept that is not
+ *   finite; blocks < 2; fewer than 2 used sites per fitted parameter and block (U < 2 P B, P = 2, or 1 with a fixed intercept); a
+ *   negative chi2 among the used sites.
+ */
+#define FMH_LDSCORE_ADJUST 1u
+typedef struct { uint32_t window; uint32_t flags; } fmh_ldscore_params;
+typedef struct { double h2, h2_se, intercept, intercept_se, ratio, mean_chi2, lambda_gc; uint64_t n_used, blocks; } fmh_ldsc_out;
+int fmh_ld_scores(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                  size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count] */,
+                  const uint32_t* h_positions_or_null /* [variants] */, const fmh_ldscore_params* params, int64_t* h_q /* [row_count] */,
+                  uint32_t* h_partners_or_null /* [row_count] */, uint32_t* h_counted /* [row_count] */, void* stream);
+int fmh_ld_scores_host(const uint8_t* h_dosage /* [K][n]: 0, 1, 2, 3 = not called */, const uint32_t* h_x_or_null /* [K] */, size_t K, size_t n,
+                       const fmh_ldscore_params* params, int64_t* h_q /* [K] */, uint32_t* h_partners_or_null /* [K] */,
+                       uint32_t* h_counted /* [K] */);   /* host only, no device */
+int fmh_ld_score_values(const int64_t* h_q, const uint32_t* h_counted, size_t K, double* h_score);   /* host only, no device */
+int fmh_ldsc_regress(const double* h_chi2, const double* h_score, const double* h_w_score_or_null, size_t K, double N, double M, uint64_t blocks,
+                     const double* fixed_intercept_or_null, fmh_ldsc_out* out);   /* host only, no device */
+
 /* ---- genomic relationship matrix and genotype PCA (an addition: the reference's PCA is the haplotype PCA above) ---------------------------
  * The per-sample link of the cohort chain QC -> fmh_ld_prune -> fmh_kinship_counts -> PCA -> association: the matrix GCTA --make-grm and
  * PLINK --make-rel compute, and its top eigenvectors (PLINK --pca), the covariates of the association scans.
