@@ -9,6 +9,7 @@ from ferromic_amd import _abi as _abi
 _abi.load()
 
 from ._core import (  # noqa: E402,F401
+    Admixture,
     AssociationScan,
     ChromosomePcaResult,
     Clumps,
@@ -39,6 +40,7 @@ from ._core import (  # noqa: E402,F401
     WcFstResult,
     WcFstSite,
     adjusted_sequence_length,
+    admixture,
     association_scan,
     chromosome_pca,
     chromosome_pca_to_file,

@@ -200,6 +200,16 @@ class LmmNullOut(C.Structure):
                                                 "h_weights", "h_linear", "h_m", "h_v", "h_r", "h_grid_log_likelihood_or_null")]
 
 
+class AdmixInfoOut(C.Structure):
+    _fields_ = [("n_samples", C.c_uint64), ("kept_rows", C.c_uint64), ("usable_rows", C.c_uint64), ("h_usable", C.c_void_p), ("h_called", C.c_void_p),
+                ("h_allele_count", C.c_void_p), ("h_sample_sites", C.c_void_p)]
+
+
+class AdmixTracks(C.Structure):
+    _fields_ = [("h_usable", C.c_void_p), ("h_called", C.c_void_p), ("h_allele_count", C.c_void_p), ("h_sample_sites", C.c_void_p),
+                ("h_usable_rows", C.POINTER(C.c_uint64))]
+
+
 class HapWindow(C.Structure):
     _fields_ = [("sum_sq", C.c_uint64), ("distinct", C.c_uint32), ("top", C.c_uint32 * 3)]
 
@@ -340,6 +350,13 @@ SYMBOLS = {
     "fmh_lmm_projections_host": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "fmh_lmm_null": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _P(_sz), _vp, _P(LmmNullOut)]),
     "fmh_lmm_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _u64, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "fmh_admix_create": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _P(_vp), _vp]),
+    "fmh_admix_info": (_i, [_vp, _P(AdmixInfoOut)]),
+    "fmh_admix_destroy": (None, [_vp]),
+    "fmh_admix_step": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "fmh_admix_step_host": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _u32, _P(AdmixTracks)]),
+    "fmh_admix_start": (_i, [_vp, _vp, _sz, _sz, _sz, _u64, _vp, _vp]),
+    "fmh_admix_accelerate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _P(_d)]),
     "fmh_haplotype_windows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmh_haplotype_stats": (_i, [_vp, _sz, _u64, _vp]),
     "fmh_haplotype_max_members": (_u32, []),
@@ -380,6 +397,7 @@ SYMBOLS = {
     "fmh_timing_read_pca": (_i, [_P(_d)]),
     "fmh_timing_read_gram": (_i, [_P(_d)]),
     "fmh_timing_read_grm": (_i, [_P(_d)]),
+    "fmh_timing_read_admix": (_i, [_P(_d)]),
     "fmh_timing_enable": (_i, [_i]),
     "fmh_timing_reset": (_i, []),
     "fmh_timing_read": (_i, [_P(_d), _P(_u64)]),

@@ -115,6 +115,8 @@ const OptionRow kOptionRows[] = {
     {"FMH_CLUMP_HOST_BYTES", &Options::clump_host_bytes, (long long)8 << 30, nullptr},
     {"FMH_LDSCORE_BUDGET_BYTES", &Options::ldscore_budget_bytes, (long long)1 << 30, nullptr},
     {"FMH_LMM_ITEM_ROWS", &Options::lmm_item_rows, 0, nullptr},
+    {"FMH_ADMIX_ITEM_ROWS", &Options::admix_item_rows, 0, nullptr},
+    {"FMH_ADMIX_BUDGET_BYTES", &Options::admix_budget_bytes, (long long)4 << 30, nullptr},
 };
 bool parse_option(const OptionRow& row, const char* text, long long* out) {
   if (row.words) {

@@ -925,6 +925,7 @@ optional<double> inversion_allele_frequency(const py::object& sample_map) {
 #include "pymodule_ldscore.inc"
 #include "pymodule_grm.inc"
 #include "pymodule_lmm.inc"
+#include "pymodule_admix.inc"
 
 }  // namespace
 
@@ -1082,6 +1083,7 @@ PYBIND11_MODULE(_core, m) {
   bind_ldscore(m, population);
   bind_grm(m, population);
   bind_lmm(m, population);
+  bind_admix(m, population);
   m.def("hudson_dxy", [](const py::object& a, const py::object& b) {
     auto p1 = coerce_population(a), p2 = coerce_population(b);
     return HudsonDxyResult{calculate_d_xy_hudson(*p1, *p2)};

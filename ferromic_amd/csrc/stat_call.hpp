@@ -1,4 +1,4 @@
-// stat_call.hpp — the host frame the device statistics share (ld.hip, sfs.hip, hap.hip, ehh.hip, fstat.hip, kinship.hip, qc.hip, assoc.hip, logistic.hip, score.hip, roh.hip, ibd.hip, clump.hip, ldscore.hip, grm.hip, lmm.hip;
+// stat_call.hpp — the host frame the device statistics share (ld.hip, sfs.hip, hap.hip, ehh.hip, fstat.hip, kinship.hip, qc.hip, assoc.hip, logistic.hip, score.hip, roh.hip, ibd.hip, clump.hip, ldscore.hip, grm.hip, lmm.hip, admix.hip;
 // pca.hip and pairwise.hip take the checks, the timer and the scratch): the refusals several entry points word alike, the plane pointers of a
 // kernel's arguments, the rows-per-item rule, the size of a persistent grid, the event timer, and StatCall - device, workspace, stream, scratch
 // and timer of one call.  One rule in one place, so the units cannot drift apart.  What only the segment statistics share (roh.hip, ibd.hip)

@@ -852,6 +852,151 @@ def lmm_projections_host(dosage, basis, weights, linear) -> LmmProjections:
     return LmmProjections(quad, lin, called, allele_count)
 
 
+# ---- admixture -------------------------------------------------------------------------------------------------------------------------------
+ADMIX_MAX_K = 16
+ADMIX_EPS = 1e-5
+ADMIX_PASS_ROWS = 128   # FMH_ADMIX_ITEM_ROWS is rounded up to whole passes
+ADMIX_UPDATE_Q, ADMIX_UPDATE_F = 1, 2
+
+
+def _admix_flags(update_q: bool, update_f: bool) -> int:
+    return (ADMIX_UPDATE_Q if update_q else 0) | (ADMIX_UPDATE_F if update_f else 0)
+
+
+class AdmixImage:
+    """fmh_admix: the resident 2-bit genotype image of the usable rows among those of [row_begin, row_begin + row_count) that `keep` keeps, for
+    the samples `samples` (ascending sample numbers; None = the first n_samples, default all).  Holds n, kept_rows, m and the host tracks
+    usable (bool), called, allele_count per kept row and sample_sites [n].  A context manager; close() frees the device memory."""
+
+    def __init__(self, m: DeviceMatrix, samples=None, n_samples: Optional[int] = None, row_begin: int = 0, row_count: Optional[int] = None, keep=None,
+                 stream=None):
+        rows = m.variants - row_begin if row_count is None else row_count
+        if samples is not None:
+            samples = np.ascontiguousarray(samples, dtype=np.uint32)
+            n = samples.size
+        else:
+            n = m.samples if n_samples is None else int(n_samples)
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8)
+            if keep.size != rows:
+                raise ValueError("keep has one entry per row of the range")
+        self._h = None
+        self.device = m.device
+        h = C.c_void_p()
+        _abi.check(_abi.load().fmh_admix_create(m._h, _ptr(samples), n, row_begin, rows, _ptr(keep), C.byref(h), stream))
+        self._h = h.value
+        info = _abi.AdmixInfoOut()
+        _abi.check(_abi.load().fmh_admix_info(self._h, C.byref(info)))
+        self.n, self.kept_rows, self.m = int(info.n_samples), int(info.kept_rows), int(info.usable_rows)
+
+        def copy(ptr, dtype, count):
+            if count == 0:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(count,)).copy()
+
+        self.usable = copy(info.h_usable, np.uint8, self.kept_rows).astype(bool)
+        self.called = copy(info.h_called, np.uint32, self.kept_rows)
+        self.allele_count = copy(info.h_allele_count, np.uint32, self.kept_rows)
+        self.sample_sites = copy(info.h_sample_sites, np.uint64, self.n)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.load().fmh_admix_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _admix_state(q, f):
+    q, f = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(f, dtype=np.float64)
+    if q.ndim != 2 or f.ndim != 2 or q.shape[1] != f.shape[1]:
+        raise ValueError("q is [n][K] and f is [m][K]")
+    return q, f
+
+
+def admix_step(image: AdmixImage, q, f, loglik: bool = True, update_q: bool = True, update_f: bool = True, stream=None, fill: Optional[float] = None):
+    """fmh_admix_step: one EM step from q [n][K], f [m][K]: (q', f', l of the input or None).  `fill` pre-fills the outputs (tests: every entry is
+    written)."""
+    q, f = _admix_state(q, f)
+    if q.shape[0] != image.n or f.shape[0] != image.m:
+        raise ValueError("q has one row per sample of the image and f one per usable row")
+    K = q.shape[1]
+    d_q, d_f = DeviceBuffer.from_numpy(image.device, q), DeviceBuffer.from_numpy(image.device, f)
+    d_qo = DeviceBuffer.from_numpy(image.device, np.full(q.size, 0.0 if fill is None else fill, dtype=np.float64))
+    d_fo = DeviceBuffer.from_numpy(image.device, np.full(f.size, 0.0 if fill is None else fill, dtype=np.float64))
+    ll = C.c_double(0.0)
+    _abi.check(_abi.load().fmh_admix_step(image._h, K, d_q.ptr, d_f.ptr, d_qo.ptr, d_fo.ptr, C.byref(ll) if loglik else None, _admix_flags(update_q, update_f),
+                                         stream))
+    return d_qo.to_numpy(np.float64, q.size).reshape(q.shape), d_fo.to_numpy(np.float64, f.size).reshape(f.shape), float(ll.value) if loglik else None
+
+
+@dataclass
+class AdmixTracks:
+    usable: np.ndarray         # bool [rows]
+    called: np.ndarray         # c, a per row, uint32
+    allele_count: np.ndarray
+    sample_sites: np.ndarray   # m_i, uint64 [n]
+    m: int
+
+
+def admix_tracks_host(dosage) -> AdmixTracks:
+    """fmh_admix_step_host without a state (host only): the tracks of a [rows][n] dosage table (0, 1, 2; above 2 = not called)."""
+    d = np.ascontiguousarray(dosage, dtype=np.uint8)
+    rows, n = d.shape
+    usable, called, allele_count, sites = np.zeros(rows, np.uint8), np.zeros(rows, np.uint32), np.zeros(rows, np.uint32), np.zeros(n, np.uint64)
+    m = C.c_uint64(0)
+    tracks = _abi.AdmixTracks(_ptr(usable), _ptr(called), _ptr(allele_count), _ptr(sites), C.pointer(m))
+    _abi.check(_abi.load().fmh_admix_step_host(_ptr(d), rows, n, 0, None, None, None, None, None, 0, C.byref(tracks)))
+    return AdmixTracks(usable.astype(bool), called, allele_count, sites, int(m.value))
+
+
+def admix_step_host(dosage, q, f, loglik: bool = True, update_q: bool = True, update_f: bool = True):
+    """fmh_admix_step_host (host only): the twin over a [rows][n] dosage table; f is [m][K] over the usable rows: (q', f', l or None)."""
+    d = np.ascontiguousarray(dosage, dtype=np.uint8)
+    q, f = _admix_state(q, f)
+    rows, n = d.shape
+    if q.shape[0] != n or f.shape[0] != admix_tracks_host(d).m:
+        raise ValueError("q has one row per sample and f one per usable row")
+    K = q.shape[1]
+    q_out, f_out = np.full(q.shape, np.nan), np.full(f.shape, np.nan)
+    ll = C.c_double(0.0)
+    _abi.check(_abi.load().fmh_admix_step_host(_ptr(d), rows, n, K, _ptr(q), _ptr(f), _ptr(q_out), _ptr(f_out), C.byref(ll) if loglik else None,
+                                              _admix_flags(update_q, update_f), None))
+    return q_out, f_out, float(ll.value) if loglik else None
+
+
+def admix_start(called, allele_count, n: int, k: int, seed: int = 0):
+    """fmh_admix_start (host only): the default start (q [n][k], f [m][k]) from c, a of the m usable rows."""
+    c, a = np.ascontiguousarray(called, dtype=np.uint32), np.ascontiguousarray(allele_count, dtype=np.uint32)
+    if c.shape != a.shape or c.ndim != 1:
+        raise ValueError("called and allele_count are one-dimensional and of one length")
+    q, f = np.empty((int(n), int(k)), dtype=np.float64), np.empty((c.size, int(k)), dtype=np.float64)
+    _abi.check(_abi.load().fmh_admix_start(_ptr(c), _ptr(a), c.size, int(n), int(k), int(seed), _ptr(q), _ptr(f)))
+    return q, f
+
+
+def admix_accelerate(state0, state1, state2):
+    """fmh_admix_accelerate (host only): states are (q, f) pairs; returns (qa, fa, alpha); alpha = 0: nothing to extrapolate, the state is state2's."""
+    (q0, f0), (q1, f1), (q2, f2) = (_admix_state(*s) for s in (state0, state1, state2))
+    if not (q0.shape == q1.shape == q2.shape and f0.shape == f1.shape == f2.shape):
+        raise ValueError("the three states have one shape")
+    qa, fa = np.empty_like(q0), np.empty_like(f0)
+    alpha = C.c_double(0.0)
+    _abi.check(_abi.load().fmh_admix_accelerate(_ptr(q0), _ptr(f0), _ptr(q1), _ptr(f1), _ptr(q2), _ptr(f2), q0.shape[0], f0.shape[0], q0.shape[1], _ptr(qa),
+                                               _ptr(fa), C.byref(alpha)))
+    return qa, fa, float(alpha.value)
+
+
 @dataclass
 class LmmNull:
     q: int

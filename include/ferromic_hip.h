@@ -82,7 +82,7 @@ int fmh_device_info(int device, char* h_name, size_t name_cap, int* h_compute_un
  *   FMH_TILED_PLANES (0 | 1 | 2)   FMH_TILED_BYTES   FMH_TILED (-1 | 0 | 1)   FMH_TILED_BATCH (10 | 5 | 2)
  *   FMH_SFS_ITEM_ROWS   FMH_SFS_LDS_BINS   FMH_HAP_THREADS (64 | 256 | 512 | 1024)   FMH_FSTAT_ITEM_ROWS   FMH_FSTAT_LDS_MASK_BYTES
  *   FMH_KIN_BUDGET_BYTES   FMH_QC_ITEM_ROWS   FMH_ASSOC_ITEM_ROWS   FMH_ASSOC_BUDGET_BYTES   FMH_SCORE_ITEM_ROWS   FMH_SCORE_BUDGET_BYTES
- *   FMH_ROH_ITEM_ROWS   FMH_IBD_ITEM_ROWS   FMH_IBD_BUDGET_BYTES   FMH_LMM_ITEM_ROWS
+ *   FMH_ROH_ITEM_ROWS   FMH_IBD_ITEM_ROWS   FMH_IBD_BUDGET_BYTES   FMH_LMM_ITEM_ROWS   FMH_ADMIX_ITEM_ROWS   FMH_ADMIX_BUDGET_BYTES
  * Values are atomics: setting one while another thread launches is safe (that launch sees the old or the new value). */
 int fmh_set_option(const char* key, const char* value_or_null);
 int fmh_get_option(const char* key, long long* h_value);
@@ -1384,6 +1384,91 @@ int fmh_lmm_stats(const double* h_quad, const double* h_lin, const uint32_t* h_c
                   const double* h_m, const double* h_v, const double* h_r, uint64_t n_samples, size_t q, size_t n_phenotypes, double* h_beta,
                   double* h_se, double* h_t, double* h_p);   /* host only, no device */
 
+/* ---- admixture: ancestry proportions by EM (an addition: the reference has none) -----------------------------------------------------------------
+ * The model of ADMIXTURE, FRAPPE, fastmixture and STRUCTURE: per sample the proportions Q of K ancestral populations, per site the allele
+ * frequencies F of those populations.  The project's own definition.
+ *
+ * Selected diploid samples i = 0 .. n-1 (a list as fmh_grm takes it); kept rows = a row range and an optional keep mask, as fmh_grm's.  Genotype
+ * classes are fmh_grm's codes: g in {0, 1, 2}, or not called (a missing call, or an allele above 1).  c_r = the called genotypes of row r, a_r
+ * the alternate alleles among them; a row is USABLE when c_r > 0 and 0 < a_r < 2 c_r; every other row is reported and takes no part.  m_i = the
+ * number of usable rows at which sample i is called.  Usable rows are j = 0 .. m-1 in row order.
+ *
+ * State: Q [n][K] and F [m][K], f64, row-major, 1 <= K <= 16 (FMH_ADMIX_MAX_K); G = fl(1 - F) elementwise; eps = 1e-5 (ADMIXTURE's bound).
+ * One EM step (Q, F) -> (Q', F'), every sum over called genotypes only:
+ *   h0_ij = sum_k q_ik f_jk        h1_ij = sum_k q_ik g_jk      (two sums of positive terms; 1 - h0 is never formed)
+ *   u_ij  = g_ij / h0_ij           v_ij  = (2 - g_ij) / h1_ij
+ *   A_jk  = sum_i u_ij q_ik        B_jk  = sum_i v_ij q_ik
+ *   f'_jk = clamp(f_jk A_jk / (f_jk A_jk + g_jk B_jk), eps, 1 - eps)
+ *   E_ik  = sum_j (u_ij f_jk + v_ij g_jk)
+ *   q0_ik = clamp(q_ik E_ik / (2 m_i), eps, 1 - eps);   q'_ik = q0_ik / sum_k q0_ik   (k ascending)
+ *   l(Q, F) = sum_ij g_ij log h0_ij + (2 - g_ij) log h1_ij       (of the step's INPUT)
+ * A sample with m_i = 0 keeps its row of Q.  Flag bits FMH_ADMIX_UPDATE_Q and FMH_ADMIX_UPDATE_F: a half whose bit is clear is copied to the
+ * output unchanged; FMH_ADMIX_UPDATE_Q alone is projection (new samples on a reference panel's frequencies).  K = 1 has the closed form
+ * f' = a / (2 c) up to rounding and q' = 1.  sum_k q_ik E_ik = 2 m_i, and l does not fall from step to step.
+ *
+ * fmh_admix is an opaque handle, because a fit reads the same genotypes hundreds of times.  fmh_admix_create counts c, a through
+ * fmh_genotype_counts, marks the usable rows, builds their 2-bit code image (sample-major, fmh_grm's) and computes m_i; the handle owns its
+ * device memory and does not need the matrix afterwards.  Refusals come before any launch: FMH_ERR_INVALID for NULLs, n_samples == 0, bad
+ * lists or ranges; FMH_ERR_UNSUPPORTED with a message for ploidy != 2, for a matrix without the packed image, and for an image over
+ * FMH_ADMIX_BUDGET_BYTES.  No kept row or no usable row gives a handle with m = 0, whose step is FMH_OK and writes only Q' (copied) and l = 0.
+ * fmh_admix_info: n, the kept rows, m, and host arrays owned by the handle: usable, called, allele_count per KEPT row, sample_sites [n].
+ *
+ * fmh_admix_step: d_q [n][K], d_f [m][K] in, d_q_out, d_f_out out (device; input and output must not alias: refused).  Every output entry is
+ * WRITTEN by one writer; nothing need be zeroed by the caller; there are no floating-point atomics, and two runs give the same bits.  K
+ * outside 1 .. 16 and NULLs are refused.  Inputs outside [eps, 1 - eps] (or rows of Q that do not sum to one) are the caller's affair: nothing
+ * checks them.  h_loglik_or_null == NULL runs a kernel without logarithms; Q', F' have the same bits either way.  The call synchronises the
+ * stream.  The step runs on v_mfma_f64_16x16x4_f64 for every K; a workgroup owns a block of usable rows
+ * (FMH_ADMIX_ITEM_ROWS, rounded up to whole passes of 128 rows; default: two blocks per compute unit, fewer where the slabs would pass the
+ * budget).  FMH_ADMIX_BUDGET_BYTES (default 4 GiB) bounds image plus padded state plus slabs; more is refused with the bytes needed.  The
+ * item size may change the last bits of Q' and l (the order of a sum) and no bit of F'; FMH_GRID_PER_CU and FMH_GRID_BLOCKS change no bit.
+ *
+ * Host only, no device:
+ *   fmh_admix_step_host: the twin for CPU tests.  h_dosage u8 [rows][n] (0, 1, 2; above 2 = not called); the same usable rule; h_f, h_f_out
+ *     [m][K] over the usable rows; every sum over ascending index in plain f64 (rows outer, samples inner for A, B, E and l).  `tracks` (may be
+ *     NULL, each member may be NULL) receives usable, called, allele_count per row, sample_sites [n] and m.  With all four state pointers NULL
+ *     only the tracks are computed (how a caller learns m).
+ *   fmh_admix_start: the default start.  mix = splitmix64's finaliser after adding 0x9E3779B97F4A7C15; U(t) = (mix(mix(seed) + t) >> 11) 2^-53;
+ *     q_ik = w_ik / sum_k w_ik with w = 1 + U(i K + k); f_jk = clamp(a_j / (2 c_j) + 0.2 (U(2^40 + j K + k) - 0.5), 0.01, 0.99); c, a of the m
+ *     usable rows.
+ *   fmh_admix_accelerate: the extrapolation of one SQUAREM-S3 cycle.  r = t1 - t0, v = (t2 - t1) - r, alpha = max(1, sqrt(sum r^2 / sum v^2)),
+ *     the sums over Q then F in ascending index; ta = (t0 + (2 alpha) r) + (alpha alpha) v, then F clamped to [eps, 1 - eps], Q clamped and
+ *     renormalised as in the step.  sum v^2 == 0: ta = t2 and *h_alpha = 0 (nothing to extrapolate).  m = 0 leaves F out (projection).
+ *   The accelerated cycle a caller runs with these: t1 = M(t0) gives l0, t2 = M(t1) gives l1, ta from fmh_admix_accelerate, t3 = M(ta) gives
+ *   la; the next cycle starts from t3 if la is finite and la >= l1, else from t2 (and from t2 without a third step when alpha = 0).  The l0 of
+ *   successive cycles never falls.
+ *
+ * Not built: K > 16; a VALU route for small K; the extrapolation on the device; cross-validation error; supervised ancestry; bootstrap or
+ * standard errors; alignment of component labels between runs; mini-batch updates; haploid data; sharding over devices; run_vcf wiring; u8 rows. */
+#define FMH_ADMIX_MAX_K 16
+#define FMH_ADMIX_UPDATE_Q 1u
+#define FMH_ADMIX_UPDATE_F 2u
+typedef struct fmh_admix fmh_admix;
+typedef struct {
+  uint64_t n_samples, kept_rows, usable_rows;
+  const uint8_t* h_usable;             /* [kept_rows]; owned by the handle, as the three below */
+  const uint32_t *h_called, *h_allele_count;   /* [kept_rows] */
+  const uint64_t* h_sample_sites;      /* [n_samples] m_i */
+} fmh_admix_info_out;
+typedef struct {
+  uint8_t* h_usable;                   /* [rows] */
+  uint32_t *h_called, *h_allele_count; /* [rows] */
+  uint64_t* h_sample_sites;            /* [n] */
+  uint64_t* h_usable_rows;             /* m */
+} fmh_admix_tracks;
+int fmh_admix_create(const fmh_matrix* m, const uint32_t* h_samples_or_null /* ascending, distinct; NULL = the first n_samples */, size_t n_samples,
+                     size_t row_begin, size_t row_count, const uint8_t* h_keep_or_null /* [row_count] */, fmh_admix** out, void* stream);
+int fmh_admix_info(const fmh_admix* h, fmh_admix_info_out* info);
+void fmh_admix_destroy(fmh_admix* h);
+int fmh_admix_step(const fmh_admix* h, size_t n_components, const double* d_q, const double* d_f, double* d_q_out, double* d_f_out,
+                   double* h_loglik_or_null, uint32_t flags, void* stream);
+int fmh_admix_step_host(const uint8_t* h_dosage /* [rows][n] */, size_t rows, size_t n, size_t n_components, const double* h_q, const double* h_f,
+                        double* h_q_out, double* h_f_out, double* h_loglik_or_null, uint32_t flags,
+                        const fmh_admix_tracks* tracks_or_null);   /* host only, no device */
+int fmh_admix_start(const uint32_t* h_called, const uint32_t* h_allele_count, size_t m, size_t n, size_t n_components, uint64_t seed, double* h_q,
+                    double* h_f);   /* host only, no device */
+int fmh_admix_accelerate(const double* h_q0, const double* h_f0, const double* h_q1, const double* h_f1, const double* h_q2, const double* h_f2,
+                         size_t n, size_t m, size_t n_components, double* h_qa, double* h_fa, double* h_alpha);   /* host only, no device */
+
 /* ---- haplotype homozygosity windows: Garud's H (an addition: the reference has none) -------------------------------------------
  * Which haplotypes are identical over a stretch of sites, from the bit-packed image.
  * A group is a 0/1 column mask with n >= 1 members (fmh_groups); members are ranked 0 .. n-1 by ascending column.  A window is a row range
@@ -1665,6 +1750,9 @@ int fmh_timing_read_gram(double* h_stage_ms /*[4]*/);
 /* Stage times of the calling thread's last fmh_grm while timing was enabled, ms by HIP events: [0] the codes kernel (with the plane flags),
  * [1] the Gram, [2] the slab reduce and the addition into the caller's matrix.  (Its eigen solver is fmh_timing_read_pca's [4].) */
 int fmh_timing_read_grm(double* h_stage_ms /*[3]*/);
+/* Stage times of the calling thread's last fmh_admix_step while timing was enabled, ms by HIP events: [0] the padded copies of Q and F,
+ * [1] the step kernel, [2] the reduce kernel (Q' and the log-likelihood). */
+int fmh_timing_read_admix(double* h_stage_ms /*[3]*/);
 
 #ifdef __cplusplus
 }
